@@ -28,14 +28,12 @@ from pathlib import Path
 
 import numpy as np
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")  # before HIP initialises: one hardware queue per pipeline stream
-
 ROOT = Path(__file__).resolve().parent
 for p in (ROOT, ROOT / "tests", ROOT / "oracle"):
     if str(p) not in sys.path:
         sys.path.insert(0, str(p))
 
-HBM_PEAK_GBS = 8000.0   # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 FP32_PEAK_TFLOPS = 157.3
 
 
@@ -275,6 +273,7 @@ def bench_wideband(args, torch, pkg, device) -> dict:
     dm.profile(0)
     ktimes = {k: v for k, v in (dm.profile_read() if not args.no_kernel_times else {}).items() if not k.startswith("gap:")}
     value = C * block * K / el / 1e6
+    dumped = dump_outputs(dm, args.dump_outputs) if args.dump_outputs else None
     return {
         "metric": "IQ MSamples/sec demodulated to stereo+RDS per GPU; channels @ real-time",
         "value": value, "unit": "MSa/s", "n_gpus": 1, "steps": K, "warmup": W, "ms_per_step": el / K * 1e3,
@@ -287,6 +286,7 @@ def bench_wideband(args, torch, pkg, device) -> dict:
         "realtime_factor": (n_in * K / el) / fs_in,
         "kernels_ms_per_step": {k: v[0] / max(v[1], 1) for k, v in ktimes.items()},
         "speculation": dm.spec_stats(),
+        **({"dumped_outputs": dumped} if dumped else {}),
     }
 
 
@@ -457,6 +457,42 @@ def launch_ranks(n: int) -> int:
     return rc
 
 
+DUMP_BUDGET_BYTES = 48 << 20     # --dump-outputs: the arrays' bytes, well inside the 64 MB the dump may take with its .npy headers
+DUMP_SAMPLE_SEED = 20240601      # which channels a too-large batch is sampled down to: fixed, so two builds dump the same channels
+
+
+def dump_outputs(dm, out_dir: str) -> dict:
+    """Write what a caller of the timed path receives for the newest block — stereo audio, RDS symbols and RDS bytes with their
+    per-channel counts (fmd_get_audio / fmd_get_rds_symbols / fmd_get_rds_bytes) — as <out_dir>/<name>.npy, float32 or float64.
+    Batches whose outputs exceed DUMP_BUDGET_BYTES are cut to a seeded, sorted sample of channels (channels.npy names them).
+    Symbol slots beyond a channel's count are zeroed (the library leaves them unwritten), as are byte slots by fmd_get_rds_bytes."""
+    audio = dm.audio()
+    syms, sym_counts = dm.rds_symbols()
+    rbytes, byte_counts = dm.rds_bytes()
+    n_ch = audio.shape[0]
+    per_ch = 4 * (audio[0].size + syms.shape[1] + rbytes.shape[1]) + 3 * 8
+    n_keep = min(n_ch, max(1, DUMP_BUDGET_BYTES // per_ch))
+    if n_keep < n_ch:
+        chans = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n_ch, size=n_keep, replace=False))
+    else:
+        chans = np.arange(n_ch)
+    for c in range(n_ch):
+        syms[c, sym_counts[c]:] = 0.0
+    arrays = {
+        "channels": chans.astype(np.float64),
+        "audio": audio[chans],                                   # [n, n_audio, 2] (L, R)
+        "rds_symbols": syms[chans],                              # [n, n_rds]
+        "rds_symbol_counts": sym_counts[chans].astype(np.float64),
+        "rds_bytes": rbytes[chans].astype(np.float32),           # [n, cap], 0..255
+        "rds_byte_counts": byte_counts[chans].astype(np.float64),
+    }
+    d = Path(out_dir)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(d / f"{name}.npy", np.ascontiguousarray(a))
+    return {"dir": str(d), "channels": int(n_keep), "of_channels": int(n_ch), "files": sorted(f"{k}.npy" for k in arrays)}
+
+
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -507,10 +543,17 @@ def main() -> None:
     ap.add_argument("--no-other-mode", action="store_true", help="skip the short run of the other arithmetic mode")
     ap.add_argument("--no-host-fed", action="store_true", help="skip the host-fed (PCIe-inclusive) extra line")
     ap.add_argument("--no-configs", action="store_true", help="skip the `configs` array (short runs of the other BASELINE configurations)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step (audio, RDS symbols, RDS bytes and their counts; "
+                         "a seeded sample of channels when they exceed 48 MB) as DIR/<name>.npy, float32 / float64.  --gpus 1 only")
     args = ap.parse_args()
     if args.exact and args.fast_math:
         raise SystemExit("bench.py: --exact and --fast-math exclude each other")
     args.fast_math = not args.exact
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit("bench.py: --dump-outputs needs --gpus 1 (the multi-GPU gather holds the outputs back a block)")
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
 
     # --gpus N without a launcher: start the ranks ourselves, as a CHILD process, before this process has touched the GPU
     # (no torch.cuda / HIP call has happened yet; a process that has initialised the GPU must never exec another program)
@@ -769,6 +812,8 @@ def main() -> None:
         # plain serial iteration, spans redone with the reference forms — same results either way
         "speculation": spec,
     }
+    if args.dump_outputs:
+        out["dumped_outputs"] = dump_outputs(dm, args.dump_outputs)
     dm.close()
     if world == 1 and not args.no_other_mode and not args.no_pipeline:
         # the same workload in the other arithmetic mode, timed the same way over at most 20 steps (no kernel timing events)

@@ -113,9 +113,9 @@ struct fmd_handle_s {
 namespace {
 
 // The pipeline keeps six streams busy beside the caller's; ROCm maps streams onto GPU_MAX_HW_QUEUES hardware queues (default
-// 4) and dependent stages sharing a queue block each other.  The library does not touch the process environment: the host
-// application sets GPU_MAX_HW_QUEUES >= 8 before the HIP runtime initialises, and fmd_create warns once on
-// stderr (and in fmd_last_error(NULL)) when it finds less.  FMD_QUIET=1 silences the warning.
+// 4) and dependent stages sharing a queue block each other.  The library does not touch the process environment (the host
+// application owns it); fmd_create warns once on stderr (and in fmd_last_error(NULL)) when the streams have
+// to share queues.  FMD_QUIET=1 silences the warning.
 void warn_hw_queues_once() {
     static bool done = false;
     if (done) return;
@@ -125,9 +125,8 @@ void warn_hw_queues_once() {
     if (n >= 7) return;
     const char* q = getenv("FMD_QUIET");
     if (q && *q && *q != '0') return;
-    fprintf(stderr, "libfmdemod: GPU_MAX_HW_QUEUES=%s: the pipelined demodulator uses up to 7 streams and loses its overlap on fewer hardware "
-                    "queues; set GPU_MAX_HW_QUEUES=16 in the environment before the HIP runtime initialises (8 if nothing else in the process "
-                    "creates streams; see INTEGRATION.md)\n", v ? v : "(unset, default 4)");
+    fprintf(stderr, "libfmdemod: GPU_MAX_HW_QUEUES=%s: the pipelined demodulator uses up to 7 streams and loses part of its overlap on fewer "
+                    "hardware queues (see INTEGRATION.md)\n", v ? v : "(unset, default 4)");
 }
 
 thread_local std::string g_create_error;

@@ -5,6 +5,8 @@ Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import 
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 from pathlib import Path
@@ -16,6 +18,7 @@ ORACLE_DIR = ROOT / "oracle"
 LIB_PATH = ORACLE_DIR / "liboracle.so"
 REF_DUMP = ORACLE_DIR / "_ref" / "fm_ref_dump"
 REF_BENCH = ORACLE_DIR / "_ref" / "fm_demod_benchmark"
+REF_RECORDS = ROOT / "tests" / "golden" / "ref_records.json"
 
 
 class Controls(C.Structure):
@@ -250,6 +253,18 @@ REF_FILES = {
 
 def have_ref() -> bool:
     return REF_DUMP.exists() and os.access(REF_DUMP, os.X_OK)
+
+
+def digest(a) -> str:
+    """dtype, size and sha256 of an array's bytes: equal digests <=> bit-identical arrays (what the recorded reference outputs hold)."""
+    a = np.ascontiguousarray(a)
+    return f"{a.dtype.str}:{a.size}:{hashlib.sha256(a.tobytes()).hexdigest()}"
+
+
+def ref_records() -> dict:
+    """Outputs of the compiled reference on the inputs of the tests that compare against it, recorded where it could be built
+    (tests/golden/make_ref_records.py): what those tests compare against where oracle/_ref is absent."""
+    return json.loads(REF_RECORDS.read_text())
 
 
 def run_ref_chain(capture: np.ndarray, tmpdir, block_size: int = 65536, u8: bool = True, extra_args=()) -> dict:

@@ -54,3 +54,51 @@ def test_the_traffic_table_is_tied_to_the_library_it_was_measured_on():
     # the committed table carries the stamp of the build its rows come from (tools/digest_round.py --install); bench.py prints
     # traffic_stale = (that stamp != this tree's)
     assert "kernel_source_stamp" in meta and len(meta["kernel_source_stamp"]) == 16
+
+
+class _FakeDemod:
+    """What dump_outputs() reads from a BatchDemod, with configs[2]'s shapes (4096 stations, 2048 audio frames a block)."""
+
+    def __init__(self, n_ch=4096, n_audio=2048, n_rds=160, cap=16):
+        import numpy as np
+        rng = np.random.default_rng(5)
+        self.a = rng.standard_normal((n_ch, n_audio, 2)).astype(np.float32)
+        self.s = rng.standard_normal((n_ch, n_rds)).astype(np.float32)
+        self.sc = rng.integers(0, n_rds + 1, n_ch).astype(np.int32)
+        self.b = rng.integers(0, 256, (n_ch, cap)).astype(np.uint8)
+        self.bc = rng.integers(0, cap + 1, n_ch).astype(np.int32)
+
+    def audio(self):
+        return self.a.copy()
+
+    def rds_symbols(self):
+        return self.s.copy(), self.sc.copy()
+
+    def rds_bytes(self):
+        return self.b.copy(), self.bc.copy()
+
+
+def test_dump_outputs_writes_a_fixed_sample_within_64_mb(tmp_path):
+    import numpy as np
+    b = _bench()
+    dm = _FakeDemod()
+    info = b.dump_outputs(dm, str(tmp_path / "a"))
+    b.dump_outputs(dm, str(tmp_path / "b"))
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == info["files"] == sorted(["channels.npy", "audio.npy", "rds_symbols.npy", "rds_symbol_counts.npy", "rds_bytes.npy",
+                                              "rds_byte_counts.npy"])
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64e6
+    for f in files:
+        x, y = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert x.dtype in (np.float32, np.float64) and x.tobytes() == y.tobytes(), f     # the same channels every time
+    ch = np.load(tmp_path / "a" / "channels.npy").astype(np.int64)
+    assert 0 < ch.size < 4096 and info["channels"] == ch.size and np.all(np.diff(ch) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "audio.npy"), dm.a[ch])
+    syms, cnt = np.load(tmp_path / "a" / "rds_symbols.npy"), np.load(tmp_path / "a" / "rds_symbol_counts.npy")
+    assert np.array_equal(cnt, dm.sc[ch])
+    for i, c in enumerate(ch[:64]):
+        assert np.array_equal(syms[i, : dm.sc[c]], dm.s[c, : dm.sc[c]]) and not syms[i, dm.sc[c]:].any()
+    assert np.array_equal(np.load(tmp_path / "a" / "rds_bytes.npy"), dm.b[ch].astype(np.float32))
+    # a batch that fits is dumped whole
+    small = b.dump_outputs(_FakeDemod(n_ch=40), str(tmp_path / "c"))
+    assert small["channels"] == 40 and np.array_equal(np.load(tmp_path / "c" / "channels.npy"), np.arange(40.0))

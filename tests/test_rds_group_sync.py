@@ -1,6 +1,7 @@
 """Host-side RDS group synchroniser (fm-radio_amd/host/rds_group_sync.hpp) against the reference's own
 RDS_Group_Sync + decoder log (oracle/_ref/fm_ref_dump stderr), on a clean and on a noisy capture (block errors, single-bit
-corrections, loss of sync and re-lock)."""
+corrections, loss of sync and re-lock).  Where oracle/_ref is absent, the reference's RDS bytes, group log and lock lines for the
+same two captures come from tests/golden/ref_records.json (tests/golden/make_ref_records.py)."""
 import re
 import subprocess
 from pathlib import Path
@@ -23,11 +24,28 @@ def _ref_log(cap, tmp):
     return groups, locks, np.fromfile(tmp / "out" / "rds_bytes.u8", dtype=np.uint8)
 
 
-@pytest.mark.skipif(not O.have_ref(), reason="oracle/_ref not built")
-@pytest.mark.parametrize("noise,seed", [(0.02, 21), (0.45, 22)])
+CASES = [(0.02, 21), (0.45, 22)]
+
+
+def capture(noise, seed) -> np.ndarray:
+    return synth.to_u8(synth.fm_capture(60 * 65536, seed=seed, noise_sigma=noise)["iq"])
+
+
+def record_key(noise, seed) -> str:
+    return f"rds_group_sync/noise={noise}/seed={seed}"
+
+
+def _reference(noise, seed, tmp):
+    """(group log lines, lock lines, RDS bytes) of the reference on the capture: live where oracle/_ref exists, else as recorded."""
+    if O.have_ref():
+        return _ref_log(capture(noise, seed), tmp)
+    rec = O.ref_records()[record_key(noise, seed)]
+    return rec["groups"], rec["locks"], np.frombuffer(bytes.fromhex(rec["rds_bytes_hex"]), dtype=np.uint8)
+
+
+@pytest.mark.parametrize("noise,seed", CASES)
 def test_group_sync_matches_reference(tmp_path, noise, seed):
-    cap = synth.to_u8(synth.fm_capture(60 * 65536, seed=seed, noise_sigma=noise)["iq"])
-    ref_groups, ref_locks, ref_bytes = _ref_log(cap, tmp_path)
+    ref_groups, ref_locks, ref_bytes = _reference(noise, seed, tmp_path)
     assert len(ref_groups) > 20
     exe = tmp_path / "group_sync_main"
     subprocess.run(["g++", "-O2", "-std=c++17", f"-I{ROOT / 'fm-radio_amd' / 'host'}", str(ROOT / "tests" / "cpp" / "group_sync_main.cpp"), "-o", str(exe)], check=True)

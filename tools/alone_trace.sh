@@ -1,8 +1,7 @@
 #!/bin/bash
 # Development tool (GPU box; needs the development build of the library: make -C fm-radio_amd/csrc dev): rocprofv3 kernel durations of single stages of the tolerance mode run on their own (FMD_DEBUG_SKIP_STAGES).
 cd /tmp && export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
-export GPU_MAX_HW_QUEUES=8
+R=$(cd "$(dirname "$0")/.." && pwd); cd $R
 for s in 56 41 49 31; do
   export FMD_DEBUG_SKIP_STAGES=$s
   rm -rf /tmp/alone_$s

@@ -3,7 +3,7 @@
 # (tools/collect_round.sh), the driver's command, the stages alone (development build of the library: tools/ab/dev.so, built by
 # `make -C fm-radio_amd/csrc dev`) and the measurement table.  ROUND=N (default 5).
 export ROUND=${ROUND:-5}
-R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
+R=$(cd "$(dirname "$0")/.." && pwd); cd $R
 O=gpurun_out/r${ROUND}_evidence; mkdir -p $O
 bash tools/collect_round.sh > $O/collect.log 2>&1
 python bench.py --steps 20 --warmup 5 > $O/bench_driver_style.json 2> $O/bench_driver_style.err

@@ -4,14 +4,13 @@
 # counter set, no tracing domains combined with --pmc.  BENCH_ARGS=--exact for the exact mode (SFX names another configuration's output).  Outputs: gpurun_out/r<ROUND>prof<sfx>/.
 set -u
 cd /tmp && export TMPDIR=/tmp
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 X="${BENCH_ARGS:-}"
 if [ -z "${SFX+x}" ]; then SFX=""; [ -n "$X" ] && SFX="_exact"; fi      # SFX=_1024k BENCH_ARGS="--fs 1024000": another configuration
 ROUND=${ROUND:-5}
 O=$R/gpurun_out/r${ROUND}prof$SFX
 rm -rf $O && mkdir -p $O
 cd $R
-export GPU_MAX_HW_QUEUES=8
 Q="--no-cpu-baseline --no-other-mode --no-configs --no-host-fed"
 python3 bench.py $X > $O/bench_default.json 2> $O/bench_default.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 bench.py $X $Q > $O/bench_under_rocprof.json 2> $O/stats.err

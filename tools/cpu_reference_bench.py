@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Time the REAL reference (oracle/_ref/fm_demod_benchmark, built from /root/reference by `make -C oracle ref`) on the
+"""Time the REAL reference (oracle/_ref/fm_demod_benchmark, built from the reference sources by `make -C oracle ref`) on the
 host cores: one process per core (the reference is single-threaded), each reading its own page-cached copy of a synthetic
 u8 capture at the reference's only rate (1.024 MSa/s), as BASELINE.md §3 plans.  Prints one JSON line."""
 import json

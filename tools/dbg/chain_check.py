@@ -1,7 +1,8 @@
 """Development check of k_chain (fmd_debug_set_chain): the one-launch form against the three-launch form and against the oracle, 256 kSa/s cf32.
 usage: chain_check.py [stations] [blocks]"""
 import sys, numpy as np
-sys.path[:0] = ["/root/repo", "/root/repo/tests", "/root/repo/oracle"]
+_R = __import__("pathlib").Path(__file__).resolve().parents[2]
+sys.path[:0] = [str(_R), str(_R / "tests"), str(_R / "oracle")]
 import fmradio_loader, synth, oraclelib as O
 from gpu_parity import lib_coeffs_to_oracle
 pkg = fmradio_loader.load()

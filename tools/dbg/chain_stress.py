@@ -1,7 +1,8 @@
 """Development: k_chain under repetition — fresh handles, a few blocks each, every block checked for NaNs in audio / RDS AGC state / symbol counts against the
 three-launch form.  Prints the first block that differs.  usage: chain_stress.py [repetitions] [stations]"""
 import sys, numpy as np
-sys.path[:0] = ["/root/repo", "/root/repo/tests", "/root/repo/oracle"]
+_R = __import__("pathlib").Path(__file__).resolve().parents[2]
+sys.path[:0] = [str(_R), str(_R / "tests"), str(_R / "oracle")]
 import fmradio_loader, synth, torch
 pkg = fmradio_loader.load()
 reps, n_ch = (int(sys.argv[1]) if len(sys.argv) > 1 else 30), (int(sys.argv[2]) if len(sys.argv) > 2 else 11)

@@ -1,6 +1,6 @@
 """Development tool: steady-state ms/step of the pipelined library (no event bracketing), several repeats."""
 import sys, time
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, str(__import__('pathlib').Path(__file__).resolve().parent.parent))
 import torch, fmradio_loader
 pkg = fmradio_loader.load()
 import bench

@@ -1,6 +1,5 @@
 #!/bin/bash
 # Measurement table: one line per configuration, on one box.  Output: gpurun_out/table/.
-export GPU_MAX_HW_QUEUES=8
 O=gpurun_out/table; mkdir -p $O
 run() { python bench.py $2 --no-cpu-baseline --no-other-mode --no-configs --no-host-fed 2>/dev/null | python -c "import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(json.dumps({'cfg': sys.argv[1], 'value': round(d['value']), 'ms': round(d['ms_per_step'],4), 'kernels': {k: round(v,3) for k,v in d['roofline']['kernels_ms_per_step'].items()}, 'spec': d.get('speculation', {}).get('pll', {}).get('samples_per_span')}))" "$1" | tee -a $O/table.jsonl; }
 rm -f $O/table.jsonl

@@ -1,6 +1,5 @@
 # Development (GPU box): the default bench lines of every profiled configuration again (bench.py changed, the counters did not)
-export GPU_MAX_HW_QUEUES=8
-R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
+R=$(cd "$(dirname "$0")/.." && pwd); cd $R
 run() { mkdir -p gpurun_out/r5prof$1; python3 bench.py $2 > gpurun_out/r5prof$1/bench_default.json 2> gpurun_out/r5prof$1/bench_default.err; tail -c 200 gpurun_out/r5prof$1/bench_default.json | head -c 100; echo; }
 run "" ""
 run _u8 "--u8"

@@ -1,5 +1,5 @@
 # Development (GPU box): every kernel of the wideband bench's last steps, whatever its namespace
-cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd); export TMPDIR=/tmp; cd "$R"
 rm -rf /tmp/tr; rocprofv3 --kernel-trace --output-format csv -d /tmp/tr -- python3 bench.py --no-cpu-baseline --wideband --no-kernel-times > /tmp/tr.json 2>/tmp/tr.err
 python3 - <<'PY'
 import csv, glob

@@ -3,9 +3,8 @@
 # form, with its counters.  Needs tools/ab/chain.so (development build: tools/build_variant.sh chain "") and tools/ab/cprobe.so
 # (tools/build_variant.sh cprobe "-DFMD_C_PROBE").  Output: gpurun_out/r6_chain/.
 set -u
-R=${GRAFT_REPO_ROOT:-/root/repo}
+R=$(cd "$(dirname "$0")/.." && pwd)
 cd $R
-export GPU_MAX_HW_QUEUES=8
 O=$R/gpurun_out/r6_chain; rm -rf $O; mkdir -p $O gpurun_out/ab
 L=fm-radio_amd/csrc/libfmdemod.so; cp $L /tmp/r6_orig.so
 Q="--no-cpu-baseline --no-other-mode --no-configs --no-host-fed"

@@ -1,7 +1,6 @@
 #!/bin/bash
 # Round 6: the HBM roof re-measured, then non-temporal IQ loads / audio stores as an A/B on one box.
 # Variants: tools/build_variant.sh ntXY "-DFMD_NT_IN=X -DFMD_NT_OUT=Y".  Output: gpurun_out/r6_nt/.
-export GPU_MAX_HW_QUEUES=8
 O=gpurun_out/r6_nt; mkdir -p $O
 tools/hbm_roof_probe 2>&1 | tee $O/hbm_roof_probe.txt
 rm -f gpurun_out/ab/table.txt

@@ -3,8 +3,8 @@
 # mode, with `gather_verified` and what the gather costs the step (against `--gather none`).  Two ranks on one device cannot form an RCCL communicator ("Duplicate GPU
 # detected"): the collective runs over gloo here — plumbing and bookkeeping, not xGMI; libfmdgather.so's same-device rotation is covered by tests/test_multi_gpu_host.py below.  No scaling figure: the first real 8-GPU run has
 # these lines to diverge from.  Output: gpurun_out/r6_two_rank/.
-R=${GRAFT_REPO_ROOT:-/root/repo}; cd $R
-export GPU_MAX_HW_QUEUES=8 HSA_ENABLE_IPC_MODE_LEGACY=0
+R=$(cd "$(dirname "$0")/.." && pwd); cd $R
+export HSA_ENABLE_IPC_MODE_LEGACY=0
 O=gpurun_out/r6_two_rank; rm -rf $O; mkdir -p $O
 P=29540
 for mode in none rotate root all; do
