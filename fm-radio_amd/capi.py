@@ -28,6 +28,17 @@ FMD_FLAG_PLL_LOW_WORK = 8
 FMD_FLAG_PLL_K8 = 16
 FMD_FLAG_PLL_STREAM_ORDER = 32
 FMD_FLAG_FAST_MATH = 64
+FMD_FLAG_RDS_DECODE = 128
+
+# include/fmdemod.h fmd_rds_db (the reference's RDS_Database + sync status, 120 bytes) and fmd_rds_group (4 x fmd_rds_block, 16 bytes)
+RDS_DB_DTYPE = np.dtype({
+    "names": ["service_name", "programme_type_name", "radio_text", "PI_code", "programme_type", "is_stereo", "is_music",
+              "is_artificial_head", "is_compressed", "is_dynamic_program_type", "day", "month", "year", "hour", "minute",
+              "local_time_offset", "traffic_announcement", "in_sync", "groups", "sync_acquisitions"],
+    "formats": ["S8", "S8", "S64", "<u2", "u1", "u1", "u1", "u1", "u1", "u1", "<i4", "<i4", "<i4", "u1", "u1", "i1", "u1", "<i4", "<u4", "<u4"],
+    "offsets": [0, 8, 16, 80, 82, 83, 84, 85, 86, 87, 88, 92, 96, 100, 101, 104, 105, 108, 112, 116],
+    "itemsize": 120})
+RDS_GROUP_DTYPE = np.dtype([("data", "<u2", (4,)), ("block_type", "u1", (4,)), ("is_valid", "u1", (4,))])   # a view, see _groups_view
 FMD_OK, FMD_ERR_ARG, FMD_ERR_SIZE, FMD_ERR_DEVICE, FMD_ERR_NO_DEVICE, FMD_ERR_NAME, FMD_ERR_STATE = 0, -1, -2, -3, -4, -5, -6
 FMD_OUTPUT_LIFETIME_BLOCKS = 5   # include/fmdemod.h; checked against the loaded library in load_library()
 
@@ -170,6 +181,8 @@ def load_library():
     L.fmd_chan_last_error.restype = C.c_char_p
     L.fmd_chan_last_error.argtypes = [C.c_void_p]
     L.fmd_last_error.restype = C.c_char_p
+    L.fmd_rdsdec_last_error.restype = C.c_char_p
+    L.fmd_rdsdec_last_error.argtypes = [C.c_void_p]
     L.fmd_last_error.argtypes = [H]
     if L.fmd_output_lifetime_blocks() != FMD_OUTPUT_LIFETIME_BLOCKS:
         raise RuntimeError("libfmdemod.so and capi.py disagree on FMD_OUTPUT_LIFETIME_BLOCKS")
@@ -227,11 +240,96 @@ def default_config(n_channels: int, fs_baseband: int = 1_024_000) -> "Config":
     return cfg
 
 
+def _groups_view(raw: np.ndarray) -> np.ndarray:
+    """uint8 [..., 16] group records -> RDS_GROUP_DTYPE [...] (the C layout interleaves data / type / valid per block)."""
+    blocks = raw.reshape(raw.shape[:-1] + (4, 4))
+    out = np.empty(raw.shape[:-1], RDS_GROUP_DTYPE)
+    out["data"] = blocks[..., 0].astype(np.uint16) | (blocks[..., 1].astype(np.uint16) << 8)
+    out["block_type"] = blocks[..., 2]
+    out["is_valid"] = blocks[..., 3]
+    return out
+
+
+def _groups_lists(raw: np.ndarray, counts: np.ndarray) -> list:
+    return [_groups_view(raw[c, : int(counts[c])]) for c in range(raw.shape[0])]
+
+
+class RDSDecoder:
+    """Standalone batched RDS decoding chain on the GPU (fmd_rdsdec_*): the reference's RDS_Decoding_Chain for C byte streams from
+    any source (a demodulator's RDS bytes, the scraper's _rds.bin files).  State carries over between process() calls."""
+
+    def __init__(self, n_channels: int, device: int = -1):
+        self.L = load_library()
+        self.d = C.c_void_p()
+        rc = self.L.fmd_rdsdec_create(n_channels, device, C.byref(self.d))
+        if rc != FMD_OK:
+            self.d = None
+            raise FmdError(rc, self.L.fmd_rdsdec_last_error(None).decode() or self.L.fmd_status_string(rc).decode())
+        self.n_channels = n_channels
+        self._gcap = 0
+
+    def close(self):
+        if getattr(self, "d", None):
+            self.L.fmd_rdsdec_destroy(self.d)
+            self.d = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc != FMD_OK:
+            raise FmdError(rc, (self.L.fmd_rdsdec_last_error(self.d) or b"").decode() or self.L.fmd_status_string(rc).decode())
+
+    def reset(self):
+        self._check(self.L.fmd_rdsdec_reset(self.d))
+
+    def reset_db(self, channel: int = -1):
+        self._check(self.L.fmd_rdsdec_reset_db(self.d, channel))
+
+    def process(self, data: np.ndarray, counts) -> None:
+        """data: uint8 [C, cap] host array, counts[c] bytes of row c (any number 0..cap).  Synchronous."""
+        data = np.ascontiguousarray(data, dtype=np.uint8)
+        counts = np.ascontiguousarray(counts, dtype=np.int32)
+        assert data.ndim == 2 and data.shape[0] == self.n_channels and counts.shape == (self.n_channels,)
+        self._check(self.L.fmd_rdsdec_process_host(self.d, data.ctypes.data_as(C.c_void_p), counts.ctypes.data_as(C.c_void_p), data.shape[1]))
+        self._gcap = self.L.fmd_rdsdec_groups_cap(data.shape[1])
+
+    def process_tensor(self, data, counts, stream=None) -> None:
+        """data: torch uint8 [C, cap] and counts int32 [C] on the device; asynchronous on `stream` (default: torch's current stream)."""
+        import torch
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        assert data.is_contiguous() and counts.is_contiguous() and data.dtype == torch.uint8 and counts.dtype == torch.int32
+        self._check(self.L.fmd_rdsdec_process_dev(self.d, C.c_void_p(data.data_ptr()), C.c_void_p(counts.data_ptr()), data.shape[1], C.c_void_p(s)))
+        self._gcap = self.L.fmd_rdsdec_groups_cap(data.shape[1])
+
+    def db(self) -> np.ndarray:
+        """RDS_DB_DTYPE [C]: every channel's database after the last call."""
+        out = np.zeros(self.n_channels, RDS_DB_DTYPE)
+        self._check(self.L.fmd_rdsdec_get_db(self.d, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def groups_raw(self) -> tuple[np.ndarray, np.ndarray]:
+        """(uint8 [C, cap, 16] group records in the C layout, counts [C]) of the last call."""
+        cap = max(self._gcap, 1)
+        raw = np.zeros((self.n_channels, cap, 16), np.uint8)
+        counts = np.zeros(self.n_channels, np.int32)
+        self._check(self.L.fmd_rdsdec_get_groups(self.d, raw.ctypes.data_as(C.c_void_p), cap, counts.ctypes.data_as(C.c_void_p)))
+        return raw, counts
+
+    def groups(self) -> list:
+        """Per channel the groups the last call delivered, RDS_GROUP_DTYPE [n]."""
+        return _groups_lists(*self.groups_raw())
+
+
 class BatchDemod:
     """C broadcast-FM demodulators advanced in lock-step on one MI355X."""
 
     def __init__(self, n_channels: int, block_size: int = 65536, fs_baseband: int = 1_024_000, device: int = -1, keep_taps: bool = False,
-                 pipelined: bool = True, pll_kernel: str = "auto", pll_stream_order: bool = False, fast_math: bool = False):
+                 pipelined: bool = True, pll_kernel: str = "auto", pll_stream_order: bool = False, fast_math: bool = False,
+                 rds_decode: bool = False):
         self.L = load_library()
         self.h = C.c_void_p()
         flags = (FMD_FLAG_KEEP_TAPS if keep_taps else 0) | (0 if pipelined else FMD_FLAG_NO_PIPELINE)
@@ -239,6 +337,7 @@ class BatchDemod:
                   "low_work": FMD_FLAG_PLL_LOW_WORK}[pll_kernel]
         flags |= FMD_FLAG_PLL_STREAM_ORDER if pll_stream_order else 0
         flags |= FMD_FLAG_FAST_MATH if fast_math else 0
+        flags |= FMD_FLAG_RDS_DECODE if rds_decode else 0
         cfg = Config(n_channels, block_size, fs_baseband, device, flags)
         rc = self.L.fmd_create(C.byref(cfg), C.byref(self.h))
         if rc != FMD_OK:
@@ -250,6 +349,8 @@ class BatchDemod:
         self._check(self.L.fmd_get_rates(self.h, C.byref(r)))
         self.rates = r
         self.bytes_cap = 16 * (r.n_rds // 256 + 1)
+        self.groups_cap = self.bytes_cap * 8 // 79 + 2     # fmd_rds_groups_dev's cap (k_rds_decode: one group per >= 79 new bits)
+        self.rds_decode = rds_decode
 
     def close(self):
         if getattr(self, "h", None):
@@ -407,6 +508,27 @@ class BatchDemod:
         self._check(self.L.fmd_get_rds_bytes(self.h, b.ctypes.data_as(C.c_void_p), self.bytes_cap, counts.ctypes.data_as(C.c_void_p)))
         return b, counts
 
+    def rds_db(self) -> np.ndarray:
+        """App::GetRDSDatabase() per channel after the newest block (FMD_FLAG_RDS_DECODE): RDS_DB_DTYPE [C]."""
+        out = np.zeros(self.n_channels, RDS_DB_DTYPE)
+        self._check(self.L.fmd_get_rds_db(self.h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def rds_groups_raw(self) -> tuple[np.ndarray, np.ndarray]:
+        """(uint8 [C, groups_cap, 16] group records in the C layout, counts [C]) delivered in the newest block."""
+        raw = np.zeros((self.n_channels, self.groups_cap, 16), np.uint8)
+        counts = np.zeros(self.n_channels, np.int32)
+        self._check(self.L.fmd_get_rds_groups(self.h, raw.ctypes.data_as(C.c_void_p), self.groups_cap, counts.ctypes.data_as(C.c_void_p)))
+        return raw, counts
+
+    def rds_groups(self) -> list:
+        """Per channel the groups delivered in the newest block, RDS_GROUP_DTYPE [n]."""
+        return _groups_lists(*self.rds_groups_raw())
+
+    def reset_rds_db(self, channel: int = -1):
+        """RDS_Database::Reset() (the database only; sync state and A/B memories stay)."""
+        self._check(self.L.fmd_reset_rds_db(self.h, channel))
+
     def stream(self, name: str) -> np.ndarray:
         n = C.c_size_t(0)
         probe = np.empty(1, np.float32)
@@ -464,6 +586,31 @@ class BatchDemod:
         class _Arr:
             __cuda_array_interface__ = {"shape": (n,), "typestr": "<f4", "data": (p.value, False), "version": 2}
         return torch.as_tensor(_Arr(), device="cuda").view(self.n_channels, self.rates.n_audio, 2)
+
+    def rds_db_tensor(self):
+        """Zero-copy torch view of the newest block's databases: uint8 [C, 120] (fmd_rds_db_dev; RDS_DB_DTYPE after .cpu().numpy().view())."""
+        import torch
+        p = C.c_void_p()
+        self._check(self.L.fmd_rds_db_dev(self.h, C.byref(p)))
+        nC = self.n_channels
+
+        class _D:
+            __cuda_array_interface__ = {"shape": (nC * 120,), "typestr": "|u1", "data": (p.value, False), "version": 2}
+        return torch.as_tensor(_D(), device="cuda").view(nC, 120)
+
+    def rds_groups_tensors(self):
+        """Zero-copy torch views of the newest block's groups: (records [C, cap, 16] uint8, counts [C] int32) — fmd_rds_groups_dev."""
+        import torch
+        pg, pc, cap = C.c_void_p(), C.c_void_p(), C.c_int(0)
+        self._check(self.L.fmd_rds_groups_dev(self.h, C.byref(pg), C.byref(pc), C.byref(cap)))
+        nC = self.n_channels
+
+        class _G:
+            __cuda_array_interface__ = {"shape": (nC * cap.value * 16,), "typestr": "|u1", "data": (pg.value, False), "version": 2}
+
+        class _C:
+            __cuda_array_interface__ = {"shape": (nC,), "typestr": "<i4", "data": (pc.value, False), "version": 2}
+        return torch.as_tensor(_G(), device="cuda").view(nC, cap.value, 16), torch.as_tensor(_C(), device="cuda")
 
     def rds_bytes_tensors(self):
         """Zero-copy torch views of the newest block's RDS byte buffers: (bytes [C, cap] uint8, counts [C] int32) — fmd_rds_bytes_dev; same

@@ -161,7 +161,7 @@ int dev_alloc(fmd_handle h, T** p, size_t count) {
 }
 
 constexpr unsigned kKnownFlags = FMD_FLAG_KEEP_TAPS | FMD_FLAG_NO_PIPELINE | FMD_FLAG_PLL_TIME_PARALLEL | FMD_FLAG_PLL_LOW_WORK | FMD_FLAG_PLL_K8 |
-                                 FMD_FLAG_PLL_STREAM_ORDER | FMD_FLAG_FAST_MATH;
+                                 FMD_FLAG_PLL_STREAM_ORDER | FMD_FLAG_FAST_MATH | FMD_FLAG_RDS_DECODE;
 
 bool config_ok(const fmd_config* c, int* m) {
     if (!c || c->n_channels <= 0) return false;
@@ -570,6 +570,34 @@ void fill_ctx_coeffs(fmd_handle h) {
     x.loops.bpsk_b0 = k.bpsk_lpf_b[0]; x.loops.bpsk_b1 = k.bpsk_lpf_b[1]; x.loops.bpsk_a0 = k.bpsk_lpf_a[0];
 }
 
+// every channel's RDS decoder (k_rds_decode) as a freshly constructed RDS_Decoding_Chain; synchronises `s`
+hipError_t rds_dec_upload_initial(void* state, int C, hipStream_t s) {
+    std::vector<uint8_t> img(rds_dec_state_bytes(C));
+    const RdsDecBufs hs = rds_dec_bufs(img.data(), C);
+    for (int c = 0; c < C; c++) {
+        uint32_t f[RDS_F_NUM];
+        rds_dec_initial(f, hs.group + c, hs.db + c);
+        for (int i = 0; i < RDS_F_NUM; i++) hs.f[(size_t)i * C + c] = f[i];
+    }
+    hipError_t e = hipMemcpyAsync(state, img.data(), img.size(), hipMemcpyHostToDevice, s);
+    return e != hipSuccess ? e : hipStreamSynchronize(s);
+}
+
+// RDS_Database::Reset() (reference rds_database.h:58-79) of one channel or all (-1), the decoder idle: the database's fields only (the
+// synchroniser's status behind them and the handler's A/B memories stay)
+hipError_t rds_dec_reset_db(fmd_rds_db* d_db, int C, int channel) {
+    const int c0 = channel < 0 ? 0 : channel, n = channel < 0 ? C : 1;
+    std::vector<fmd_rds_db> v((size_t)n);
+    hipError_t e = hipMemcpy(v.data(), d_db + c0, sizeof(fmd_rds_db) * (size_t)n, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return e;
+    for (fmd_rds_db& r : v) {
+        fmd_rds_db z{};
+        z.in_sync = r.in_sync; z.groups = r.groups; z.sync_acquisitions = r.sync_acquisitions;
+        r = z;
+    }
+    return hipMemcpy(d_db + c0, v.data(), sizeof(fmd_rds_db) * (size_t)n, hipMemcpyHostToDevice);
+}
+
 int zero_history(fmd_handle h, hipStream_t s) {
     const Dims& d = h->ctx.d;
     Buffers& b = h->ctx.b;
@@ -589,7 +617,9 @@ int zero_history(fmd_handle h, hipStream_t s) {
         }
         HIP_TRY(h, hipMemsetAsync(b.rds_count[p], 0, sizeof(int) * (size_t)d.C, s));
         HIP_TRY(h, hipMemsetAsync(b.rds_bytes_count[p], 0, sizeof(int) * (size_t)d.C, s));
+        if (b.rds_groups_count[p]) HIP_TRY(h, hipMemsetAsync(b.rds_groups_count[p], 0, sizeof(int) * (size_t)d.C, s));
     }
+    if (h->ctx.rds_decode) HIP_TRY(h, rds_dec_upload_initial(h->ctx.rds_dec.f, d.C, s));
     HIP_TRY(h, launch_reset_state(h->ctx, s));
     // everything is idle here (callers synchronise first): restart the per-wavefront PLL hand-over chain, watchdog flag included
     if (b.pll_chain) HIP_TRY(h, hipMemsetAsync(b.pll_chain, 0, sizeof(unsigned) * ((size_t)h->pll_waves + 1 + (size_t)d.C + 2), s));      // (and the body hints behind it)
@@ -1108,6 +1138,7 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
     h->bytes_cap = 16 * (d.n_rds / 256 + 1);
     h->ctx.bytes_cap = h->bytes_cap;
     h->ctx.keep_taps = (cfg->flags & FMD_FLAG_KEEP_TAPS) ? 1 : 0;
+    h->ctx.rds_decode = (cfg->flags & FMD_FLAG_RDS_DECODE) ? 1 : 0;
     h->ctx.fast = (cfg->flags & FMD_FLAG_FAST_MATH) ? 1 : 0;
     if (const char* e = dev_env("FMD_DEBUG_SKIP_STAGES")) h->debug_skip = (unsigned)strtoul(e, nullptr, 0);   // development knob
     // fmd_submit_* puts a block's extract stage off until the next block's front end is queued (launch_deferred) from 1024 stations'
@@ -1160,6 +1191,14 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
         if (!rc) rc = dev_alloc(h, &b.rds_bytes[p], C * h->bytes_cap);
         if (!rc) rc = dev_alloc(h, &b.rds_bytes_count[p], C);
         if (!rc) rc = dev_alloc(h, &b.rds[p], C * d.n_rds);
+        if (!rc && h->ctx.rds_decode) rc = dev_alloc(h, &b.rds_db[p], C);
+        if (!rc && h->ctx.rds_decode) rc = dev_alloc(h, &b.rds_groups[p], C * (size_t)rds_groups_cap(h->bytes_cap));
+        if (!rc && h->ctx.rds_decode) rc = dev_alloc(h, &b.rds_groups_count[p], C);
+    }
+    if (!rc && h->ctx.rds_decode) {
+        uint8_t* st = nullptr;
+        rc = dev_alloc(h, &st, rds_dec_state_bytes(d.C));
+        if (!rc) h->ctx.rds_dec = rds_dec_bufs(st, d.C);
     }
     for (int p = 0; p < 2 && !rc; p++) rc = dev_alloc(h, &b.lmr_est[p], C * d.n_est);
     for (int p = 0; p < 2 && !rc && fast; p++) rc = dev_alloc(h, &b.pv_hist[p], C * 4);
@@ -1450,6 +1489,54 @@ int fmd_rds_bytes_dev(fmd_handle h, const uint8_t** d_bytes, const int** d_count
     return FMD_OK;
 }
 
+int fmd_get_rds_db(fmd_handle h, fmd_rds_db* db) {
+    if (!h || !db || !h->ctx.rds_decode) return FMD_ERR_ARG;
+    int rc = fmd_synchronize(h);
+    if (rc) return rc;
+    HIP_TRY(h, hipMemcpy(db, h->ctx.b.rds_db[h->out_slot], sizeof(fmd_rds_db) * (size_t)h->ctx.d.C, hipMemcpyDeviceToHost));
+    return FMD_OK;
+}
+
+int fmd_rds_db_dev(fmd_handle h, const fmd_rds_db** d_db) {
+    if (!h || !d_db || !h->ctx.rds_decode) return FMD_ERR_ARG;
+    { int rc = outputs_wanted(h); if (rc) return rc; }
+    *d_db = h->ctx.b.rds_db[h->out_slot];
+    return FMD_OK;
+}
+
+int fmd_get_rds_groups(fmd_handle h, fmd_rds_group* groups, int cap_groups_per_channel, int* counts) {
+    if (!h || !groups || !counts || cap_groups_per_channel < 0 || !h->ctx.rds_decode) return FMD_ERR_ARG;
+    int rc = fmd_synchronize(h);
+    if (rc) return rc;
+    const int C = h->ctx.d.C, gcap = rds_groups_cap(h->bytes_cap);
+    std::vector<fmd_rds_group> tmp((size_t)C * gcap);
+    HIP_TRY(h, hipMemcpy(tmp.data(), h->ctx.b.rds_groups[h->out_slot], sizeof(fmd_rds_group) * tmp.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(counts, h->ctx.b.rds_groups_count[h->out_slot], sizeof(int) * (size_t)C, hipMemcpyDeviceToHost));
+    for (int c = 0; c < C; c++) {
+        const int n = std::min(counts[c], std::min(cap_groups_per_channel, gcap));
+        std::memcpy(groups + (size_t)c * cap_groups_per_channel, tmp.data() + (size_t)c * gcap, sizeof(fmd_rds_group) * (size_t)n);
+    }
+    return FMD_OK;
+}
+
+int fmd_rds_groups_dev(fmd_handle h, const fmd_rds_group** d_groups, const int** d_counts, int* cap_groups_per_channel) {
+    if (!h || !d_groups || !d_counts || !cap_groups_per_channel || !h->ctx.rds_decode) return FMD_ERR_ARG;
+    { int rc = outputs_wanted(h); if (rc) return rc; }
+    *d_groups = h->ctx.b.rds_groups[h->out_slot];
+    *d_counts = h->ctx.b.rds_groups_count[h->out_slot];
+    *cap_groups_per_channel = rds_groups_cap(h->bytes_cap);
+    return FMD_OK;
+}
+
+int fmd_reset_rds_db(fmd_handle h, int channel) {
+    if (!h || !h->ctx.rds_decode || channel < -1 || channel >= h->cfg.n_channels) return FMD_ERR_ARG;
+    HIP_TRY(h, hipSetDevice(h->device));
+    int rc = sync_all(h);
+    if (rc) return rc;
+    HIP_TRY(h, rds_dec_reset_db(h->ctx.rds_dec.db, h->ctx.d.C, channel));
+    return FMD_OK;
+}
+
 int fmd_get_stream(fmd_handle h, const char* name, float* out, size_t cap_floats, size_t* n_floats) {
     if (!h || !name) return FMD_ERR_ARG;
     const Dims& d = h->ctx.d;
@@ -1550,7 +1637,9 @@ size_t state_floats(fmd_handle h) {
 }  // namespace
 }  // extern "C++"
 
-size_t fmd_state_size(fmd_handle h) { return h ? sizeof(StateHeader) + sizeof(float) * state_floats(h) : 0; }
+// FMD_FLAG_RDS_DECODE: the channel's RDS decoder behind the float state — its RDS_F_NUM synchroniser fields, the group being assembled, the database
+static constexpr size_t kRdsDecBlobBytes = RDS_F_NUM * sizeof(uint32_t) + sizeof(fmd_rds_group) + sizeof(fmd_rds_db);
+size_t fmd_state_size(fmd_handle h) { return h ? sizeof(StateHeader) + sizeof(float) * state_floats(h) + (h->ctx.rds_decode ? kRdsDecBlobBytes : 0) : 0; }
 
 int fmd_get_state(fmd_handle h, int channel, void* blob, size_t cap_bytes) {
     if (!h || !blob) return FMD_ERR_ARG;
@@ -1580,6 +1669,14 @@ int fmd_get_state(fmd_handle h, int channel, void* blob, size_t cap_bytes) {
     for (const StatePart& p : state_parts(h)) {
         HIP_TRY(h, hipMemcpy(out, p.base + (size_t)channel * p.stride, sizeof(float) * p.floats, hipMemcpyDeviceToHost));
         out += p.floats;
+    }
+    if (h->ctx.rds_decode) {
+        const RdsDecBufs& r = h->ctx.rds_dec;
+        uint8_t* o = reinterpret_cast<uint8_t*>(out);
+        HIP_TRY(h, hipMemcpy2D(o, sizeof(uint32_t), r.f + channel, sizeof(uint32_t) * (size_t)d.C, sizeof(uint32_t), RDS_F_NUM, hipMemcpyDeviceToHost));
+        o += RDS_F_NUM * sizeof(uint32_t);
+        HIP_TRY(h, hipMemcpy(o, r.group + channel, sizeof(fmd_rds_group), hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(o + sizeof(fmd_rds_group), r.db + channel, sizeof(fmd_rds_db), hipMemcpyDeviceToHost));
     }
     return FMD_OK;
 }
@@ -1614,6 +1711,14 @@ int fmd_set_state(fmd_handle h, int channel, const void* blob, size_t n_bytes) {
     for (const StatePart& p : state_parts(h)) {
         HIP_TRY(h, hipMemcpy(p.base + (size_t)channel * p.stride, in, sizeof(float) * p.floats, hipMemcpyHostToDevice));
         in += p.floats;
+    }
+    if (h->ctx.rds_decode) {
+        const RdsDecBufs& r = h->ctx.rds_dec;
+        const uint8_t* i8 = reinterpret_cast<const uint8_t*>(in);
+        HIP_TRY(h, hipMemcpy2D(r.f + channel, sizeof(uint32_t) * (size_t)d.C, i8, sizeof(uint32_t), sizeof(uint32_t), RDS_F_NUM, hipMemcpyHostToDevice));
+        i8 += RDS_F_NUM * sizeof(uint32_t);
+        HIP_TRY(h, hipMemcpy(r.group + channel, i8, sizeof(fmd_rds_group), hipMemcpyHostToDevice));
+        HIP_TRY(h, hipMemcpy(r.db + channel, i8 + sizeof(fmd_rds_group), sizeof(fmd_rds_db), hipMemcpyHostToDevice));
     }
     return FMD_OK;
 }
@@ -1810,5 +1915,157 @@ int fmd_profile_read(fmd_handle h, fmd_kernel_time* out, int cap, int* n_out) {
 }
 
 const char* fmd_last_error(fmd_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Standalone batched RDS decoder (RDS_Decoding_Chain::Process for C byte streams): the handle's k_rds_decode on the caller's bytes.
+struct fmd_rdsdec_s {
+    int C = 0, device = 0;
+    hipStream_t own = nullptr;
+    hipEvent_t done = nullptr;            // behind the newest launch: the next call (whatever its stream) and the getters wait for it
+    uint8_t* state = nullptr;
+    RdsDecBufs st{};
+    fmd_rds_db* db = nullptr;             // [C] snapshot after the newest call
+    fmd_rds_group* groups = nullptr;      // [C][gcap] groups of the newest call
+    int* counts = nullptr;                // [C]
+    size_t groups_alloc = 0;              // groups allocated
+    int gcap = 0;                         // groups per channel of the newest call
+    uint8_t* stage = nullptr; size_t stage_bytes = 0;   // device staging of the host entry point: the bytes, then the counts
+    std::string err;
+};
+
+static int rdsdec_fail(fmd_rdsdec d, int code, const char* what, hipError_t e) {
+    d->err = std::string(what) + ": " + hipGetErrorString(e);
+    return code;
+}
+#define RDSDEC_TRY(d, expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) return rdsdec_fail((d), FMD_ERR_DEVICE, #expr, e_); } while (0)
+
+int fmd_rdsdec_groups_cap(int cap_bytes_per_channel) { return cap_bytes_per_channel < 0 ? 0 : rds_groups_cap(cap_bytes_per_channel); }
+
+int fmd_rdsdec_create(int n_channels, int device, fmd_rdsdec* out) {
+    if (!out || n_channels <= 0) return FMD_ERR_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return FMD_ERR_NO_DEVICE;
+    if (device < 0 && hipGetDevice(&device) != hipSuccess) return FMD_ERR_NO_DEVICE;
+    if (device >= ndev) return FMD_ERR_ARG;
+    fmd_rdsdec d = new (std::nothrow) fmd_rdsdec_s;
+    if (!d) return FMD_ERR_ARG;
+    d->C = n_channels;
+    d->device = device;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d->own, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&d->done, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d->state), rds_dec_state_bytes(n_channels));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d->db), sizeof(fmd_rds_db) * (size_t)n_channels);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d->counts), sizeof(int) * (size_t)n_channels);
+    if (e == hipSuccess) e = hipMemsetAsync(d->counts, 0, sizeof(int) * (size_t)n_channels, d->own);
+    if (e == hipSuccess) { d->st = rds_dec_bufs(d->state, n_channels); e = rds_dec_upload_initial(d->state, n_channels, d->own); }
+    if (e == hipSuccess) e = hipMemcpyAsync(d->db, d->st.db, sizeof(fmd_rds_db) * (size_t)n_channels, hipMemcpyDeviceToDevice, d->own);
+    if (e == hipSuccess) e = hipEventRecord(d->done, d->own);
+    if (e == hipSuccess) e = hipStreamSynchronize(d->own);
+    if (e != hipSuccess) {
+        g_create_error = std::string("fmd_rdsdec_create: ") + hipGetErrorString(e);
+        fmd_rdsdec_destroy(d);
+        return FMD_ERR_DEVICE;
+    }
+    *out = d;
+    return FMD_OK;
+}
+
+int fmd_rdsdec_destroy(fmd_rdsdec d) {
+    if (!d) return FMD_ERR_ARG;
+    (void)hipSetDevice(d->device);
+    if (d->done) (void)hipEventSynchronize(d->done);
+    for (void* p : {(void*)d->state, (void*)d->db, (void*)d->groups, (void*)d->counts}) if (p) (void)hipFree(p);
+    if (d->stage) (void)hipFree(d->stage);
+    if (d->done) (void)hipEventDestroy(d->done);
+    if (d->own) (void)hipStreamDestroy(d->own);
+    delete d;
+    return FMD_OK;
+}
+
+int fmd_rdsdec_reset(fmd_rdsdec d) {
+    if (!d) return FMD_ERR_ARG;
+    RDSDEC_TRY(d, hipSetDevice(d->device));
+    RDSDEC_TRY(d, hipEventSynchronize(d->done));
+    RDSDEC_TRY(d, rds_dec_upload_initial(d->state, d->C, d->own));
+    return FMD_OK;
+}
+
+int fmd_rdsdec_reset_db(fmd_rdsdec d, int channel) {
+    if (!d || channel < -1 || channel >= d->C) return FMD_ERR_ARG;
+    RDSDEC_TRY(d, hipSetDevice(d->device));
+    RDSDEC_TRY(d, hipEventSynchronize(d->done));
+    RDSDEC_TRY(d, rds_dec_reset_db(d->st.db, d->C, channel));
+    return FMD_OK;
+}
+
+int fmd_rdsdec_process_dev(fmd_rdsdec d, const uint8_t* d_bytes, const int* d_counts, int cap_bytes_per_channel, void* stream) {
+    if (!d || !d_bytes || !d_counts || cap_bytes_per_channel < 0) return FMD_ERR_ARG;
+    RDSDEC_TRY(d, hipSetDevice(d->device));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int gcap = rds_groups_cap(cap_bytes_per_channel);
+    const size_t need = (size_t)d->C * gcap;
+    if (need > d->groups_alloc) {       // the previous call's kernel may still write the old records: wait for it before freeing them
+        RDSDEC_TRY(d, hipEventSynchronize(d->done));
+        if (d->groups) RDSDEC_TRY(d, hipFree(d->groups));
+        d->groups = nullptr;
+        d->groups_alloc = 0;
+        RDSDEC_TRY(d, hipMalloc(reinterpret_cast<void**>(&d->groups), sizeof(fmd_rds_group) * need));
+        d->groups_alloc = need;
+    }
+    RDSDEC_TRY(d, hipStreamWaitEvent(s, d->done, 0));   // consecutive calls update the state in place: one after the other
+    RdsDecArgs a{d->C, d_bytes, d_counts, cap_bytes_per_channel, d->st, d->db, d->groups, d->counts, gcap};
+    RDSDEC_TRY(d, launch_rds_decode(a, s));
+    RDSDEC_TRY(d, hipEventRecord(d->done, s));
+    d->gcap = gcap;
+    return FMD_OK;
+}
+
+int fmd_rdsdec_process_host(fmd_rdsdec d, const uint8_t* bytes, const int* counts, int cap_bytes_per_channel) {
+    if (!d || !bytes || !counts || cap_bytes_per_channel < 0) return FMD_ERR_ARG;
+    RDSDEC_TRY(d, hipSetDevice(d->device));
+    RDSDEC_TRY(d, hipEventSynchronize(d->done));
+    const size_t nb = (size_t)d->C * cap_bytes_per_channel, off = (nb + 15) & ~(size_t)15, total = off + sizeof(int) * (size_t)d->C;
+    if (total > d->stage_bytes) {
+        if (d->stage) RDSDEC_TRY(d, hipFree(d->stage));
+        d->stage = nullptr;
+        d->stage_bytes = 0;
+        RDSDEC_TRY(d, hipMalloc(reinterpret_cast<void**>(&d->stage), total));
+        d->stage_bytes = total;
+    }
+    int* dc = reinterpret_cast<int*>(d->stage + off);
+    RDSDEC_TRY(d, hipMemcpyAsync(d->stage, bytes, nb, hipMemcpyHostToDevice, d->own));
+    RDSDEC_TRY(d, hipMemcpyAsync(dc, counts, sizeof(int) * (size_t)d->C, hipMemcpyHostToDevice, d->own));
+    int rc = fmd_rdsdec_process_dev(d, d->stage, dc, cap_bytes_per_channel, d->own);
+    if (rc) return rc;
+    RDSDEC_TRY(d, hipStreamSynchronize(d->own));
+    return FMD_OK;
+}
+
+int fmd_rdsdec_get_db(fmd_rdsdec d, fmd_rds_db* db) {
+    if (!d || !db) return FMD_ERR_ARG;
+    RDSDEC_TRY(d, hipSetDevice(d->device));
+    RDSDEC_TRY(d, hipEventSynchronize(d->done));
+    RDSDEC_TRY(d, hipMemcpy(db, d->db, sizeof(fmd_rds_db) * (size_t)d->C, hipMemcpyDeviceToHost));
+    return FMD_OK;
+}
+
+int fmd_rdsdec_get_groups(fmd_rdsdec d, fmd_rds_group* groups, int cap_groups_per_channel, int* counts) {
+    if (!d || !counts || cap_groups_per_channel < 0 || (!groups && cap_groups_per_channel > 0)) return FMD_ERR_ARG;
+    RDSDEC_TRY(d, hipSetDevice(d->device));
+    RDSDEC_TRY(d, hipEventSynchronize(d->done));
+    RDSDEC_TRY(d, hipMemcpy(counts, d->counts, sizeof(int) * (size_t)d->C, hipMemcpyDeviceToHost));
+    if (!d->groups) return FMD_OK;
+    std::vector<fmd_rds_group> tmp((size_t)d->C * d->gcap);
+    RDSDEC_TRY(d, hipMemcpy(tmp.data(), d->groups, sizeof(fmd_rds_group) * tmp.size(), hipMemcpyDeviceToHost));
+    for (int c = 0; c < d->C; c++) {
+        const int n = std::min(counts[c], std::min(cap_groups_per_channel, d->gcap));
+        if (n > 0) std::memcpy(groups + (size_t)c * cap_groups_per_channel, tmp.data() + (size_t)c * d->gcap, sizeof(fmd_rds_group) * (size_t)n);
+    }
+    return FMD_OK;
+}
+
+const char* fmd_rdsdec_last_error(fmd_rdsdec d) { return d ? d->err.c_str() : g_create_error.c_str(); }
 
 }  // extern "C"

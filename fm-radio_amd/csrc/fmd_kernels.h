@@ -189,6 +189,10 @@ struct Buffers {
     float*  lmr[kSlots];         // [C][n_audio]    (KEEP_TAPS)
     uint8_t* rds_bytes[kSlots];  // [C][bytes_cap]
     int*    rds_bytes_count[kSlots]; // [C]
+    // FMD_FLAG_RDS_DECODE only (null otherwise): k_rds_decode's outputs
+    fmd_rds_db*    rds_db[kSlots];            // [C]   database after the block
+    fmd_rds_group* rds_groups[kSlots];        // [C][rds_groups_cap(bytes_cap)]
+    int*           rds_groups_count[kSlots];  // [C]
     // per-channel controls
     float*  b_lpr;          // [C][128]
     float*  b_lmr;          // [C][128]
@@ -214,6 +218,49 @@ struct Buffers {
     unsigned long long* spec_stats;  // [8] speculation counters: pll {chunks, general, replayed, -}, rds {chunks, general, replayed, -}
 };
 
+// RDS decoding chain (k_rds_decode, fmd_kernels_rds.inc): per-channel state.  The synchroniser's scalars are planar [RDS_F_NUM][C]
+// (one coalesced load / store per field and launch); the group being assembled and the database are one record per channel.
+enum RdsDecField { RDS_F_WIN, RDS_F_SYN, RDS_F_HUNT, RDS_F_BITS, RDS_F_BLOCK, RDS_F_ERRORS, RDS_F_DESYNC, RDS_F_AB, RDS_F_NUM };
+// window (26 bits), its syndrome, 1 = FINDING_SYNC, bits into the block, curr_data_block, block errors in the group,
+// consecutive groups with errors, the handler's A/B memories (radio text | programme type name << 8; both start at 0b100)
+struct RdsDecBufs {
+    uint32_t* f;              // [RDS_F_NUM][C]
+    fmd_rds_group* group;     // [C]
+    fmd_rds_db* db;           // [C]
+};
+inline size_t rds_dec_state_bytes(int C) { return (size_t)C * (RDS_F_NUM * sizeof(uint32_t) + sizeof(fmd_rds_group) + sizeof(fmd_rds_db)); }
+// the three arrays inside one allocation of rds_dec_state_bytes(C)
+inline RdsDecBufs rds_dec_bufs(void* base, int C) {
+    RdsDecBufs s;
+    s.f = static_cast<uint32_t*>(base);
+    s.group = reinterpret_cast<fmd_rds_group*>(s.f + (size_t)RDS_F_NUM * C);
+    s.db = reinterpret_cast<fmd_rds_db*>(s.group + C);
+    return s;
+}
+// one channel's state as the fields of a freshly constructed RDS_Decoding_Chain
+inline void rds_dec_initial(uint32_t f[RDS_F_NUM], fmd_rds_group* group, fmd_rds_db* db) {
+    for (int i = 0; i < RDS_F_NUM; i++) f[i] = 0;
+    f[RDS_F_HUNT] = 1;
+    f[RDS_F_AB] = 0x4u | (0x4u << 8);
+    *group = fmd_rds_group{};
+    *db = fmd_rds_db{};
+}
+static_assert(sizeof(fmd_rds_db) == 120 && sizeof(fmd_rds_group) == 16, "fixed layouts of include/fmdemod.h");
+struct RdsDecArgs {
+    int C;
+    const uint8_t* bytes;     // [C][cap]
+    const int* counts;        // [C]
+    int cap;
+    RdsDecBufs st;
+    fmd_rds_db* db_out;       // [C]   snapshot after this launch's bytes
+    fmd_rds_group* groups_out;   // [C][groups_cap]
+    int* groups_count;        // [C]
+    int groups_cap;
+};
+inline int rds_groups_cap(int cap_bytes) { return cap_bytes * 8 / 79 + 2; }
+// t1: optional event that receives the kernel's end timestamp / completion (as FMD_LAUNCH's last-kernel event)
+hipError_t launch_rds_decode(const RdsDecArgs& a, hipStream_t s, hipEvent_t t1 = nullptr);
+
 // Batch size the latency/throughput switches are keyed on: the stages behind the first decimator cost the same at every input
 // rate; the decimator itself (m > 1) adds FIR work and HBM traffic that compete with the serial kernels (measured cross-overs: x 1.5).
 inline int effective_channels(const Dims& d) { return d.m == 1 ? d.C : d.C + d.C / 2; }
@@ -230,6 +277,8 @@ struct LaunchCtx {
     int deemph_in_tile;     // FMD_FLAG_FAST_MATH: the de-emphasis IIR runs inside k_front's tile (every filtering channel's pole <= 0.905, i.e. up to ~79 us)
     int split_front;        // fmd_debug_split_front: 1.024 / 2.048 MSa/s tolerance mode with k_predecim_mfma and k_front_mfma as two kernels (the parity check of k_front_pre_mfma)
     int bytes_cap;
+    int rds_decode;                       // FMD_FLAG_RDS_DECODE: k_rds_decode behind k_rds_sync (state in rds_dec)
+    RdsDecBufs rds_dec;
     int uniform_cutoffs;                  // every station has the same L+R / L-R cut-offs: one set of k_extract_bp's tap tables serves any of them
     int extract_pairing;                  // k_extract_bp with two stations per workgroup: 0 = where it pays (launch_extract_ta), 1 = wherever possible (tests), 2 = never
     int pll_time_parallel_max_channels;   // batches up to this size use the time-parallel PLL kernel, larger ones the low-work one

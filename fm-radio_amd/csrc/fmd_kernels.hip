@@ -3001,6 +3001,7 @@ __global__ __launch_bounds__(256) void k_hilbert(Dims d, const float* __restrict
 }
 
 #include "fmd_kernels_fast.inc"
+#include "fmd_kernels_rds.inc"
 
 __global__ void k_selftest_atan2(const float* __restrict__ y, const float* __restrict__ x, float* __restrict__ out,
                                  unsigned char* __restrict__ ok_out, size_t n, int table_form) {
@@ -3426,27 +3427,39 @@ hipError_t launch_stage_chain(const LaunchCtx& ctx, SlotRef r, const void* d_iq,
     return hipGetLastError();
 }
 
+// FMD_FLAG_RDS_DECODE: k_rds_decode on the block's bytes, right behind k_rds_sync on the same stream (which orders consecutive blocks'
+// decoder launches, the condition for its in-place state); it is then the stage's last kernel and carries its end event
+static hipError_t launch_stage_rds_decode(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    const Buffers& b = ctx.b;
+    RdsDecArgs a{ctx.d.C, b.rds_bytes[r.buf], b.rds_bytes_count[r.buf], ctx.bytes_cap, ctx.rds_dec, b.rds_db[r.buf], b.rds_groups[r.buf],
+                 b.rds_groups_count[r.buf], rds_groups_cap(ctx.bytes_cap)};
+    return launch_rds_decode(a, s, r.t1 ? r.t1 : r.done);
+}
+
 hipError_t launch_stage_rds(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
     const Dims& d = ctx.d;
     const Buffers& b = ctx.b;
+    const bool dec = ctx.rds_decode != 0;
     if (ctx.fast) {
         const bool partials = d.n_audio % 256 == 0;       // k_extract_bp ran and left the block's power as 2 partial sums per tile
         static const bool two_waves = dev_env("FMD_RDS_TWO_WAVES") != nullptr;      // (A/B hook: the two-wavefront form)
         if (partials && !two_waves) {      // the loop split over mixer, clock and dump wavefronts (fmd_kernels_fast.inc)
-            FMD_LAUNCH(r, true, true, k_rds_sync3, dim3(serial_waves(d)), dim3(5 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
+            FMD_LAUNCH(r, true, !dec, k_rds_sync3, dim3(serial_waves(d)), dim3(5 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
                        b.rds_raw_sym[r.buf], b.rds_count[r.buf], b.rds_bytes[r.buf], b.rds_bytes_count[r.buf], ctx.bytes_cap, ctx.keep_taps,
                        b.rds_pow[r.buf], 2 * (d.n_audio / 256));
-            return hipGetLastError();
+            return dec ? launch_stage_rds_decode(ctx, r, s) : hipGetLastError();
         }
-        FMD_LAUNCH(r, true, true, k_rds_sync<true>, dim3(serial_waves(d)), dim3(2 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
+        FMD_LAUNCH(r, true, !dec, k_rds_sync<true>, dim3(serial_waves(d)), dim3(2 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
                    b.rds_raw_sym[r.buf], b.rds_count[r.buf], b.rds_bytes[r.buf], b.rds_bytes_count[r.buf], ctx.bytes_cap, ctx.keep_taps,
                    partials ? b.rds_pow[r.buf] : (const float*)nullptr, 2 * (d.n_audio / 256), TapPtrs{});
     } else {
-        FMD_LAUNCH(r, true, true, k_rds_sync<false>, dim3(serial_waves(d)), dim3(2 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
+        FMD_LAUNCH(r, true, !dec, k_rds_sync<false>, dim3(serial_waves(d)), dim3(2 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
                    b.rds_raw_sym[r.buf], b.rds_count[r.buf], b.rds_bytes[r.buf], b.rds_bytes_count[r.buf], ctx.bytes_cap, ctx.keep_taps, (const float*)nullptr, 0,
                    tap_ptrs(ctx, r.buf));
     }
-    return hipGetLastError();
+    return dec ? launch_stage_rds_decode(ctx, r, s) : hipGetLastError();
 }
 
 template <typename InT, int TT = 512>

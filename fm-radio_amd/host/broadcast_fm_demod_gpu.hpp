@@ -10,6 +10,7 @@
 //   GetPilotOutput() / GetPLLOutput() / Get_PLL_*_Phase_Error_Output() (.h:244-248), GetBPSKSync().Get*() (bpsk_synchroniser.h:78-85): same names
 //   GetControls()                                                 GetControls() / ApplyControls()
 //   App::Process(span<const complex<uint8_t>>) (src/app.cpp:39-50)  App_GPU::Process(const uint8_t* iq, size_t n_samples)
+//   RDS_Database& App::GetRDSDatabase() (src/app.h:42)             RDS_Database_GPU& App_GPU::GetRDSDatabase() (FMD_FLAG_RDS_DECODE)
 //
 // Like the reference, observers run synchronously on the caller's thread inside Process (utility/observable.h:17-21),
 // wrong-sized blocks are dropped silently (broadcast_fm_demod.cpp:311-313) and outputs are views valid until the next
@@ -71,9 +72,10 @@ class Broadcast_FM_Demod_GPU {
         return {reinterpret_cast<const std::complex<float>*>(v.data()) + (size_t)c * n, (size_t)n};
     }
 public:
-    explicit Broadcast_FM_Demod_GPU(int _block_size, int _n_channels = 1, int fs_baseband = 1024000, bool keep_taps = true)
+    // extra_flags: further FMD_FLAG_* (App_GPU passes FMD_FLAG_RDS_DECODE)
+    explicit Broadcast_FM_Demod_GPU(int _block_size, int _n_channels = 1, int fs_baseband = 1024000, bool keep_taps = true, unsigned extra_flags = 0u)
         : n_channels(_n_channels), block_size(_block_size) {
-        fmd_config cfg{_n_channels, _block_size, fs_baseband, -1, keep_taps ? FMD_FLAG_KEEP_TAPS : 0u};
+        fmd_config cfg{_n_channels, _block_size, fs_baseband, -1, (keep_taps ? FMD_FLAG_KEEP_TAPS : 0u) | extra_flags};
         int rc = fmd_create(&cfg, &h);
         if (rc != FMD_OK) throw std::runtime_error(std::string("fmd_create: ") + fmd_last_error(nullptr));
         fmd_get_rates(h, &rates);
@@ -95,6 +97,9 @@ public:
     // 4. RDS synchronisation / 5. Audio mixing (reference getters .h:249-256)
     View<Frame> GetAudioOut(int c = 0) const { return {reinterpret_cast<const Frame*>(audio.data()) + (size_t)c * rates.n_audio, (size_t)rates.n_audio}; }
     View<float> GetRDSPredSymbols(int c = 0) const { return {rds_sym.data() + (size_t)c * rates.n_rds, (size_t)rds_count[c]}; }
+    // reference GetRDSRawSymbols() (.h:254): the symbols before the sign decision, as many as GetRDSPredSymbols (needs keep_taps)
+    View<std::complex<float>> GetRDSRawSymbols(int c = 0) { fetch("rds_raw_sym", rds_raw);
+        return {reinterpret_cast<const std::complex<float>*>(rds_raw.data()) + (size_t)c * rates.n_rds, (size_t)rds_count[c]}; }
     View<float> GetLPRAudioOutput(int c = 0) { fetch("lpr", lpr); return {lpr.data() + (size_t)c * rates.n_audio, (size_t)rates.n_audio}; }
     View<float> GetLMRAudioOutput(int c = 0) { fetch("lmr", lmr); return {lmr.data() + (size_t)c * rates.n_audio, (size_t)rates.n_audio}; }
     View<std::complex<float>> GetFMOutIQ(int c = 0) { fetch("fm_out_iq", fm_out_iq);
@@ -158,6 +163,52 @@ private:
     }
 };
 
+// reference AlternateFrequency / TrafficAnnouncement / RDS_Database (src/rds_decoder/rds_database.h:10-79), same field names.  alt_freqs stays
+// empty, as in the reference (its handler's OnAlternativeFrequencyCode is a TODO).  Reset() is the GUI's "Reset Database" button
+// (src/gui/render_rds_database.cpp:46): it clears this copy and the decoder's database (fmd_reset_rds_db); sync state and A/B memories stay.
+struct AlternateFrequency { enum Type { VHF, MF, LF }; Type type; uint32_t freq; };
+enum TrafficAnnouncement { NONE, EON_INFO, AWAIT_EON_ANNOUNCE, NOW_EON_ANNOUNCE };
+struct RDS_Database_GPU {
+    char service_name[8]{0};
+    char programme_type_name[8]{0};
+    char radio_text[64]{0};
+    uint8_t programme_type = 0;
+    uint16_t PI_code = 0;
+    bool is_stereo = false;
+    bool is_music = false;
+    bool is_artificial_head = false;
+    bool is_compressed = false;
+    bool is_dynamic_program_type = false;
+    std::vector<AlternateFrequency> alt_freqs;
+    struct datetime_t { int day = 0; int month = 0; int year = 0; uint8_t hour = 0; uint8_t minute = 0; } datetime;
+    int8_t local_time_offset = 0;
+    TrafficAnnouncement traffic_announcement = TrafficAnnouncement::NONE;
+
+    void Reset() {
+        const fmd_handle h = handle;
+        const int c = channel;
+        *this = RDS_Database_GPU{};
+        handle = h;
+        channel = c;
+        if (h) fmd_reset_rds_db(h, c);
+    }
+    void Assign(const fmd_rds_db& d) {
+        std::memcpy(service_name, d.service_name, 8);
+        std::memcpy(programme_type_name, d.programme_type_name, 8);
+        std::memcpy(radio_text, d.radio_text, 64);
+        programme_type = d.programme_type;
+        PI_code = d.PI_code;
+        is_stereo = d.is_stereo; is_music = d.is_music; is_artificial_head = d.is_artificial_head;
+        is_compressed = d.is_compressed; is_dynamic_program_type = d.is_dynamic_program_type;
+        datetime.day = d.datetime.day; datetime.month = d.datetime.month; datetime.year = d.datetime.year;
+        datetime.hour = d.datetime.hour; datetime.minute = d.datetime.minute;
+        local_time_offset = d.local_time_offset;
+        traffic_announcement = (TrafficAnnouncement)d.traffic_announcement;
+    }
+    fmd_handle handle = nullptr;   // the decoder this record mirrors (Reset)
+    int channel = 0;
+};
+
 // reference App (src/app.h:19-47, app.cpp:39-65): accumulate arbitrary-sized u8 IQ pieces into exactly one block
 // (ReconstructionBuffer semantics, utility/reconstruction_buffer.h:16-26), then run the demodulator on it.
 class App_GPU {
@@ -165,8 +216,12 @@ class App_GPU {
     std::vector<uint8_t> buf;   // [block_size][2]
     size_t length = 0;          // samples filled
     Broadcast_FM_Demod_GPU demod;
+    RDS_Database_GPU db;        // the reference App always runs its RDS_Decoding_Chain (src/app.cpp:19-34): so does this one
 public:
-    explicit App_GPU(int _block_size) : block_size(_block_size), buf((size_t)_block_size * 2), demod(_block_size, 1, 1024000) {}
+    explicit App_GPU(int _block_size)
+        : block_size(_block_size), buf((size_t)_block_size * 2), demod(_block_size, 1, 1024000, true, FMD_FLAG_RDS_DECODE) {
+        db.handle = demod.Handle();
+    }
     size_t Process(const uint8_t* iq, size_t n_samples) {
         size_t nb_read = 0;
         while (nb_read < n_samples) {
@@ -175,11 +230,19 @@ public:
             std::memcpy(buf.data() + 2 * length, iq + 2 * nb_read, 2 * take);
             length += take;
             nb_read += take;
-            if (length == (size_t)block_size) { demod.ProcessU8(buf.data(), (size_t)block_size); length = 0; }
+            if (length == (size_t)block_size) {
+                demod.ProcessU8(buf.data(), (size_t)block_size);
+                length = 0;
+                fmd_rds_db d;
+                if (fmd_get_rds_db(demod.Handle(), &d) != FMD_OK) throw std::runtime_error(std::string("fmd_get_rds_db: ") + fmd_last_error(demod.Handle()));
+                db.Assign(d);
+            }
         }
         return nb_read;
     }
     Broadcast_FM_Demod_GPU& GetFMDemod() { return demod; }
+    // reference App::GetRDSDatabase() (src/app.cpp:33-35): the database after the newest block
+    RDS_Database_GPU& GetRDSDatabase() { return db; }
     auto& OnAudioBlock() { return demod.OnAudioOut(); }
     auto& On_RDS_Bytes() { return demod.On_RDS_Bytes(); }
 };

@@ -265,7 +265,8 @@ const char* fmd_last_error(fmd_handle h);
  * channel — the member variables of one reference Broadcast_FM_Demod (broadcast_fm_demod.h:94-227) — as an opaque,
  * self-describing blob of fmd_state_size() bytes.  Both calls synchronise the handle first.  A blob can be restored into any
  * channel of any handle with the same fs_baseband; the restored channel then continues bit-identically.  Controls are not
- * part of the blob (fmd_get_controls / fmd_set_controls). */
+ * part of the blob (fmd_get_controls / fmd_set_controls).  With FMD_FLAG_RDS_DECODE the blob also holds the channel's RDS decoder
+ * (synchroniser, group under way, A/B memories, database): 168 bytes more, and only handles with the flag take it. */
 size_t fmd_state_size(fmd_handle h);
 int    fmd_get_state(fmd_handle h, int channel, void* blob, size_t cap_bytes);
 int    fmd_set_state(fmd_handle h, int channel, const void* blob, size_t n_bytes);
@@ -278,6 +279,81 @@ int fmd_get_rds_bytes(fmd_handle h, uint8_t* bytes, int cap_bytes_per_channel, i
 /* ... and as device views of the newest block (same lifetime rule as fmd_audio_dev): d_bytes [C][*cap_bytes_per_channel],
  * d_counts [C] — for hosts that fetch the outputs with their own asynchronous copies (fm-radio_amd/host/station_ring.hpp). */
 int fmd_rds_bytes_dev(fmd_handle h, const uint8_t** d_bytes, const int** d_counts, int* cap_bytes_per_channel);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * RDS decoding chain on the GPU (reference src/rds_decoder/rds_decoding_chain.h: RDS_Group_Sync -> RDS_Decoder ->
+ * RDS_Database_Decoder_Handler -> RDS_Database), one decoder per channel, fed with the Manchester decoder's bytes.
+ * Bit-identical to the reference: group sync on the CRC-10 offset words with single-bit correction
+ * (rds_group_sync.cpp:29-127, crc10.cpp:28-60), the group decoder (rds_decoder.cpp:82-540) and the database handler
+ * (rds_database_decoder_handler.cpp).  Kernel k_rds_decode (fmd_kernels_rds.inc).
+ * ------------------------------------------------------------------------------------------------------------------ */
+/* opt-in: the handle runs k_rds_decode behind its RDS stage (fmd_get_rds_db, fmd_get_rds_groups).  Without it nothing changes:
+ * no allocation, no launch, the same fmd_state_size. */
+#define FMD_FLAG_RDS_DECODE      128u
+
+/* reference enum TrafficAnnouncement (rds_database.h:20-25), in its order: the 0A group's TP << 1 | TA */
+enum { FMD_RDS_TA_NONE = 0, FMD_RDS_TA_EON_INFO = 1, FMD_RDS_TA_AWAIT_EON_ANNOUNCE = 2, FMD_RDS_TA_NOW_EON_ANNOUNCE = 3 };
+
+/* reference RDS_Database (rds_database.h:27-79) as a fixed-layout record (120 bytes); alt_freqs is left out because the
+ * reference's handler never fills it (OnAlternativeFrequencyCode is a TODO).  The last three fields are beyond the reference:
+ * the synchroniser's status. */
+typedef struct {
+    char     service_name[8];          /* PS, '\r' stored as 0 */
+    char     programme_type_name[8];   /* PTYN */
+    char     radio_text[64];           /* RT */
+    uint16_t PI_code;
+    uint8_t  programme_type;
+    uint8_t  is_stereo, is_music, is_artificial_head, is_compressed, is_dynamic_program_type;
+    struct { int32_t day, month, year; uint8_t hour, minute, pad_[2]; } datetime;
+    int8_t   local_time_offset;
+    uint8_t  traffic_announcement;     /* FMD_RDS_TA_* */
+    uint8_t  pad_[2];
+    int32_t  in_sync;                  /* 1: the group synchroniser is reading groups (READ_BLOCK), 0: it is hunting for block A */
+    uint32_t groups;                   /* groups delivered to the decoder since the decoder's reset */
+    uint32_t sync_acquisitions;        /* times the synchroniser locked onto a block A since the decoder's reset */
+} fmd_rds_db;
+
+/* reference rds_block_t / rds_group_t (rds_constants.h:30-39): block_type 0 A, 1 B, 2 C, 3 C' (C1), 4 D.  An invalid block keeps
+ * its uncorrected data and the type of the last offset word tried, as in the reference. */
+typedef struct { uint16_t data; uint8_t block_type; uint8_t is_valid; } fmd_rds_block;
+typedef struct { fmd_rds_block blocks[4]; } fmd_rds_group;
+
+/* App::GetRDSDatabase() (reference src/app.cpp:33-35, app.h:42) per channel, after the newest block: db [C] (host copy) / a device
+ * view [C] (same lifetime rule as fmd_rds_bytes_dev).  FMD_ERR_ARG without FMD_FLAG_RDS_DECODE. */
+int fmd_get_rds_db(fmd_handle h, fmd_rds_db* db);
+int fmd_rds_db_dev(fmd_handle h, const fmd_rds_db** d_db);
+/* the groups RDS_Group_Sync::OnGroup() delivered in the newest block (rds_group_sync.cpp:95): groups [C][cap_groups_per_channel],
+ * counts [C].  A channel delivers at most fmd_rds_groups_dev's *cap_groups_per_channel groups a block; a smaller cap truncates (counts
+ * stay the true numbers). */
+int fmd_get_rds_groups(fmd_handle h, fmd_rds_group* groups, int cap_groups_per_channel, int* counts);
+int fmd_rds_groups_dev(fmd_handle h, const fmd_rds_group** d_groups, const int** d_counts, int* cap_groups_per_channel);
+/* RDS_Database::Reset() (rds_database.h:58-79; the GUI's reset button, src/gui/render_rds_database.cpp:46) for one channel, or all
+ * with -1: clears the database only.  The synchroniser and the handler's A/B flag memories keep their state, as in the reference.
+ * Synchronises the handle; the next block's snapshot shows the cleared record. */
+int fmd_reset_rds_db(fmd_handle h, int channel);
+
+/* Standalone batched decoder: RDS_Decoding_Chain::Process (rds_decoding_chain.h:24-26) for n_channels independent byte streams,
+ * the counterpart of the reference's rds_decode tool (src/rds_decode.cpp).  Decodes bytes from any source (e.g. the scraper's
+ * _rds.bin files) with the same kernel.  State carries over from call to call; counts need not be multiples of 16. */
+typedef struct fmd_rdsdec_s* fmd_rdsdec;
+int fmd_rdsdec_create(int n_channels, int device, fmd_rdsdec* out);
+int fmd_rdsdec_destroy(fmd_rdsdec d);
+/* every channel back to the freshly constructed chain */
+int fmd_rdsdec_reset(fmd_rdsdec d);
+/* RDS_Database::Reset() for one channel (-1: all); see fmd_reset_rds_db */
+int fmd_rdsdec_reset_db(fmd_rdsdec d, int channel);
+/* d_bytes [C][cap_bytes_per_channel] on the device, d_counts [C] on the device (0 <= counts[c] <= cap).  Asynchronous on `stream`;
+ * the outputs (database after the call, groups delivered during it) are readable once the stream has reached this point.
+ * The group records of a call hold up to fmd_rdsdec_groups_cap(cap) groups per channel: enough for any count. */
+int fmd_rdsdec_process_dev(fmd_rdsdec d, const uint8_t* d_bytes, const int* d_counts, int cap_bytes_per_channel, void* stream);
+/* host buffers: copies, runs, synchronises */
+int fmd_rdsdec_process_host(fmd_rdsdec d, const uint8_t* bytes, const int* counts, int cap_bytes_per_channel);
+/* most groups one channel can deliver from cap_bytes new bytes (one group needs >= 79 new bits: 78 behind a re-lock) */
+int fmd_rdsdec_groups_cap(int cap_bytes_per_channel);
+/* host copies after the last process call (synchronise its stream first): db [C]; groups [C][cap_groups_per_channel], counts [C] */
+int fmd_rdsdec_get_db(fmd_rdsdec d, fmd_rds_db* db);
+int fmd_rdsdec_get_groups(fmd_rdsdec d, fmd_rds_group* groups, int cap_groups_per_channel, int* counts);
+const char* fmd_rdsdec_last_error(fmd_rdsdec d);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Wideband channeliser (SURVEY.md §8f row 3 / BASELINE configs[4]; NOT part of the reference, which tunes one station in

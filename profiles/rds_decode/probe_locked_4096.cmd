@@ -1,0 +1,1 @@
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/probe_locked_4096 -o run -- python3 tools/rds_decode_probe.py --channels 4096 --state locked --launches 200
