@@ -2,7 +2,6 @@
 // controls, device buffers and the per-block kernel launch sequence.  Host side only; the kernels are
 // in fmd_kernels.hip.  There is no CPU fallback: without a gfx950 device every call fails loudly.
 #include <hip/hip_runtime.h>
-#include <hip/hip_ext.h>
 
 #include <algorithm>
 #include <cstdarg>
@@ -32,7 +31,7 @@ static const char* const kStageName[ST_COUNT] = {"k_front", "k_deemphasis+k_hilb
 // ... and of the tolerance mode's kernels, as they appear in rocprofv3 kernel traces
 static const char* const kStageNameFast[ST_COUNT] = {"k_front_mfma", "k_deemphasis", "k_pilot_power", "k_pll_sparse", "k_extract_bp", "k_rds_sync", "k_predecim_mfma"};
 
-struct ProfiledBlock { hipEvent_t t0[ST_COUNT], t1[ST_COUNT]; bool used[ST_COUNT]; bool chain = false; };
+struct ProfiledBlock { hipEvent_t t0[ST_COUNT], t1[ST_COUNT]; bool used[ST_COUNT]; };
 
 struct fmd_handle_s {
     fmd_config cfg{};
@@ -71,14 +70,6 @@ struct fmd_handle_s {
     // Tolerance mode, fmd_submit_*: k_extract_bp shares k_front_mfma's stream and a block's extract + RDS stages are queued when the
     // NEXT block is submitted (behind that block's front end) or when somebody asks for the outputs — see process_dev
     bool lazy_extract = false, lazy_capable = false;
-    bool no_fused_pll = false;               // development A/B: the deferred pilot stage as a launch of its own
-    bool uniform_cutoffs = true;             // every station has the same L+R / L-R cut-offs (one set of tap tables): what k_chain needs of the controls
-    bool chain_off = true;                   // the one-launch form of a steady block (k_chain) is OFF unless fmd_debug_set_chain(h, 1) / FMD_CHAIN=1 (development builds) asks for it: measured slower, DESIGN.md section 3
-    long chain_blocks = 0;                   // blocks run as k_chain since create / reset
-    bool last_block_chain = false;
-    bool pll_eager = false;                  // development A/B: the pilot stage queued at submission on its own queue (round 3's arrangement)
-    bool split_queues = false;               // the front end's and the extract stage's queues on disjoint sets of CUs (hipExtStreamCreateWithCUMask): the two run side by side
-    bool front_with_predecim = true;         // 1.024 / 2.048 MSa/s, deferred schedule: the front end follows the first decimator on ITS queue
     // pll_pending: the block's pilot stage has not been queued either — it rides in the next block's front-end launch (k_front_mfma<FUSED>) or,
     // where that is not possible (a start-up block, the getters' per-sample streams, a flush), goes in front of the extract stage on its own;
     // front_dep: the event behind the stage that made the block's fm_out; pll_dep / pll_stream: where the pilot stage was queued (NULL event: same
@@ -353,9 +344,8 @@ int upload_controls(fmd_handle h, hipStream_t s) {
         }
         HIP_TRY(h, hipMemcpyAsync(b.aud_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipStreamSynchronize(s));
-        h->uniform_cutoffs = true;
-        for (int c = 1; c < C; c++) if (idx[(size_t)c * 2] != idx[0] || idx[(size_t)c * 2 + 1] != idx[1]) { h->uniform_cutoffs = false; break; }
-        h->ctx.uniform_cutoffs = h->uniform_cutoffs ? 1 : 0;
+        h->ctx.uniform_cutoffs = 1;
+        for (int c = 1; c < C; c++) if (idx[(size_t)c * 2] != idx[0] || idx[(size_t)c * 2 + 1] != idx[1]) { h->ctx.uniform_cutoffs = 0; break; }
     }
     HIP_TRY(h, hipMemcpyAsync(b.b_lpr, lpr.data(), lpr.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(b.b_lmr, lmr.data(), lmr.size() * 4, hipMemcpyHostToDevice, s));
@@ -633,7 +623,6 @@ int zero_history(fmd_handle h, hipStream_t s) {
     for (hipEvent_t& e : h->x_done) e = nullptr;
     h->ev_consumed = nullptr;
     h->out_slot = 0; h->sub_slot = 0; h->have_out = false; h->out_block = -1;
-    h->chain_blocks = 0; h->last_block_chain = false;
     h->epoch++;
     for (bool& u : h->slot_used) u = false;
     for (bool& u : h->consumer_pending) u = false;
@@ -674,7 +663,7 @@ int launch_deferred_pll(fmd_handle h, hipStream_t sP) {
 int launch_deferred(fmd_handle h, bool behind_front) {
     auto& q = h->deferred;
     if (!q.active) return FMD_OK;
-    hipStream_t sXq = (behind_front && !h->split_queues) ? h->sF : h->sX, sR = h->sR;
+    hipStream_t sXq = behind_front ? h->sF : h->sX, sR = h->sR;
     if (h->consumer_pending[q.slot]) {       // fmd_release_outputs: a consumer still reads this slot's old outputs
         HIP_TRY(h, hipStreamWaitEvent(sXq, h->ev_C[q.slot], 0));
         HIP_TRY(h, hipStreamWaitEvent(sR, h->ev_C[q.slot], 0));
@@ -809,7 +798,7 @@ int process_dev(fmd_handle h, const InT* d_iq, int n_channels, int n_samples, vo
     // Deferred schedule at 1.024 / 2.048 MSa/s: the front end (with the previous block's pilot stage riding it) follows the first
     // decimator on that queue, and the extract stages have the front end's queue to themselves: two queues that each run ahead,
     // instead of one on which k_extract_bp and the front end take turns while the decimator works beside both.
-    hipStream_t sFq = (lazy && h->ctx.d.m > 1 && sP != sF && h->ctx.fast && h->front_with_predecim) ? sP : sF;
+    hipStream_t sFq = (lazy && h->ctx.d.m > 1 && sP != sF && h->ctx.fast) ? sP : sF;
     hipStream_t s_first = predecim ? sP : sFq;     // the stream of the stage that reads the caller's input
     if (pipe) {
         // input is ready once everything queued so far on the caller's stream has run
@@ -826,47 +815,6 @@ int process_dev(fmd_handle h, const InT* d_iq, int n_channels, int n_samples, vo
     // the block after the last de-emphasised one: k_front maintains the Hilbert history (fo_tail) again and must not overwrite
     // what the previous block's k_hilbert, on its own stream, is still reading
     if (pipe && !h->ctx.any_deemph && h->last_block_deemph) HIP_TRY(h, hipStreamWaitEvent(sFq, h->ev_F[h->sub_slot], 0));
-    // Tolerance mode, 256 kSa/s cf32, a steady block: front end, pilot stage and extract stage as ONE launch (k_chain, fmd_kernels_chain.inc) on the
-    // front end's queue, the RDS stage behind it on its own.  Nothing of such a block is put off: its outputs are complete one launch and the
-    // RDS stage after its submission, and no kernel of it waits for another queue.  Start-up blocks, de-emphasised or differently filtered
-    // stations, u8 captures, FMD_FLAG_KEEP_TAPS and un-pipelined handles keep the three launches; both forms leave the same histories.
-    const bool chain = pipe && !u8 && !ref.warm && !h->chain_off && h->uniform_cutoffs && !h->ctx.any_deemph && !h->ctx.deemph_in_tile && !h->last_block_deemph &&
-                       !(h->debug_skip & ~(1u << ST_RDS)) && chain_possible(h->ctx);
-    if (chain) {
-        { int rc = launch_deferred(h, true); if (rc) return rc; }       // (a start-up block ahead of this one: its put-off stages first, in order on this queue)
-        if (h->consumer_pending[slot]) {
-            HIP_TRY(h, hipStreamWaitEvent(sF, h->ev_C[slot], 0));
-            HIP_TRY(h, hipStreamWaitEvent(sR, h->ev_C[slot], 0));
-            h->consumer_pending[slot] = false;
-        }
-        const int nx = (slot + 1) % kSlots;      // (the block writes the histories in front of the next slot's rows: see the pilot stage below)
-        if (h->slot_used[nx] && h->x_done[nx]) HIP_TRY(h, hipStreamWaitEvent(sF, h->x_done[nx], 0));      // (whichever queue that extract stage ran on)
-        if (h->last_p_event && h->last_p_stream != sF) HIP_TRY(h, hipStreamWaitEvent(sF, h->last_p_event, 0));
-        if (h->last_x_event && h->last_x_stream != sF) HIP_TRY(h, hipStreamWaitEvent(sF, h->last_x_event, 0));
-        SlotRef r = ref;
-        if (pm && prof_stage(ST_FRONT)) { r.t0 = pm->t0[ST_FRONT]; r.t1 = pm->t1[ST_FRONT]; pm->used[ST_FRONT] = true; pm->chain = true; }
-        if (!r.t1) r.done = h->ev_E[slot];
-        dep = r.t1 ? r.t1 : h->ev_E[slot];
-        e = launch_stage_chain(h->ctx, r, d_iq, sF);
-        if (e != hipSuccess) return fail(h, FMD_ERR_DEVICE, "k_chain launch: %s", hipGetErrorString(e));
-        if (ordered) HIP_TRY(h, hipStreamWaitEvent(s, dep, 0));          // the caller may reuse `iq` in stream order after this call
-        HIP_TRY(h, hipEventRecord(h->ev_F[slot], sF));                   // fmd_wait_input: an event that outlives this call
-        h->ev_consumed = h->ev_F[slot];
-        h->last_p_stream = sF; h->last_p_event = dep; h->last_x_stream = sF; h->last_x_event = dep; h->x_done[slot] = dep;
-        HIP_TRY(h, hipStreamWaitEvent(sR, dep, 0));
-        if ((e = run(ST_RDS, sR, launch_stage_rds, h->ev_X[slot])) != hipSuccess) return fail(h, FMD_ERR_DEVICE, "k_rds_sync launch: %s", hipGetErrorString(e));
-        if (dep != h->ev_X[slot]) HIP_TRY(h, hipEventRecord(h->ev_X[slot], sR));
-        h->last_block_deemph = false;
-        h->slot_used[slot] = true;
-        h->sub_slot = slot;
-        h->out_slot = slot; h->have_out = true; h->out_block = h->n_blocks;
-        h->n_blocks++;
-        h->chain_blocks++; h->last_block_chain = true;
-        h->last_stream = s;
-        poison.armed = false;
-        return FMD_OK;
-    }
-    h->last_block_chain = false;
     hipEvent_t input_done = nullptr;               // fires when the caller's buffer has been consumed
     if (predecim) {
         SlotRef r = ref;
@@ -887,9 +835,9 @@ int process_dev(fmd_handle h, const InT* d_iq, int n_channels, int n_samples, vo
         const SlotRef* ride = nullptr;
         auto& q = h->deferred;
         if (lazy && q.active && q.pll_pending && !q.ref.warm && !q.deemph && q.front_stream == sFq && !h->ctx.any_deemph && !h->ctx.b.fm_out_iq[q.slot] &&
-            !(h->debug_skip & ((1u << ST_PLL) | (1u << ST_FRONT))) && !h->no_fused_pll) {
+            !(h->debug_skip & ((1u << ST_PLL) | (1u << ST_FRONT)))) {
             ride = &q.ref;
-            q.pll_pending = false; q.pll_dep = (sFq != sF || h->split_queues) ? dep : nullptr; q.pll_stream = sFq;
+            q.pll_pending = false; q.pll_dep = (sFq != sF) ? dep : nullptr; q.pll_stream = sFq;
             if (h->last_p_event && h->last_p_stream != sFq) HIP_TRY(h, hipStreamWaitEvent(sFq, h->last_p_event, 0));
             h->last_p_stream = sFq; h->last_p_event = dep;          // (the launch's own event)
         }
@@ -926,7 +874,7 @@ int process_dev(fmd_handle h, const InT* d_iq, int n_channels, int n_samples, vo
     }
     const hipEvent_t fm_out_dep = dep;              // behind this event the block's fm_out is complete
     const bool fm_out_cross = h->ctx.any_deemph != 0 || sFq != sF;
-    const bool pll_now = !lazy || h->pll_eager;
+    const bool pll_now = !lazy;
     if (pll_now) {
     { int rc = launch_deferred_pll(h, sB); if (rc) return rc; }        // (the put-off block's pilot stage first)
     if (pipe) HIP_TRY(h, hipStreamWaitEvent(sB, dep, 0));
@@ -1073,46 +1021,19 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
     auto bail = [&](int rc) { g_create_error = h->err; fmd_destroy(h); return rc; };
     if (hipSetDevice(dev) != hipSuccess) return bail(fail(h, FMD_ERR_DEVICE, "hipSetDevice failed"));
     { hipError_t e = prepare_kernels(); if (e != hipSuccess) return bail(fail(h, FMD_ERR_DEVICE, "prepare_kernels: %s", hipGetErrorString(e))); }
-    // development switch FMD_CU_MASK_F / FMD_CU_MASK_X (hex words, 8 x 32 bits, e.g. ffff-ffff-...): the front end's queues and the extract
-    // stage's queue restricted to those CUs (tools/cumask_ab.sh)
-    std::vector<uint32_t> mask_f, mask_x;
-    auto parse_mask = [](const char* e, std::vector<uint32_t>& m) { while (e && *e) { char* end = nullptr; const unsigned long v = strtoul(e, &end, 16); if (!end || end == e) break; m.push_back((uint32_t)v); e = *end ? end + 1 : end; } };   // (any one non-hex character separates the words)
-    parse_mask(dev_env("FMD_CU_MASK_F"), mask_f); parse_mask(dev_env("FMD_CU_MASK_X"), mask_x);
-    h->split_queues = (!mask_f.empty() && !mask_x.empty()) || dev_env("FMD_SPLIT_QUEUES") != nullptr;     // FMD_SPLIT_QUEUES: the two-queue schedule on plain (unmasked) queues, with FMD_STREAM_PRIORITIES
-    { hipError_t e = !mask_f.empty() ? hipExtStreamCreateWithCUMask(&h->own_stream, (uint32_t)mask_f.size(), mask_f.data()) : hipStreamCreateWithFlags(&h->own_stream, hipStreamNonBlocking);
-      if (e != hipSuccess) return bail(fail(h, FMD_ERR_DEVICE, "stream: %s", hipGetErrorString(e))); }
-
-    h->pipelined = (cfg->flags & FMD_FLAG_NO_PIPELINE) == 0;
-    if (h->pipelined) warn_hw_queues_once();
-
     // (A CU-mask split between the serial and the FIR streams was measured: it shields the PLL wave from FIR waves
     //  sharing its SIMD — 3.06 -> 2.75 ms — but CU-masked streams did not overlap with each other on this runtime, so
     //  the step got slower overall.  Plain streams + s_setprio in the serial kernels it is.)
     // (the second PLL stream is own_stream: one more stream would be the ninth on the device with the caller's and would share a
     //  hardware queue with another stage; everything else own_stream does is preceded by a full synchronisation)
-    h->sB2 = h->own_stream;
-    {
-        // experiment hook: FMD_STREAM_PRIORITIES="f,b,x,r" — priorities of the front / PLL / extract / RDS streams (0 = default, negative = higher)
-        int prio[6] = {0, 0, 0, 0, 0, 0};       // sF, sD, sA, sB, sX, sR
-        if (const char* e = dev_env("FMD_STREAM_PRIORITIES")) { int f = 0, b = 0, x = 0, r = 0; if (std::sscanf(e, "%d%*c%d%*c%d%*c%d", &f, &b, &x, &r) == 4) { prio[0] = f; prio[1] = f; prio[3] = b; prio[4] = x; prio[5] = r; } }
-        int least = 0, greatest = 0;
-        (void)hipDeviceGetStreamPriorityRange(&least, &greatest);
-        int i = 0;
-        const int reserve_cus = dev_env("FMD_CU_RESERVE") ? atoi(dev_env("FMD_CU_RESERVE")) : 0;
-        for (hipStream_t* st : {&h->sF, &h->sD, &h->sA, &h->sB, &h->sX, &h->sR}) {
-            const int p = std::min(least, std::max(greatest, prio[i++]));
-            hipError_t e;
-            if (!mask_f.empty() && !mask_x.empty() && (st == &h->sF || st == &h->sX)) { const auto& mk = st == &h->sF ? mask_f : mask_x; e = hipExtStreamCreateWithCUMask(st, (uint32_t)mk.size(), mk.data()); }
-            else if (reserve_cus > 0) {      // (development: the RDS stage's queue on CUs 0 .. reserve - 1 of every XCD, every other queue on the rest)
-                uint32_t mk[8];
-                for (int w = 0; w < 8; w++) { const int lo = 32 * w; uint32_t v = 0; for (int b = 0; b < 32; b++) if (((lo + b) / 8 < reserve_cus) == (st == &h->sR)) v |= 1u << b; mk[w] = v; }
-                e = hipExtStreamCreateWithCUMask(st, 8, mk);
-            }
-            else e = p ? hipStreamCreateWithPriority(st, hipStreamNonBlocking, p) : hipStreamCreateWithFlags(st, hipStreamNonBlocking);
-            if (e != hipSuccess) return bail(fail(h, FMD_ERR_DEVICE, "stream: %s", hipGetErrorString(e)));
-        }
-        if (dev_env("FMD_STREAM_PRIORITIES")) std::fprintf(stderr, "fmdemod: stream priority range [%d (least) .. %d (greatest)]\n", least, greatest);
+    for (hipStream_t* st : {&h->own_stream, &h->sF, &h->sD, &h->sA, &h->sB, &h->sX, &h->sR}) {
+        hipError_t e = hipStreamCreateWithFlags(st, hipStreamNonBlocking);
+        if (e != hipSuccess) return bail(fail(h, FMD_ERR_DEVICE, "stream: %s", hipGetErrorString(e)));
     }
+    h->sB2 = h->own_stream;
+
+    h->pipelined = (cfg->flags & FMD_FLAG_NO_PIPELINE) == 0;
+    if (h->pipelined) warn_hw_queues_once();
     {
         std::vector<hipEvent_t*> evs = {&h->ev_in};
         for (int i = 0; i < kSlots; i++) { evs.push_back(&h->ev_P[i]); evs.push_back(&h->ev_F[i]); evs.push_back(&h->ev_A[i]); evs.push_back(&h->ev_B[i]); evs.push_back(&h->ev_E[i]); evs.push_back(&h->ev_X[i]); evs.push_back(&h->ev_C[i]); evs.push_back(&h->ev_D[i]); }
@@ -1131,7 +1052,6 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
     // 8 % faster at 2560 channels, 6 % at 3072), 8 lanes per channel (30 % fewer VALU instructions) beyond (2 % faster at 4096)
     h->ctx.pll_k16_max_channels = (cfg->flags & FMD_FLAG_PLL_K8) ? 0 : 3584;
     h->ctx.pll_unlocked_now = false; h->ctx.pll_launch_no = 0;
-    if (const char* e = dev_env("FMD_DEBUG_PLL_K16_MAX")) h->ctx.pll_k16_max_channels = atoi(e);   // development knob
     d.n_fm_in = d.N / m; d.n_fm_out = d.n_fm_in / 2; d.n_rds = d.n_fm_out / 8; d.n_audio = d.n_fm_out / 4;
     d.n_est = (d.n_audio + 9) / 10;
     d.tail_base = front_tail_len(m, (cfg->flags & FMD_FLAG_FAST_MATH) != 0);
@@ -1144,12 +1064,8 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
     // fmd_submit_* puts a block's extract stage off until the next block's front end is queued (launch_deferred) from 1024 stations'
     // worth of 256 kSa/s blocks on (same-box A/B with the three-wavefront RDS stage: +-0 at 1024 stations, +1 % at 1536, +6 % at 2048,
     // +10 % at 2560, +6-7 % from 3072 on; smaller batches are pure stage latency and keep every stage on a queue of its own)
-    h->lazy_capable = h->pipelined && h->ctx.fast && (size_t)d.C * d.n_fm_out >= (size_t)1024 * 8192 && !dev_env("FMD_NO_LAZY_EXTRACT");
+    h->lazy_capable = h->pipelined && h->ctx.fast && (size_t)d.C * d.n_fm_out >= (size_t)1024 * 8192;
     h->lazy_extract = h->lazy_capable;
-    h->no_fused_pll = dev_env("FMD_NO_FUSED_PLL") != nullptr;
-    h->chain_off = dev_env("FMD_CHAIN") == nullptr;
-    h->pll_eager = dev_env("FMD_PLL_EAGER") != nullptr;
-    if (dev_env("FMD_FRONT_OWN_QUEUE")) h->front_with_predecim = false;
 
     fmd_controls def;
     fmd_default_controls(&def);
@@ -1249,14 +1165,16 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
     // per-wavefront hand-over between consecutive k_pilot_pll launches: the time-parallel kernel only, pipelined mode only
     // (the low-work kernel k_pilot_pll_pairs has no chain argument: its launches must stay ordered by the stream)
     const bool time_parallel = d.C <= h->ctx.pll_time_parallel_max_channels;
-    // (FMD_FLAG_KEEP_TAPS: k_pll_taps reads the loop's start state ahead of the PLL kernel — consecutive blocks' launches stay in stream order)
-    h->pll_chained = h->pipelined && !h->ctx.fast && !h->ctx.keep_taps && time_parallel && effective_channels(d) <= 3328 && !(cfg->flags & (FMD_FLAG_PLL_STREAM_ORDER | FMD_FLAG_PLL_LOW_WORK));
     // (two ranges: 3585 .. 4096 effective stations — 8 or 16 lanes of the time-parallel kernel; above pll_time_parallel_max_channels, up to 16384 stations —
     //  the low-work kernel or the time-parallel one with 8 lanes, whose sequence form gets through loops out of lock: 8192 stations with 1 % unlocked
     //  2.87 -> 1.9 ms a block.  The FMD_FLAG_PLL_* selectors switch the choice off.)
-    h->pll_k_adaptive = !h->ctx.fast && !dev_env("FMD_PLL_K_FIXED") &&
+    h->pll_k_adaptive = !h->ctx.fast &&
                         ((time_parallel && !(cfg->flags & (FMD_FLAG_PLL_K8 | FMD_FLAG_PLL_LOW_WORK)) && effective_channels(d) > h->ctx.pll_k16_max_channels && effective_channels(d) <= 4096) ||
                          (!time_parallel && !(cfg->flags & FMD_FLAG_PLL_LOW_WORK) && d.C <= 16384));
+    // (FMD_FLAG_KEEP_TAPS: k_pll_taps reads the loop's start state ahead of the PLL kernel — consecutive blocks' launches stay in stream order;
+    //  the hand-over is indexed by wavefront, so it never runs beside the adaptive lane count)
+    h->pll_chained = h->pipelined && !h->ctx.fast && !h->ctx.keep_taps && time_parallel && effective_channels(d) <= 3328 && !(cfg->flags & (FMD_FLAG_PLL_STREAM_ORDER | FMD_FLAG_PLL_LOW_WORK)) &&
+                     !h->pll_k_adaptive;
     h->pll_waves = (effective_channels(d) <= h->ctx.pll_k16_max_channels || (h->pll_k_adaptive && time_parallel)) ? (d.C + 3) / 4 : (d.C + 7) / 8;
     if (!rc) rc = dev_alloc(h, &b.pll_chain, (size_t)h->pll_waves + 1 + (size_t)d.C + 2);
     if (!rc) b.pll_hint = b.pll_chain + h->pll_waves + 1;
@@ -1825,14 +1743,6 @@ int fmd_debug_split_front(fmd_handle h, int on) {
     return FMD_OK;
 }
 
-int fmd_debug_set_chain(fmd_handle h, int on) {
-    if (!h) return FMD_ERR_ARG;
-    int rc = fmd_synchronize(h);
-    if (rc) return rc;
-    h->chain_off = on == 0;
-    return FMD_OK;
-}
-
 int fmd_debug_pll_adaptive(fmd_handle h, int k16_max_channels, int time_parallel_max_channels) {
     if (!h || k16_max_channels < 0 || time_parallel_max_channels < 0) return FMD_ERR_ARG;
     if (h->ctx.fast || !h->pll_unl_host || effective_channels(h->ctx.d) > 4096) return fail(h, FMD_ERR_ARG, "the exact mode, up to 4096 stations");
@@ -1852,12 +1762,6 @@ int fmd_debug_extract_pairing(fmd_handle h, int mode) {
     int rc = fmd_synchronize(h);
     if (rc) return rc;
     h->ctx.extract_pairing = mode;
-    return FMD_OK;
-}
-
-int fmd_debug_chain_blocks(fmd_handle h, long* blocks) {
-    if (!h || !blocks) return FMD_ERR_ARG;
-    *blocks = h->chain_blocks;
     return FMD_OK;
 }
 
@@ -1881,7 +1785,6 @@ int fmd_profile_read(fmd_handle h, fmd_kernel_time* out, int cap, int* n_out) {
             const char* nm = h->ctx.fast ? kStageNameFast[i] : kStageName[i];
             if (h->ctx.fast && i == ST_EXTRACT && h->ctx.d.n_audio % 256 == 0) nm = "k_extract_bp";      // (round 5: fmd_kernels_bp.inc)
             if (i == ST_FRONT && front_takes_capture(h->ctx)) nm = "k_front_pre_mfma";
-            if (i == ST_FRONT && pm->chain) nm = "k_chain";                                             // (round 6: fmd_kernels_chain.inc)
             for (int j = 0; j < n; j++) if (std::strncmp(out[j].name, nm, sizeof(out[j].name)) == 0) { slot = j; break; }
             if (slot < 0) {
                 if (n >= cap) continue;

@@ -33,7 +33,6 @@
 #include <vector>
 
 #include "fmdemod.h"
-#include "fmd_kernels.h"     // dev_env: development switches are read only in builds with -DFMD_DEV_HOOKS
 
 namespace {
 
@@ -364,7 +363,7 @@ int fmd_chan_create(const fmd_chan_config* cfg, fmd_channelizer* out) {
     ok = ok && hipMemcpy(h->taps, h->h_taps.data(), sizeof(float) * h->h_taps.size(), hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(h->inc, inc.data(), sizeof(unsigned long long) * h->C, hipMemcpyHostToDevice) == hipSuccess;
     // the matrix-core form: L == 16 and the operand / window sizes it is built for (10 MSa/s -> 256 kSa/s with 640 taps per phase)
-    if (ok && L == 16 && (15 * M) / 16 + T <= kMK && (kMG - 1) * M + kMK <= kMRail && !fmd::dev_env("FMD_CHAN_VALU")) {
+    if (ok && L == 16 && (15 * M) / 16 + T <= kMK && (kMG - 1) * M + kMK <= kMRail) {
         std::vector<float> at((size_t)4 * kMKW * 64, 0.0f);
         for (int w = 0; w < 4; w++)
             for (int j = 0; j < kMKW; j++)
@@ -439,9 +438,7 @@ int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_i
         // two workgroups per CU: three (what its 164 registers and 49 KB of LDS allow) leave no wavefront slot and no LDS for the
         // demodulator's kernels that run beside it, which then wait for a 60 us persistent workgroup to finish — the configs[4] line x537
         // with three, x571-581 with two (profiles/round5/rds_stage_ab.txt)
-        int per_cu = 2;
-        if (const char* e = fmd::dev_env("FMD_CHAN_WG_PER_CU")) { const int v = atoi(e); if (v >= 1 && v <= 3) per_cu = v; }      // (development A/B)
-        int gx = (per_cu * 256) / h->C;
+        int gx = (2 * 256) / h->C;
         gx = gx < 1 ? 1 : (gx > n_tiles ? n_tiles : gx);
         hipLaunchKernelGGL(k_channelize16_mfma, dim3((unsigned)gx, (unsigned)h->C), dim3(256), sizeof(float) * (2 * kMRail + 4 * 256), s, d, win, h->atab, h->inc,
                            reinterpret_cast<float2*>(d_out), n_tiles);

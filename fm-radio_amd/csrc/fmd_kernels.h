@@ -319,8 +319,6 @@ hipError_t launch_stage_deemph(const LaunchCtx& ctx, SlotRef r, hipStream_t s); 
 hipError_t launch_stage_power(const LaunchCtx& ctx, SlotRef r, hipStream_t s);                             // k_pilot_power
 hipError_t launch_stage_pll(const LaunchCtx& ctx, SlotRef r, hipStream_t s);                               // k_pilot_pll
 hipError_t launch_stage_extract(const LaunchCtx& ctx, SlotRef r, hipStream_t s);                           // k_extract
-bool chain_possible(const LaunchCtx& ctx);                                                                 // tolerance mode, 256 kSa/s cf32: front end + pilot + extract as one launch
-hipError_t launch_stage_chain(const LaunchCtx& ctx, SlotRef r, const void* d_iq, hipStream_t s);              // k_chain (fmd_kernels_chain.inc)
 hipError_t launch_stage_rds(const LaunchCtx& ctx, SlotRef r, hipStream_t s);                               // k_rds_sync
 hipError_t launch_lmr_phase_peek(const LaunchCtx& ctx, int par, float* out_row, hipStream_t s);            // k_lmr_phase into a scratch row
 hipError_t launch_reset_state(const LaunchCtx& ctx, hipStream_t stream);

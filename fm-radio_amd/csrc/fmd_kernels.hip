@@ -361,9 +361,7 @@ __device__ __forceinline__ int2 raw_u8(const uchar2* __restrict__ in_c, const fl
     return make_int2((int)v.x - 127, (int)v.y - 127);
 }
 
-// DEM_READY (round 6, cf32 captures away from the block's start): the caller has written the discriminator output's bf16 halves itself — the phase
-// difference as ONE arctangent of x[n] conj(x[n-1]), straight from the loaded samples (discriminator_pairs below) — and has passed a barrier.
-template <int TT, int WU, bool TIES = false, bool DEM_READY = false>
+template <int TT, int WU, bool TIES = false>
 __device__ __forceinline__ void front_from_phases(const Dims& d, float* smem, const float* theta, uint32_t* dem32, int c, int o0, int tid, float fm_gain,
                                                   const float* __restrict__ deemph, const FrontOps& op, float* __restrict__ fo_pl,
                                                   float4* __restrict__ pv_pl, const PllSparseTab* __restrict__ sp,
@@ -379,45 +377,43 @@ __device__ __forceinline__ void front_from_phases(const Dims& d, float* smem, co
     unsigned long long fp_t = __builtin_readcyclecounter();
 #endif
     // phase difference, wrap, scale: two samples per thread and step, split into bf16 halves, in place over the phases
-    if constexpr (!DEM_READY) {
-        const float gain_t = fm_gain * bits_f32(kTwoPiBits);           // the discriminator's gain per turn
-        constexpr int NPW = G::NWB / 2;                              // words per half
-        constexpr int PERP = (NPW + 255) / 256;
-        uint32_t wh[PERP], wl[PERP];
+    const float gain_t = fm_gain * bits_f32(kTwoPiBits);           // the discriminator's gain per turn
+    constexpr int NPW = G::NWB / 2;                              // words per half
+    constexpr int PERP = (NPW + 255) / 256;
+    uint32_t wh[PERP], wl[PERP];
 #pragma unroll
-        for (int r = 0; r < PERP; r++) {
-            const int pw = tid + 256 * r, j = 2 * pw;
-            wh[r] = 0u; wl[r] = 0u;
-            if (j < NW - 1) {
-                const float t0 = theta[j], t1 = theta[j + 1], t2 = (j + 2 < NW) ? theta[j + 2] : t1;
-                float d0 = t1 - t0, d1 = t2 - t1;
-                d0 = d0 - rintf(d0); d1 = d1 - rintf(d1);           // reference fm_demod.cpp:36-43: the phase difference wrapped to half a turn
-                if constexpr (TIES) {
-                    if (__builtin_expect(fabsf(fabsf(d0) - 0.5f) < 2.0e-6f || fabsf(fabsf(d1) - 0.5f) < 2.0e-6f, 0)) {      // (wrap_tie_u8 above)
-                        const int2 s0 = raw_u8(raw_c, raw_tail, raw_tail_len, g_lo + j), s1 = raw_u8(raw_c, raw_tail, raw_tail_len, g_lo + j + 1);
-                        if (fabsf(fabsf(d0) - 0.5f) < 2.0e-6f) d0 = wrap_tie_u8(d0, s0.x, s0.y, s1.x, s1.y, sp->wrap_tie);
-                        if (j + 2 < NW && fabsf(fabsf(d1) - 0.5f) < 2.0e-6f) {
-                            const int2 s2 = raw_u8(raw_c, raw_tail, raw_tail_len, g_lo + j + 2);
-                            d1 = wrap_tie_u8(d1, s1.x, s1.y, s2.x, s2.y, sp->wrap_tie);
-                        }
+    for (int r = 0; r < PERP; r++) {
+        const int pw = tid + 256 * r, j = 2 * pw;
+        wh[r] = 0u; wl[r] = 0u;
+        if (j < NW - 1) {
+            const float t0 = theta[j], t1 = theta[j + 1], t2 = (j + 2 < NW) ? theta[j + 2] : t1;
+            float d0 = t1 - t0, d1 = t2 - t1;
+            d0 = d0 - rintf(d0); d1 = d1 - rintf(d1);           // reference fm_demod.cpp:36-43: the phase difference wrapped to half a turn
+            if constexpr (TIES) {
+                if (__builtin_expect(fabsf(fabsf(d0) - 0.5f) < 2.0e-6f || fabsf(fabsf(d1) - 0.5f) < 2.0e-6f, 0)) {      // (wrap_tie_u8 above)
+                    const int2 s0 = raw_u8(raw_c, raw_tail, raw_tail_len, g_lo + j), s1 = raw_u8(raw_c, raw_tail, raw_tail_len, g_lo + j + 1);
+                    if (fabsf(fabsf(d0) - 0.5f) < 2.0e-6f) d0 = wrap_tie_u8(d0, s0.x, s0.y, s1.x, s1.y, sp->wrap_tie);
+                    if (j + 2 < NW && fabsf(fabsf(d1) - 0.5f) < 2.0e-6f) {
+                        const int2 s2 = raw_u8(raw_c, raw_tail, raw_tail_len, g_lo + j + 2);
+                        d1 = wrap_tie_u8(d1, s1.x, s1.y, s2.x, s2.y, sp->wrap_tie);
                     }
                 }
-                d0 *= gain_t; d1 = (j + 1 < NW - 1) ? d1 * gain_t : 0.0f;
-                uint32_t h0, l0, h1, l1;
-                split_bf16(d0, h0, l0); split_bf16(d1, h1, l1);
-                wh[r] = pack_hi16(h0, h1); wl[r] = pack_hi16(l0, l1);
             }
-        }
-        F_STAMP(2);
-        __syncthreads();
-#pragma unroll
-        for (int r = 0; r < PERP; r++) {
-            const int pw = tid + 256 * r;
-            if (pw < NPW) { dem_hi32[pw] = wh[r]; dem_lo32[pw] = wl[r]; }
+            d0 *= gain_t; d1 = (j + 1 < NW - 1) ? d1 * gain_t : 0.0f;
+            uint32_t h0, l0, h1, l1;
+            split_bf16(d0, h0, l0); split_bf16(d1, h1, l1);
+            wh[r] = pack_hi16(h0, h1); wl[r] = pack_hi16(l0, l1);
         }
     }
+    F_STAMP(2);
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < PERP; r++) {
+        const int pw = tid + 256 * r;
+        if (pw < NPW) { dem_hi32[pw] = wh[r]; dem_lo32[pw] = wl[r]; }
+    }
     F_STAMP(3);
-    if constexpr (!DEM_READY) __syncthreads();
+    __syncthreads();
     F_STAMP(4);
     // a3: decimate-by-2 FIR: wavefront w takes the 16-column tiles w, w + 4, ... (a column = 16 consecutive outputs).
     // fm_out goes to its plane undelayed (the rows start with the previous block's tail, k_pll_sparse); the consumers delay it by 32
@@ -540,58 +536,8 @@ __global__ __launch_bounds__(256, FUSED ? 6 : 5) void k_front_mfma(Dims d, const
 #endif
     // a0-a2: staging, arctangent (all loads first)
     bool staged = false;
-// Round 6 A/B (profiles/round6/front_conj_ab.txt): the cf32 discriminator as one arctangent of x[n] conj(x[n-1]) straight from
-// the loaded samples (no phase array in LDS, one barrier in the tile instead of three) against round 5's two arctangents through LDS: same
-// results to 1e-6, and SLOWER — k_front_mfma 0.163 ms against 0.152 in the step (4096 stations), 0.348 against 0.32 at 8192: the 8-byte load
-// of the sample in front of every pair is one more vector-memory instruction per two samples on a kernel that already keeps the memory pipe
-// and the vector ALU busy together, and what it saves (LDS round trips, two barriers) was hidden by the six workgroups a CU holds.
-// Kept behind the macro; k_chain (fmd_kernels_chain.inc) uses the form where it has no LDS for a phase array.
-#ifndef FMD_FRONT_CONJ
-#define FMD_FRONT_CONJ 0
-#endif
-#if FMD_FRONT_CONJ
-    if constexpr (sizeof(InT) == 8) {
-        // cf32 input away from the block's start (round 6): the discriminator's phase difference as ONE arctangent of
-        // x[n] conj(x[n-1]) — the reference takes the two samples' arctangents and wraps their difference (fm_demod.cpp:30-45): the same angle,
-        // in (-1/2, 1/2] turns by construction — straight from the loaded samples: word w of the output (elements 2 w, 2 w + 1) needs the
-        // tile's samples 2 w, 2 w + 1, 2 w + 2 = the 16-byte pair at the even block sample g_lo + 2 w + 1 and the 8 bytes in front of it.  No
-        // phase array in LDS (one write and 1.5 reads per sample), no wrap, and one barrier in the tile instead of three.
-        if (tile != 0) {
-            constexpr int NWORD = (NW - 1 + 1) / 2;                       // 1055 words hold the NW - 1 differences (the last word's second element is 0)
-            constexpr int PERW = NWORD / 256, RESTW = NWORD - 256 * PERW;  // (1024-sample tiles: four full rounds and 31 words for the first lanes)
-            const float gain_t = fm_gain * bits_f32(kTwoPiBits);
-            uint32_t* dem_hi32 = reinterpret_cast<uint32_t*>(smem);
-            uint32_t* dem_lo32 = dem_hi32 + G::NWB / 2;
-            const float2* base = in_c + (g_lo + 1);                       // (even sample: 16-byte aligned)
-            float4 qb[PERW + 1]; float2 pb[PERW + 1];
-#pragma unroll
-            for (int r = 0; r < PERW; r++) { const int w = tid + 256 * r; qb[r] = ld_stream(reinterpret_cast<const float4*>(base + 2 * w)); pb[r] = base[2 * w - 1]; }
-            if (tid < RESTW) { const int w = 256 * PERW + tid; qb[PERW] = ld_stream(reinterpret_cast<const float4*>(base + 2 * w)); pb[PERW] = base[2 * w - 1]; }
-            auto pair = [&](const float4& q, const float2& p, int w) __attribute__((always_inline)) {
-                const float re0 = fmaf(q.x, p.x, q.y * p.y), im0 = fmaf(q.y, p.x, -(q.x * p.y));        // x[2w+1] conj(x[2w])
-                const float re1 = fmaf(q.z, q.x, q.w * q.y), im1 = fmaf(q.w, q.x, -(q.z * q.y));        // x[2w+2] conj(x[2w+1])
-                const float d0 = fast_atan2_turns(im0, re0) * gain_t;
-                const float d1 = (2 * w + 1 < NW - 1) ? fast_atan2_turns(im1, re1) * gain_t : 0.0f;
-                uint32_t h0, l0, h1, l1;
-                split_bf16(d0, h0, l0); split_bf16(d1, h1, l1);
-                dem_hi32[w] = pack_hi16(h0, h1); dem_lo32[w] = pack_hi16(l0, l1);
-            };
-#pragma unroll
-            for (int r = 0; r < PERW; r++) pair(qb[r], pb[r], tid + 256 * r);
-            if (tid < RESTW) pair(qb[PERW], pb[PERW], 256 * PERW + tid);
-            else if (256 * PERW + tid < G::NWB / 2) { dem_hi32[256 * PERW + tid] = 0u; dem_lo32[256 * PERW + tid] = 0u; }      // (the padding under the zero taps)
-            F_STAMP(0);
-            __syncthreads();
-            F_STAMP(1);
-            front_from_phases<TT, WU, false, true>(d, smem, theta, reinterpret_cast<uint32_t*>(smem), c, o0, tid, fm_gain, deemph, op, fo_pl, pv_pl, sp);
-            if (tile == tiles - 1) {
-                float2* tout = tail_out + (size_t)c * d.tail_base;
-                for (int idx = tid; idx < d.tail_base; idx += 256) tout[idx] = load_iq(in_c, (unsigned)(d.N - d.tail_base + idx));
-            }
-            return;
-        }
-    }
-#else      // (round 5's form, kept for the A/B: tools/build_variant.sh name "-DFMD_FRONT_CONJ=0")
+    // (Round 6 measured the cf32 discriminator as one arctangent of x[n] conj(x[n-1]) straight from the loaded samples, with no phase
+    // array in LDS: same results to 1e-6 and slower, k_front_mfma 0.163 ms against 0.152 at 4096 stations)
     if constexpr (sizeof(InT) == 8) {
         // cf32 input away from the block's start: 16 bytes per lane (two samples).  The tile starts at an odd sample (TAIL is odd): the
         // pairs start one sample earlier, pair q = samples 2 q - 1 and 2 q of the tile; what is left behind the full rounds, one per thread.
@@ -615,7 +561,6 @@ __global__ __launch_bounds__(256, FUSED ? 6 : 5) void k_front_mfma(Dims d, const
             staged = true;
         }
     }
-#endif
     if constexpr (sizeof(InT) == 2 && (NW + 1) / 8 >= 256) {
         // u8 input away from the block's start: 16 bytes per lane are eight samples (the tile starts at sample 1 of such a group:
         // octet o = samples 8 o - 1 .. 8 o + 6 of the tile); one full round, the rest one sample per thread.
@@ -2466,7 +2411,6 @@ __device__ unsigned long long g_x_probe2[16];
 #endif
 
 #include "fmd_kernels_bp.inc"
-#include "fmd_kernels_chain.inc"
 
 // Tolerance mode, FMD_FLAG_KEEP_TAPS (the "fm_out_iq" getter) and block lengths whose audio blocks are not multiples of 256 (those run
 // k_extract<128, true> on the interleaved stream, with the history tails it keeps for itself): the analytic signal from the fm_out plane,
@@ -3068,10 +3012,8 @@ __global__ void k_reset(Dims d, float* __restrict__ state) {
 // and the front end has slack.  With 44 KB of extra dynamic LDS its workgroups come two to a CU instead of six and leave the serial stages'
 // wavefronts the issue slots: 1024 stations 0.125 -> 0.114 ms (RDS launch 0.121 -> 0.102, the front end itself 0.060 -> 0.053), 1536 stations
 // 0.135 -> 0.126, 1792: 0.144 -> 0.136, 1024 x u8 0.117 -> 0.110; 512 stations and the 40 of configs[4]: no difference; 640: slower (0.111 ->
-// 0.120: no deferred schedule there), 2048: slower (0.148 -> 0.154) (profiles/round5/rds_stage_ab.txt).  FMD_FRONT_LDS_PAD (development builds) overrides the amount.
+// 0.120: no deferred schedule there), 2048: slower (0.148 -> 0.154) (profiles/round5/rds_stage_ab.txt).
 static size_t front_lds_pad(const Dims& d) {
-    static const long forced = dev_env("FMD_FRONT_LDS_PAD") ? atol(dev_env("FMD_FRONT_LDS_PAD")) : -1;
-    if (forced >= 0) return (size_t)(forced <= 49152 ? forced : 49152);
     return (d.m == 1 && d.C >= 1024 && d.C <= 1792) ? 45056 : 0;
 }
 template <typename InT, int TT = 512, bool FAST = false>
@@ -3086,14 +3028,12 @@ static hipError_t launch_front(const LaunchCtx& ctx, SlotRef r, const InT* d_iq,
             // cf32 captures, round 6: 2048-output tiles for batches that still give the chip 12 288 workgroups (3072 stations' worth of 64 ms blocks) —
             // half as many workgroups fetch the FIR's operand images (7 KB each from L2: 230 MB a block at 1024-output tiles) and recompute a
             // tile's 63-sample halo: k_front_mfma 0.154 -> 0.142 ms in the step, 268 -> 278 GSa/s at 4096 stations, +2.5 % at 8192; at 2048 stations
-            // (8192 workgroups) 1024-output tiles are 1 % better (profiles/round6/front_tile_ab.txt).  FMD_FRONT_CF32_TILE (development builds) forces one.
-            static const int forced = dev_env("FMD_FRONT_CF32_TILE") ? atoi(dev_env("FMD_FRONT_CF32_TILE")) : 0;
-            const bool big = forced ? forced == 2048 : (long)d.C * (d.n_fm_out / 2048) >= 12288;
+            // (8192 workgroups) 1024-output tiles are 1 % better (profiles/round6/front_tile_ab.txt).
+            const bool big = (long)d.C * (d.n_fm_out / 2048) >= 12288;
             if (big && d.n_fm_out % 2048 == 0 && !ctx.deemph_in_tile) return launch_front<InT, 2048, FAST>(ctx, r, d_iq, s, pll);
         }
         if constexpr (FAST && sizeof(InT) == 2) {   // u8 captures: 2048-output tiles (4 KB of input per 1024-output workgroup leaves too few bytes in flight per CU)
-            static const bool t1024 = dev_env("FMD_FRONT_U8_T1024") != nullptr;      // (A/B hook)
-            if (d.n_fm_out % 2048 == 0 && !ctx.deemph_in_tile && !t1024) return launch_front<InT, 2048, FAST>(ctx, r, d_iq, s, pll);
+            if (d.n_fm_out % 2048 == 0 && !ctx.deemph_in_tile) return launch_front<InT, 2048, FAST>(ctx, r, d_iq, s, pll);
         }
         if (d.n_fm_out % 1024 == 0) return launch_front<InT, 1024, FAST>(ctx, r, d_iq, s, pll);
     }
@@ -3132,14 +3072,13 @@ template <int M, typename InT>
 static hipError_t launch_predecim(const LaunchCtx& ctx, SlotRef r, const InT* d_iq, hipStream_t s) {
     const Dims& d = ctx.d;
     using G = PredecimGeom<M>;
-    static const bool valu_form = dev_env("FMD_PREDECIM_VALU") != nullptr;      // (A/B hook: the tolerance mode's first decimator on the VALU)
     // tile: 2048 input samples of cf32 (16 KB; the kernel then sits on its HBM floor whatever the tile), 8192 of u8 (16 KB as well:
     // with 4 KB per workgroup too few bytes are in flight per CU); blocks that are no multiple of it: 256 outputs per workgroup
     constexpr int TPM = (sizeof(InT) == 2 ? 8192 : 2048) / M;
-    if (ctx.fast && !valu_form && d.n_fm_in % TPM != 0 && d.n_fm_in % 256 == 0) {
+    if (ctx.fast && d.n_fm_in % TPM != 0 && d.n_fm_in % 256 == 0) {
         FMD_LAUNCH(r, true, true, (k_predecim_mfma<M, InT, 256>), dim3((unsigned)(d.n_fm_in / 256 * d.C)), dim3(256), 0, s, d, d_iq, ctx.b.pre_tail[r.par], ctx.b.pre_tail[r.par ^ 1],
                    reinterpret_cast<float*>(ctx.b.fm_in[r.buf]), ctx.b.front_mfma + kFrontImgU4);
-    } else if (ctx.fast && !valu_form && d.n_fm_in % TPM == 0) {
+    } else if (ctx.fast && d.n_fm_in % TPM == 0) {
         FMD_LAUNCH(r, true, true, (k_predecim_mfma<M, InT, TPM>), dim3((unsigned)(d.n_fm_in / TPM * d.C)), dim3(256), 0, s, d, d_iq, ctx.b.pre_tail[r.par], ctx.b.pre_tail[r.par ^ 1],
                    reinterpret_cast<float*>(ctx.b.fm_in[r.buf]), ctx.b.front_mfma + kFrontImgU4);
     } else if (ctx.fast)
@@ -3165,8 +3104,7 @@ hipError_t launch_stage_predecim(const LaunchCtx& ctx, SlotRef r, const void* d_
 // 1.024 / 2.048 MSa/s, tolerance mode: the first decimator inside the front end's kernel (k_front_pre_mfma) — the block then has no
 // predecim stage and launch_stage_front takes the capture.  Not with a de-emphasised station (k_front_mfma's WU form stays on fm_in).
 bool front_takes_capture(const LaunchCtx& ctx) {
-    static const bool off = dev_env("FMD_NO_FRONT_PRE") != nullptr;      // (A/B hook)
-    return ctx.d.m > 1 && ctx.fast && !ctx.any_deemph && !ctx.deemph_in_tile && ctx.d.n_fm_out % 1024 == 0 && !off && !ctx.split_front;
+    return ctx.d.m > 1 && ctx.fast && !ctx.any_deemph && !ctx.deemph_in_tile && ctx.d.n_fm_out % 1024 == 0 && !ctx.split_front;
 }
 
 template <int M, typename InT>
@@ -3299,13 +3237,12 @@ static void launch_extract_ta(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
         //  clamped — ADVICE r5: at 8 bits a block of a million samples could wrap nt to 0)
         constexpr int kNtMax = 0x7fff;
         for (int v = (tiles + 3) / 4 < kNtMax ? (tiles + 3) / 4 : kNtMax; v >= 1; v--) if ((long)((tiles + 4 * v - 1) / (4 * v)) * d.C >= 1536) { nt = v; break; }
-        if (const char* e = dev_env("FMD_BP_NT")) { const int v = atoi(e); if (v > 0 && v <= kNtMax) nt = v; }      // (development A/B)
         int grid_x = (tiles + 4 * nt - 1) / (4 * nt) * d.C;
         // round 6: two stations per workgroup (tables and the block edge's matrix fetched once for both) where a station is one workgroup anyway,
         // every station has the same cut-offs and the pairs still are 1536 workgroups; ctx.extract_pairing: 1 forces it (tests), 2 switches it off
         const bool one_wg_per_station = 4 * nt >= tiles;
         const bool pair = ctx.uniform_cutoffs && one_wg_per_station && 2 * tiles <= 4 * kNtMax && d.C >= 2 &&
-                          (ctx.extract_pairing == 1 || (ctx.extract_pairing == 0 && (d.C + 1) / 2 >= 1536 && !dev_env("FMD_BP_NOPAIR")));
+                          (ctx.extract_pairing == 1 || (ctx.extract_pairing == 0 && (d.C + 1) / 2 >= 1536));
         if (pair) { nt = (2 * tiles + 3) / 4; grid_x = (d.C + 1) / 2; }
         if (dev_env("FMD_BP_NOEDGE")) nt |= 0x10000;                     // (development, timing only: the first tile's sums over the previous block skipped)
         if (pair) FMD_LAUNCH(r, true, true, k_extract_bp<2>, dim3((unsigned)grid_x), dim3(TA), 0, s, d, nt, b.fo_pl[r.buf], b.pll_poly[r.buf],
@@ -3364,24 +3301,6 @@ extern "C" int fmd_debug_read_x_probe2(unsigned long long* out16) {
 }
 namespace fmd {
 #endif
-}  // namespace fmd
-// development: how many k_chain workgroups the runtime places on one CU (registers, LDS)
-extern "C" int fmd_debug_chain_occupancy(void) {
-    int n = -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fmd::k_chain, 320, fmd::ChainLds::BYTES) != hipSuccess) return -1;
-    return n;
-}
-namespace fmd {
-#ifdef FMD_C_PROBE
-}  // namespace fmd
-extern "C" int fmd_debug_read_c_probe(unsigned long long* out32) {
-    return (int)hipMemcpyFromSymbol(out32, HIP_SYMBOL(fmd::g_c_probe), 32 * sizeof(unsigned long long));
-}
-extern "C" int fmd_debug_read_c_start(unsigned long long* out2048) {
-    return (int)hipMemcpyFromSymbol(out2048, HIP_SYMBOL(fmd::g_c_start), 2048 * sizeof(unsigned long long));
-}
-namespace fmd {
-#endif
 #ifdef FMD_RDS_PROBE
 }  // namespace fmd
 extern "C" int fmd_debug_read_rds_probe(unsigned long long* out16) {
@@ -3389,44 +3308,6 @@ extern "C" int fmd_debug_read_rds_probe(unsigned long long* out16) {
 }
 namespace fmd {
 #endif
-// Tolerance mode, 256 kSa/s cf32 captures: the block's front end, pilot stage and extract stage as ONE launch (fmd_kernels_chain.inc); the
-// RDS stage follows as before.  chain_possible: what the kernel's geometry needs of the configuration (the host adds what it needs of the
-// block: no start-up block, no de-emphasis, one set of cut-offs for all stations — fmd_api.cpp).
-bool chain_possible(const LaunchCtx& ctx) {
-    const Dims& d = ctx.d;
-    return ctx.fast && d.m == 1 && !ctx.keep_taps && !ctx.b.fm_out_iq[0] && d.n_fm_out % 1024 == 0 && d.n_audio % 256 == 0 && d.tail_base >= 64;
-}
-hipError_t launch_stage_chain(const LaunchCtx& ctx, SlotRef r, const void* d_iq, hipStream_t s) {
-    const Dims& d = ctx.d;
-    const Buffers& b = ctx.b;
-    const int nxt = (r.buf + 1) % kSlots;
-    ChainArgs a{};
-    a.in = static_cast<const float2*>(d_iq); a.tail_in = b.base_tail[r.par]; a.tail_out = b.base_tail[r.par ^ 1];
-    a.front_tab = b.front_mfma; a.sp = b.sparse_tab; a.fm_gain = ctx.front.fm_gain;
-    a.fo_hist = b.fo_pl[r.buf]; a.fo_next = b.fo_pl[nxt];
-    a.hist_in = b.pv_hist[r.par]; a.hist_out = b.pv_hist[r.par ^ 1];
-    a.poly = b.pll_poly[r.buf]; a.poly_next = b.pll_poly[nxt];
-    a.state = b.state; a.k = ctx.loops;
-    a.bp_tab = b.bp_tab; a.aud_idx = b.aud_idx; a.rds_tab = b.rds_bp_tab; a.bp_edge = b.bp_edge; a.mixctl = b.mix;
-    a.audio = b.audio[r.buf]; a.rds = b.rds[r.buf]; a.lmr_est = b.lmr_est[r.par];
-    a.lmr_est_prev = lmr_inline(ctx) ? b.lmr_est[r.par ^ 1] : (const float*)nullptr;
-    a.field_cur = lmr_field(r.par); a.field_prev = lmr_field(r.par ^ 1); a.rds_pow = b.rds_pow[r.buf];
-    a.spec_stats = b.spec_stats;
-    // (more than 64 KB of dynamic LDS has to be asked for; per call: a process may drive several devices)
-    const hipError_t lds_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(k_chain), hipFuncAttributeMaxDynamicSharedMemorySize, ChainLds::BYTES);
-    if (lds_ok != hipSuccess) return lds_ok;
-    FMD_LAUNCH(r, true, true, k_chain, dim3((unsigned)((d.C + ChainGeom::G - 1) / ChainGeom::G)), dim3(320), ChainLds::BYTES, s, d, a);
-    if (!lmr_inline(ctx)) {   // P_{b+1} behind block b (launch_stage_extract)
-        if (ctx.fast && ctx.d.n_est <= kLmrInlineMax)
-            hipLaunchKernelGGL(k_lmr_phase_fast, dim3((unsigned)ctx.d.C), dim3(kWave), 0, s, ctx.d, ctx.b.lmr_est[r.par], ctx.b.state, lmr_field(r.par),
-                               ctx.b.state + (size_t)lmr_field(r.par ^ 1) * ctx.d.C);
-        else
-            hipLaunchKernelGGL(k_lmr_phase, dim3(serial_waves(ctx.d)), dim3(kWave), 0, s, ctx.d, ctx.b.lmr_est[r.par], ctx.b.state, lmr_field(r.par),
-                               ctx.b.state + (size_t)lmr_field(r.par ^ 1) * ctx.d.C);
-    }
-    return hipGetLastError();
-}
-
 // FMD_FLAG_RDS_DECODE: k_rds_decode on the block's bytes, right behind k_rds_sync on the same stream (which orders consecutive blocks'
 // decoder launches, the condition for its in-place state); it is then the stage's last kernel and carries its end event
 static hipError_t launch_stage_rds_decode(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
@@ -3444,8 +3325,7 @@ hipError_t launch_stage_rds(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
     const bool dec = ctx.rds_decode != 0;
     if (ctx.fast) {
         const bool partials = d.n_audio % 256 == 0;       // k_extract_bp ran and left the block's power as 2 partial sums per tile
-        static const bool two_waves = dev_env("FMD_RDS_TWO_WAVES") != nullptr;      // (A/B hook: the two-wavefront form)
-        if (partials && !two_waves) {      // the loop split over mixer, clock and dump wavefronts (fmd_kernels_fast.inc)
+        if (partials) {      // the loop split over mixer, clock and dump wavefronts (fmd_kernels_fast.inc)
             FMD_LAUNCH(r, true, !dec, k_rds_sync3, dim3(serial_waves(d)), dim3(5 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
                        b.rds_raw_sym[r.buf], b.rds_count[r.buf], b.rds_bytes[r.buf], b.rds_bytes_count[r.buf], ctx.bytes_cap, ctx.keep_taps,
                        b.rds_pow[r.buf], 2 * (d.n_audio / 256));

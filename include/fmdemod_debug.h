@@ -76,15 +76,6 @@ int fmd_profile_enable(fmd_handle h, int on);
  * Between blocks only. */
 int fmd_debug_split_front(fmd_handle h, int on);
 int fmd_profile_read(fmd_handle h, fmd_kernel_time* out, int cap, int* n_out);
-/* Tolerance mode, 256 kSa/s cf32: on = 1 runs a steady block's front end, pilot stage and extract stage as ONE launch (k_chain,
- * fm-radio_amd/csrc/fmd_kernels_chain.inc: fm_out, the pilot points' sums and the span cubics stay in LDS) instead of the three launches
- * that are the default.  Round 6's measured A/B (profiles/round6/chain_*): 22 % fewer HBM bytes (832 MB a block
- * against 1069), correct — within 1.1e-6 RMS of the three-launch form's audio, the same distance from the oracle — and SLOWER (0.268 ms against
- * 0.237 without the RDS stage, 0.44 against 0.25 with it): two 80 KB workgroups per CU are all the LDS admits, ten wavefronts a CU do not
- * hide the chain's latencies, and the RDS stage's workgroups take slots from a grid that needs every one of them.  Kept as a development switch and as the parity test of both forms.
- * Between blocks only; both forms leave the same histories, so a handle may change between them at any block.
- * fmd_debug_chain_blocks: how many blocks since create / reset ran as k_chain. */
-int fmd_debug_set_chain(fmd_handle h, int on);
 /* Exact mode, test hook: the batch sizes up to which the pilot PLL runs as the time-parallel kernel with 16 lanes a station (default 3584) and as the
  * time-parallel kernel at all (default 7168; the low-work kernel above).  Beyond either the choice follows what is out of lock:
  * 8 lanes / the low-work kernel while every loop holds lock, 16 lanes (up to 4096 stations) / the time-parallel kernel while some do not.  With small
@@ -93,7 +84,6 @@ int fmd_debug_pll_adaptive(fmd_handle h, int k16_max_channels, int time_parallel
 /* Tolerance mode: k_extract_bp with two stations per workgroup (the tap tables and the block edge's matrix fetched once for both; results bit-identical):
  * 0 = where it pays (3072 stations and more with equal cut-offs, the default), 1 = wherever possible (so that tests reach it with a few stations), 2 = never. */
 int fmd_debug_extract_pairing(fmd_handle h, int mode);
-int fmd_debug_chain_blocks(fmd_handle h, long* blocks);
 
 #ifdef __cplusplus
 }

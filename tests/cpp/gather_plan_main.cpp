@@ -131,8 +131,8 @@ static int test_run(int R, long K) {
         });
         long complete = 0, right_place = 0;
         for (long w = 0; w < K; w++) {
+            s.holding.store(-1);              // (before begin_wait: once it gives block w - 1's views back, a rank may refill their set)
             s.sync.begin_wait(w);
-            s.holding.store(-1);
             bool ok = true;
             for (int q = 0; q < R; q++) ok = ok && s.sync.wait_submitted(q, w);     // (the simulation polls every rank: a shard is there once its rank has submitted)
             if (!ok) break;

@@ -510,93 +510,21 @@ def test_fast_mode_dead_channel_cannot_slow_or_disturb_its_neighbours(pkg):
     assert st["samples_per_span"] > 15.0, st
 
 
-def test_one_launch_form_of_a_steady_block_matches_the_three_launch_form(pkg):
-    """k_chain (fmd_debug_set_chain, fm-radio_amd/csrc/fmd_kernels_chain.inc: front end, pilot stage and extract stage of a steady 256 kSa/s cf32
-    block as ONE launch, fm_out in LDS) against the three-launch form that is the default and against the oracle: the same distance from the
-    oracle, a few 1e-6 from each other (its discriminator takes one arctangent of x[n] conj(x[n-1]) where the other takes two arctangents'
-    difference), identical RDS bits from lock on — and a handle that CHANGES between the two forms every block (they keep the same
-    histories: IQ tail, fm_out tail, pilot columns, last cubic, loop state) stays as close.  11 stations: a workgroup's 8 and a ragged one."""
-    import torch
-    fs, bs, nb, n_ch = 256_000, 16384, 12, 11
-    caps = _caps(n_ch, nb * bs, float(fs), seed=9700)
-
-    def run(schedule):
-        dm = pkg.BatchDemod(n_ch, bs, fs, fast_math=True)
-        au, by = [], [b"" for _ in range(n_ch)]
-        for b in range(nb):
-            dm.set_chain(schedule(b))
-            assert dm.submit(torch.from_numpy(np.ascontiguousarray(caps[:, b * bs:(b + 1) * bs])).cuda()) == 0
-            dm.synchronize()
-            au.append(dm.audio().reshape(n_ch, -1).copy())
-            b_, bc = dm.rds_bytes()
-            for c in range(n_ch):
-                by[c] += b_[c, :bc[c]].tobytes()
-        k = [dm.get_coeffs(c) for c in range(n_ch)]
-        n_chain = dm.chain_blocks()
-        dm.close()
-        return np.concatenate(au, axis=1), [np.frombuffer(x, np.uint8) for x in by], k, n_chain
-
-    three, by3, k, n0 = run(lambda b: False)
-    one, by1, _, n1 = run(lambda b: True)
-    mixed, bym, _, nm = run(lambda b: b % 2 == 1)
-    assert n0 == 0 and n1 == nb - 1 and nm == nb // 2      # (the first block is a start-up block: always the three launches)
-    na = one.shape[1] // nb
-    worst = {"one_vs_three": 0.0, "mixed_vs_three": 0.0, "one_vs_oracle": 0.0, "three_vs_oracle": 0.0}
-    for c in range(n_ch):
-        worst["one_vs_three"] = max(worst["one_vs_three"], rms(one[c].astype(np.float64) - three[c]))
-        worst["mixed_vs_three"] = max(worst["mixed_vs_three"], rms(mixed[c].astype(np.float64) - three[c]))
-        assert same_bits_once_in_lock(by1[c], by3[c], skip_bits=5 * 76) and same_bits_once_in_lock(bym[c], by3[c], skip_bits=5 * 76), c
-    for c in (0, 3, 7, 8, 10):
-        o = O.run_chain(caps[c], bs, fs, u8=False, coeffs=lib_coeffs_to_oracle(k[c]), streams=["audio"])["audio"].reshape(-1)
-        for name, a in (("one_vs_oracle", one), ("three_vs_oracle", three)):
-            per_block = [rms(a[c, b * na:(b + 1) * na].astype(np.float64) - o[b * na:(b + 1) * na]) for b in range(4, nb)]      # (in lock: no flipped estimates in play)
-            worst[name] = max(worst[name], max(per_block))
-        assert same_bits_once_in_lock(by1[c], O.run_chain(caps[c], bs, fs, u8=False, coeffs=lib_coeffs_to_oracle(k[c]), streams=["rds_sym"])["rds_bytes"], skip_bits=5 * 76), c
-    print("k_chain:", {a: f"{b:.2e}" for a, b in worst.items()})
-    assert worst["one_vs_three"] <= 5e-6 and worst["mixed_vs_three"] <= 5e-6, worst        # (measured 1.2e-6)
-    assert worst["one_vs_oracle"] <= TOL_RMS and worst["one_vs_oracle"] <= 1.25 * worst["three_vs_oracle"] + 2e-6, worst
-    record_parity_metrics("one_launch_form_k_chain_11_stations_12_blocks", worst)
-    # Repetition on fresh handles, 64 stations (8 workgroups: beside the RDS stage's workgroup of the block before, whose LDS they inherit): the
-    # kernel must not depend on what it finds in LDS — round 6 found quad 303 of a window (behind its last sample, under zero taps) unwritten:
-    # 0 x a NaN pattern left by another kernel made column 15 of every tile NaN on 3 of 4 runs on some boxes and never on others
-    caps64 = caps[np.arange(64) % n_ch][:, :4 * bs]
-    blocks = [torch.from_numpy(np.ascontiguousarray(caps64[:, b * bs:(b + 1) * bs])).cuda() for b in range(4)]
-    def short(chain):
-        dm = pkg.BatchDemod(64, bs, fs, fast_math=True)
-        out = []
-        for b in range(4):
-            dm.set_chain(chain)
-            assert dm.submit(blocks[b]) == 0
-            dm.synchronize()
-            out.append((dm.audio().reshape(64, -1).copy(), dm.rds_symbols()[1].copy()))
-        dm.close()
-        return out
-    ref = short(False)
-    for rep in range(8):
-        got = short(True)
-        for b in range(4):
-            assert not np.isnan(got[b][0]).any(), (rep, b)
-            assert rms(got[b][0].astype(np.float64) - ref[b][0]) <= 5e-6 and np.array_equal(got[b][1], ref[b][1]), (rep, b)
-
-
-def test_one_launch_form_leaves_a_complete_state(pkg):
-    """fmd_get_state / fmd_set_state across k_chain blocks: a station's state taken after four one-launch blocks and restored into another
-    handle (other batch size, other block parity, three-launch form) continues bit-identically to what the FIRST handle produces when IT goes
-    on in the three-launch form — i.e. the one-launch form keeps every history the other form reads (IQ tail, fm_out tail, the pilot points'
-    last columns, the last span's cubic, the loop state, the L-R estimates) — through fmd_process_* (the caller's stream ordered behind the
-    library's read) as well as fmd_submit_*."""
+def test_state_moves_between_handles_across_submit_and_process(pkg):
+    """fmd_get_state / fmd_set_state in the tolerance mode without FMD_FLAG_KEEP_TAPS: a station's state taken after five blocks, alternately
+    submitted (fmd_submit_*) and processed (fmd_process_*, the caller's stream ordered behind the library's read), and restored into another
+    handle (other batch size, other block parity) continues bit-identically to what the FIRST handle produces — i.e. the state blob holds
+    every history the pipeline reads (IQ tail, fm_out tail, the pilot points' last columns, the last span's cubic, the loop state, the L-R
+    estimates)."""
     import torch
     fs, bs, nb = 256_000, 16384, 9
     caps = _caps(9, nb * bs, float(fs), seed=9800)
     a = pkg.BatchDemod(9, bs, fs, fast_math=True)
-    a.set_chain(True)
-    for b in range(5):                                   # block 0: start-up (three launches); 1 .. 4 as k_chain, alternately submitted and processed
+    for b in range(5):                                   # block 0: start-up; then alternately processed and submitted
         t = torch.from_numpy(np.ascontiguousarray(caps[:, b * bs:(b + 1) * bs])).cuda()
         assert (a.process(t) if b % 2 else a.submit(t)) == 0
     a.synchronize()
-    assert a.chain_blocks() == 4
     blob = a.get_state(7)
-    a.set_chain(False)
     other = _caps(3, 2 * bs, float(fs), seed=9801)
     bdm = pkg.BatchDemod(3, bs, fs, fast_math=True)
     for b in range(2):

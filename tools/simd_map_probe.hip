@@ -8,7 +8,7 @@ __global__ void k_where(unsigned* out) {
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(id));
     if ((threadIdx.x & 63) == 0) out[blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)] = id;
 }
-__global__ void k_chain(float* out, int iters, int active_waves) {
+__global__ void k_dep_chain(float* out, int iters, int active_waves) {
     const int w = threadIdx.x >> 6;
     float a = threadIdx.x * 1e-3f, b = 1.0001f;
     if (w < active_waves) {
@@ -29,8 +29,8 @@ int main() {
     float* o; (void)hipMalloc(&o, 64 * 256 * 4);
     hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
     for (int act = 1; act <= 4; act++) {
-        hipLaunchKernelGGL(k_chain, dim3(64), dim3(256), 0, 0, o, 1000, act);
-        (void)hipEventRecord(e0); hipLaunchKernelGGL(k_chain, dim3(64), dim3(256), 0, 0, o, 20000, act); (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
+        hipLaunchKernelGGL(k_dep_chain, dim3(64), dim3(256), 0, 0, o, 1000, act);
+        (void)hipEventRecord(e0); hipLaunchKernelGGL(k_dep_chain, dim3(64), dim3(256), 0, 0, o, 20000, act); (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
         float ms; (void)hipEventElapsedTime(&ms, e0, e1);
         printf("active waves %d of 4: %.3f ms (%.2f ns per dependent fma)\n", act, ms, ms * 1e6 / (20000.0 * 16));
     }
