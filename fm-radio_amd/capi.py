@@ -77,6 +77,14 @@ class ChanConfig(C.Structure):
                 ("taps_per_phase", C.c_int), ("max_input_samples", C.c_longlong), ("device", C.c_int)]
 
 
+class ResamplerConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("fs_in", C.c_int), ("fs_out", C.c_int), ("method", C.c_int), ("taps_per_phase", C.c_int),
+                ("max_input_frames", C.c_longlong), ("device", C.c_int)]
+
+
+FMD_RESAMPLE_REFERENCE, FMD_RESAMPLE_POLYPHASE = 0, 1
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("total_ms", C.c_double), ("launches", C.c_int)]
 
@@ -178,6 +186,16 @@ def load_library():
     L.fmd_chan_process_cf32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
     L.fmd_chan_last_error.restype = C.c_char_p
     L.fmd_chan_last_error.argtypes = [C.c_void_p]
+    L.fmd_resampler_design.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.fmd_resampler_create.argtypes = [C.POINTER(ResamplerConfig), C.POINTER(C.c_void_p)]
+    L.fmd_resampler_destroy.argtypes = [C.c_void_p]
+    L.fmd_resampler_reset.argtypes = [C.c_void_p, C.c_int]
+    L.fmd_resampler_set_input_rate.argtypes = [C.c_void_p, C.c_int]
+    L.fmd_resampler_output_frames.argtypes = [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]
+    for name in ("fmd_resampler_process_f32_dev", "fmd_resampler_process_pcm16_dev", "fmd_resampler_process_f32_host"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]
+    L.fmd_resampler_last_error.restype = C.c_char_p
+    L.fmd_resampler_last_error.argtypes = [C.c_void_p]
     L.fmd_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.argtypes = [C.c_void_p]
@@ -683,3 +701,99 @@ class Channelizer:
             self.close()
         except Exception:
             pass
+
+
+def resampler_design(fs_in: int, fs_out: int, taps_per_phase: int = 0):
+    """Host-only polyphase design of the audio resampler: (taps [T, L] float32 with taps[t, p] = h[p + t L], L, M).  Needs no GPU."""
+    lib = load_library()
+    L, M = C.c_int(0), C.c_int(0)
+    rc = lib.fmd_resampler_design(int(fs_in), int(fs_out), int(taps_per_phase), None, C.byref(L), C.byref(M))
+    if rc != FMD_OK:
+        raise FmdError(rc, f"unsupported resampler rates {fs_in} -> {fs_out} ({taps_per_phase} taps per phase)")
+    T = taps_per_phase if taps_per_phase > 0 else 32 * -(-M.value // L.value)    # include/fmdemod.h: the default grows with M / L
+    taps = np.empty((T, L.value), np.float32)
+    lib.fmd_resampler_design(int(fs_in), int(fs_out), int(taps_per_phase), taps.ctypes.data_as(C.c_void_p), None, None)
+    return taps, L.value, M.value
+
+
+class AudioResampler:
+    """C stations' stereo audio from fs_in to fs_out on the GPU (fmd_resampler_*): the reference's Resampled_PCM_Player for a batch.
+    method "reference" is its block-local linear interpolation, bit-identical; "polyphase" streams through an anti-aliasing filter.
+    Feed it BatchDemod.audio_tensor() (or any [C, n, 2] float32 CUDA tensor whose frames are contiguous)."""
+
+    design = staticmethod(resampler_design)
+
+    def __init__(self, n_channels: int, fs_out: int, fs_in: int = 32000, method: str = "polyphase", taps_per_phase: int = 0,
+                 max_input_frames: int = 1 << 16, device: int = -1):
+        self.L = load_library()
+        m = {"reference": FMD_RESAMPLE_REFERENCE, "polyphase": FMD_RESAMPLE_POLYPHASE}[method]
+        cfg = ResamplerConfig(n_channels, int(fs_in), int(fs_out), m, int(taps_per_phase), int(max_input_frames), device)
+        self.r = C.c_void_p()
+        rc = self.L.fmd_resampler_create(C.byref(cfg), C.byref(self.r))
+        if rc != FMD_OK:
+            self.r = None
+            raise FmdError(rc, self.L.fmd_resampler_last_error(None).decode() or self.L.fmd_status_string(rc).decode())
+        self.n_channels, self.fs_in, self.fs_out, self.method = n_channels, int(fs_in), int(fs_out), method
+
+    def close(self):
+        if getattr(self, "r", None):
+            self.L.fmd_resampler_destroy(self.r)
+            self.r = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc < 0:
+            raise FmdError(rc, (self.L.fmd_resampler_last_error(self.r) or b"").decode() or self.L.fmd_status_string(rc).decode())
+        return rc
+
+    def output_frames(self, n_in: int) -> int:
+        """frames per channel the next call with n_in input frames emits"""
+        n = C.c_longlong(0)
+        self._check(self.L.fmd_resampler_output_frames(self.r, int(n_in), C.byref(n)))
+        return n.value
+
+    def reset(self, channel: int = -1):
+        self._check(self.L.fmd_resampler_reset(self.r, int(channel)))
+
+    def set_input_rate(self, fs_in: int) -> bool:
+        """SetInputSampleRate: True if the rate changed"""
+        changed = self._check(self.L.fmd_resampler_set_input_rate(self.r, int(fs_in))) == 1
+        self.fs_in = int(fs_in)
+        return changed
+
+    def _run(self, fn, x, n_in, dtype, out, stream):
+        import torch
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
+                and x.stride(2) == 1 and x.stride(1) == 2):
+            raise ValueError("x must be a CUDA float32 tensor [C, n, 2] with contiguous frames")
+        n_in = int(x.shape[1]) if n_in is None else int(n_in)
+        want = self.output_frames(n_in)
+        if out is None:
+            out = torch.empty((self.n_channels, max(want, 1), 2), dtype=dtype, device=x.device)
+        assert out.dtype == dtype and out.dim() == 3 and out.stride(2) == 1 and out.stride(1) == 2 and out.shape[1] >= want
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        got = C.c_longlong(0)
+        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
+        out_stride = out.stride(0) // 2 if out.shape[0] > 1 else out.shape[1]
+        self._check(fn(self.r, C.c_void_p(x.data_ptr()), in_stride, n_in, C.c_void_p(out.data_ptr()), out_stride, C.byref(got),
+                       C.c_void_p(stream)))
+        return out[:, :got.value]
+
+    def process(self, x, n_in: int | None = None, out=None, stream=None):
+        """x: [C, n, 2] float32 on the device (the first n_in frames are read, default all).  Returns [C, n_out, 2] float32, asynchronous on
+        `stream` (default: torch's current stream)."""
+        import torch
+        return self._run(self.L.fmd_resampler_process_f32_dev, x, n_in, torch.float32, out, stream)
+
+    def process_pcm16(self, x, n_in: int | None = None, out=None, stream=None):
+        """The same as the scraper's 16-bit PCM frames: [C, n_out, 2] int16."""
+        import torch
+        return self._run(self.L.fmd_resampler_process_pcm16_dev, x, n_in, torch.int16, out, stream)

@@ -389,6 +389,67 @@ int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_i
                               size_t* n_out, void* stream);
 const char* fmd_chan_last_error(fmd_channelizer h);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Batched audio resampler: the stage between OnAudioOut and the listener (reference Resampled_PCM_Player,
+ * src/audio/resampled_pcm_player.cpp:15-54, fed every OnAudioOut block at src/fm_demod_tuner.cpp:145-165).  C stations'
+ * stereo f32 frames at fs_in (fmd_rates.fs_audio) in, [C][n_out][2] at fs_out out, on the GPU.  Standalone: it reads the
+ * demodulator's audio views (fmd_audio_dev) and changes nothing in the demodulator.  Two methods:
+ *   FMD_RESAMPLE_REFERENCE  Resample() (resampled_pcm_player.cpp:37-54): each call is one ConsumeBuffer of n_in frames,
+ *                           block-local linear interpolation, bit-identical to the reference's build; nothing carries over.
+ *                           n_out = (int)((float)fs_out / (float)fs_in * (float)n_in).  Where the reference's running
+ *                           single-precision index walks past the block's last frame (long calls: n_in = 16384 at 48 kHz) its
+ *                           span indexing would abort: such a call returns FMD_ERR_ARG and writes nothing.
+ *   FMD_RESAMPLE_POLYPHASE  (beyond the reference) streaming rational L / M = fs_out / fs_in in lowest terms, anti-aliased:
+ *                           y[n] = sum_{t<T} h[p + t L] x[floor(n M / L) - t], p = n M mod L, n counted since the last reset;
+ *                           output n is emitted by the call that delivers input frame floor(n M / L).  h: one Kaiser-windowed
+ *                           sinc (>= 60 dB from min(fs_in, fs_out) / 2 up, every phase's DC gain 1).  Each channel keeps its
+ *                           last T - 1 input frames (zero after a reset); the frame counters are 64-bit, on the host and shared by
+ *                           all channels, so fmd_resampler_output_frames is exact.  Fixed fp32 FMA order: a station's outputs do
+ *                           not depend on how its input was split into calls, on the batch size or on its row.
+ * fs_in == fs_out: either method passes the input through unchanged (ConsumeBuffer, resampled_pcm_player.cpp:17-20).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_resampler_s* fmd_resampler;
+enum { FMD_RESAMPLE_REFERENCE = 0, FMD_RESAMPLE_POLYPHASE = 1 };
+typedef struct {
+    int       n_channels;
+    int       fs_in;             /* input rate, Hz: 32000 = fmd_rates.fs_audio */
+    int       fs_out;            /* output rate, Hz: 48000, 44100, 22050, 16000, 8000, ... (the player's device rate) */
+    int       method;            /* FMD_RESAMPLE_* */
+    int       taps_per_phase;    /* polyphase only: T, multiple of 4 in 8 ... 256; 0 = default: 32 x ceil(M / L) */
+    long long max_input_frames;  /* largest n_in of a call */
+    int       device;            /* HIP device ordinal, -1 = current */
+} fmd_resampler_config;
+
+/* host-only polyphase design (no GPU needed): L / M and, if taps != NULL, the prototype h stored [t][p] = h[p + t L]
+ * (taps_per_phase 0 = the default) */
+int fmd_resampler_design(int fs_in, int fs_out, int taps_per_phase, float* taps, int* L, int* M);
+/* Resampled_PCM_Player::Resampled_PCM_Player (resampled_pcm_player.cpp:5-11) x n_channels */
+int fmd_resampler_create(const fmd_resampler_config* cfg, fmd_resampler* out);
+int fmd_resampler_destroy(fmd_resampler r);
+/* polyphase: channel >= 0 clears that channel's history; -1 clears every history and restarts the frame counters.  Waits for
+ * the resampler's earlier calls.  (The reference method has no state: nothing to do.) */
+int fmd_resampler_reset(fmd_resampler r, int channel);
+/* Resampled_PCM_Player::SetInputSampleRate (resampled_pcm_player.cpp:29-33): returns 1 if the rate changed (polyphase: the
+ * filter is re-designed and every history and counter reset), 0 if not, < 0 on error */
+int fmd_resampler_set_input_rate(fmd_resampler r, int fs_in);
+/* the frame count the next process call with n_in input frames emits per channel */
+int fmd_resampler_output_frames(fmd_resampler r, long long n_in, long long* n_out);
+/* Resampled_PCM_Player::ConsumeBuffer (resampled_pcm_player.cpp:15-27) for every channel.
+ * d_in [C][in_stride][2] f32 on the device (fmd_audio_dev's view: in_stride = n_audio), n_in <= in_stride and <= max_input_frames;
+ * d_out [C][out_stride][2] on the device, out_stride >= the call's *n_out.  Asynchronous on `stream`; consecutive calls may use
+ * different streams (the library orders them).  A call on a new n_in (reference method) uploads that length's index table once.
+ * The pcm16 form writes the scraper's frames (fm_scraper.cpp:79-82: sample * (32767 * 0.95f), truncated toward zero): exactly
+ * that conversion of the f32 form's output. */
+int fmd_resampler_process_f32_dev(fmd_resampler r, const float* d_in, long long in_stride, long long n_in,
+                                  float* d_out, long long out_stride, long long* n_out, void* stream);
+int fmd_resampler_process_pcm16_dev(fmd_resampler r, const float* d_in, long long in_stride, long long n_in,
+                                    int16_t* d_out, long long out_stride, long long* n_out, void* stream);
+/* the same with a HOST destination out [C][out_stride][2] f32: resamples on `stream` and synchronises it (for hosts that write
+ * files, fm-radio_amd/host/resampled_pcm_player_gpu.hpp) */
+int fmd_resampler_process_f32_host(fmd_resampler r, const float* d_in, long long in_stride, long long n_in,
+                                   float* out, long long out_stride, long long* n_out, void* stream);
+const char* fmd_resampler_last_error(fmd_resampler r);
+
 #ifdef __cplusplus
 }
 #endif
