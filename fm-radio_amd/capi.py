@@ -178,6 +178,8 @@ def load_library():
     L.fmd_debug_extract_pairing.argtypes = [H, C.c_int]
     L.fmd_profile_read.argtypes = [H, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]
     L.fmd_chan_design.argtypes = [C.c_double, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.fmd_chan_default_taps_per_phase.restype = C.c_int
+    L.fmd_chan_default_taps_per_phase.argtypes = [C.c_double, C.c_double]
     L.fmd_chan_create.argtypes = [C.POINTER(ChanConfig), C.POINTER(C.c_void_p)]
     L.fmd_chan_destroy.argtypes = [C.c_void_p]
     L.fmd_chan_reset.argtypes = [C.c_void_p]
@@ -647,8 +649,22 @@ def chan_design(fs_in: float, fs_out: float, taps_per_phase: int = 640):
     return taps, L.value, M.value
 
 
+def chan_default_taps(fs_in: float, fs_out: float = 256_000.0) -> int:
+    """The taps per phase Channelizer(..., taps_per_phase=0) uses for a rate pair (fmd_chan_default_taps_per_phase).  Needs no GPU."""
+    t = load_library().fmd_chan_default_taps_per_phase(float(fs_in), float(fs_out))
+    if t <= 0:
+        raise FmdError(t, f"unsupported channeliser rates {fs_in} -> {fs_out}")
+    return t
+
+
 class Channelizer:
-    """Wideband capture -> [C][n_out] cf32 stations at fs_out on the GPU (fmd_chan_*); feeds BatchDemod.process directly."""
+    """Wideband capture -> [C][n_out] cf32 stations at fs_out on the GPU (fmd_chan_*); feeds BatchDemod.process directly.
+
+    Accepts every pair of integer rates with fs_out / fs_in = L / M, L <= 64 and M / L <= 128 (fs_in up to 32.768 MSa/s at 256 kSa/s:
+    the whole FM band in one capture), with 4 to 4096 taps per phase; taps_per_phase=0 takes chan_default_taps(fs_in, fs_out).  Kernels:
+    10 MSa/s -> 256 kSa/s with 640 taps per phase on the matrix cores (k_channelize16_mfma); the whole-band pairs with L dividing 16
+    (16, 20, 20.48, 24, 30.72, 32, 32.768 MSa/s) on the matrix cores too (k_channelize_band_mfma); every other pair on the vector ALUs.
+    A station's output does not depend on its row or on the number of stations."""
 
     def __init__(self, fs_in: float, center_hz, fs_out: float = 256_000.0, max_input_samples: int = 640_000, taps_per_phase: int = 0, device: int = -1):
         self.L = load_library()

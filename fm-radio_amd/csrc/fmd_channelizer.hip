@@ -48,6 +48,7 @@ struct ChanDims {
     unsigned long long o0;  // absolute index of the first output of this call
     unsigned long long n_base;  // absolute input index of the window's first sample: [T - 1 history samples][this call's block]
     long long n_in;             // samples of this call's block
+    int tile;                   // outputs per workgroup of k_channelize: kTile, fewer where its window would not fit (whole-band rates)
 };
 
 // The window of a call is [T - 1 history samples][the caller's block]: two buffers, read in place (round 5: staging the block behind the
@@ -231,14 +232,136 @@ __global__ __launch_bounds__(256, 3) void k_channelize16_mfma(ChanDims d, ChanWi
     }
 }
 
-// any L <= 64: one output per thread (the first 128 threads), taps read from global memory
+// Whole-band rates on the matrix cores (16 - 32.768 MSa/s -> 256 kSa/s: M / L = 62.5 - 128, L dividing 16).  The same banded product as
+// k_channelize16_mfma: the 16 outputs o = 16 g + m of group g read the window x[g S - (T - 1) + tau], S = 16 M / L (an integer when L | 16),
+//     y[16 g + m] = sum_tau A[m][tau] x[g S - (T - 1) + tau],   A[m][tau] = h[p(m) + L t],  t = c(m) + T - 1 - tau,
+//     c(m) = floor(m M / L), p(m) = (m M) mod L  — the same for every group, since 16 g M is a multiple of L.
+// What differs is the size: K = floor(15 M / L) + T is 1961 - 4020 taus, a 16 x K operand of 125 - 257 KB that four wavefronts cannot hold
+// in registers.  So A is built per K-step from the prototype, held in LDS phase-major and reversed (hr[p][u] = h[p + L (T - 1 - u)],
+// u = tau - c(m)): per MFMA one LDS read and one select for the band's structural zeros (u outside [0, T)).  Columns are the windows of
+// the tile's G groups, real rail then imaginary rail (G = 8, or 4 / 2 where 8 would not fit the LDS budget; the spare columns repeat the
+// used ones).  Wavefront w takes the K-steps [w KW, (w + 1) KW) with four accumulators; the four partial tiles meet in LDS in a fixed order.
+// Every output's sum has one fixed order for a configuration: it does not depend on the station's row, the batch or the call's cuts.
+// The window is stored with one spare float every 256 samples (band_pos): group strides S are multiples of 32 floats at several of
+// these rates (1280, 1920, 2048), which would put all of a wavefront's columns on one LDS bank.
+// Non-finite input: as in k_channelize16_mfma, the banded operand multiplies EVERY staged sample of a group's window, its structural zeros
+// included, so one Inf / NaN input sample makes all 16 outputs of every group whose window holds it NaN.  A capture from a device is
+// finite by construction; a host that may feed non-finite floats filters them at its boundary.
+constexpr int kBandLds = 100352;            // bytes per workgroup: what two k_channelize16_mfma workgroups take, i.e. the demodulator keeps its room
+struct BandPlan {
+    int G;          // groups of 16 outputs per tile (8, 4 or 2)
+    int KW;         // K-steps of 4 taus per wavefront, a multiple of 8: 16 KW >= K
+    int S;          // group stride in input samples: 16 M / L
+    int n_win;      // staged samples per rail: (G - 1) S + 16 KW
+    int rail;       // floats from the real rail's start to the prototype's; the imaginary rail follows the prototype
+};
+__device__ __forceinline__ int band_pos(int i) { return i + (i >> 8); }
+
+__global__ __launch_bounds__(256) void k_channelize_band_mfma(ChanDims d, ChanWin win, const float* __restrict__ hrev /* [L][T] reversed */,
+                                                              const unsigned long long* __restrict__ phase_inc, float2* __restrict__ out,
+                                                              BandPlan bp, int n_tiles) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    // [real rail][prototype][imaginary rail]: an A read outside the prototype (a structural zero, discarded by the select) stays in LDS
+    float* xr = smem;
+    float* hr = smem + bp.rail;
+    float* xi = hr + d.L * d.T;
+    float* part = xr;                       // [wavefront][column][row], over the real rail once a tile's products are done
+    const int k = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, col = lane & 15, kq = lane >> 4;
+    const int L = d.L, T = d.T, G = bp.G;
+    for (int i = tid; i < L * T; i += 256) hr[i] = hrev[i];
+    // this lane's row of A (m = col) and K-slot kq: u = 4 j + kq - c(m), prototype index p(m) T + u
+    const int c_m = (col * d.M) / L, p_m = (col * d.M) % L;
+    const int j_lo = wv * bp.KW;
+    const int u0 = 4 * j_lo + kq - c_m;
+    const float* ha = hr + p_m * T + u0;
+    // this lane's column of X: group gi, rail
+    const int gi = col & (G - 1), rail = (col / G) & 1;
+    const float* xb = rail ? xi : xr;
+    const int i0 = gi * bp.S + 4 * j_lo + kq;
+    const unsigned long long inc = phase_inc[k];
+    float ss, cs;
+    sincospif((float)(unsigned int)((256ull * inc) >> 32) * 4.656612873077393e-10f, &ss, &cs);
+    hand_over_history(d, win);
+    const unsigned long long g_first = d.o0 / 16ull;          // a call's first output need not start a group: rows before it are not stored
+    const long long n_have = (long long)(d.T - 1) + d.n_in;  // samples of [history ++ block]
+    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const unsigned long long g0 = g_first + (unsigned long long)tile * (unsigned long long)G;
+        const unsigned long long n_lo = g0 * (unsigned long long)bp.S - (unsigned long long)(T - 1);   // absolute index of window sample 0
+        const long long j0 = (long long)(n_lo - d.n_base);    // its index in [history ++ block] (negative in front of the call's data)
+        __syncthreads();                                      // the previous tile's reads of the rails (and of `part`) are done
+        // batches of 16 samples a thread (4096 a workgroup): the 16 loads in flight together (one workgroup per CU: a load at a time would
+        // leave the staging waiting on L2 for most of a tile's time), then mixed with the phasor computed exactly for the batch's first sample and
+        // advanced by recurrence (stride 256: drift < 2e-6 as in stage_mixed)
+#pragma unroll 1
+        for (int ib = 0; ib < bp.n_win; ib += 16 * 256) {
+            float2 x[16];
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int i = ib + tid + 256 * r;
+                const long long j = j0 + i;
+                const bool ok = i < bp.n_win && j >= 0 && j < n_have;
+                const float2 v = win_at(d, win, j < 0 ? 0 : (j < n_have ? j : n_have - 1));   // (an address inside [history ++ block] either way)
+                x[r] = ok ? v : make_float2(0.f, 0.f);
+            }
+            float s, c;
+            sincospif((float)(unsigned int)(((n_lo + (unsigned long long)(ib + tid)) * inc) >> 32) * 4.656612873077393e-10f, &s, &c);
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int i = ib + tid + 256 * r;
+                if (i < bp.n_win) {
+                    const int q = band_pos(i);
+                    xr[q] = fmaf(x[r].x, c, x[r].y * s); xi[q] = fmaf(x[r].y, c, -(x[r].x * s));   // x * (cos - j sin)
+                }
+                const float cn = fmaf(c, cs, -(s * ss)), sn = fmaf(s, cs, c * ss);
+                c = cn; s = sn;
+            }
+        }
+        __syncthreads();
+        // chunks of 8 K-steps, the next chunk's 16 LDS reads in flight over this chunk's 8 MFMAs (one wavefront per SIMD: nothing else
+        // would hide their latency); four accumulators, as one wavefront needs to keep the matrix core busy
+        f32x4_t acc[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[q] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+        float hn[8], bn[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) { hn[q] = ha[4 * q]; bn[q] = xb[band_pos(i0 + 4 * q)]; }
+#pragma unroll 1
+        for (int jc = 0; jc < bp.KW; jc += 8) {
+            float a[8], b[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++) { a[q] = (unsigned)(u0 + 4 * (jc + q)) < (unsigned)T ? hn[q] : 0.f; b[q] = bn[q]; }
+            if (jc + 8 < bp.KW) {
+#pragma unroll
+                for (int q = 0; q < 8; q++) { hn[q] = ha[4 * (jc + 8 + q)]; bn[q] = xb[band_pos(i0 + 4 * (jc + 8 + q))]; }
+            }
+#pragma unroll
+            for (int q = 0; q < 8; q++) acc[q & 3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[q], b[q], acc[q & 3], 0, 0, 0);
+        }
+        const f32x4_t acc0 = (acc[0] + acc[1]) + (acc[2] + acc[3]);
+        __syncthreads();                                      // every wavefront's reads of the real rail are done: `part` takes its place
+        *reinterpret_cast<float4*>(part + (wv * 16 + col) * 16 + 4 * kq) = make_float4(acc0[0], acc0[1], acc0[2], acc0[3]);
+        __syncthreads();
+        if (tid < 16 * G) {
+            const int g = tid >> 4, m = tid & 15;
+            float re = 0.f, im = 0.f;
+#pragma unroll
+            for (int w = 0; w < 4; w++) { re += part[(w * 16 + g) * 16 + m]; im += part[(w * 16 + G + g) * 16 + m]; }
+            const long long rel = (long long)((g0 + (unsigned long long)g) * 16ull + (unsigned long long)m - d.o0);
+            if (rel >= 0 && rel < d.n_out) out[(size_t)k * d.out_stride + rel] = make_float2(re, im);
+        }
+    }
+}
+
+// any L <= 64: one output per thread (the first d.tile <= 128 threads), taps read from global memory.  A tile is kTile outputs for every
+// rate pair whose window of 128 outputs fits kMaxWindow; beyond that (M / L up to 128, T up to 4096) 64, 32 or 16 outputs, whatever fits.
+// An output's sum does not depend on the tile.
 __global__ __launch_bounds__(256) void k_channelize(ChanDims d, ChanWin win, const float* __restrict__ taps /* [T][L] */,
                                                     const unsigned long long* __restrict__ phase_inc /* [C], turns * 2^64 per input sample */,
                                                     float2* __restrict__ out /* [C][out_stride] */) {
     __shared__ float2 xs[kMaxWindow];
     const int k = blockIdx.y;
-    const long long tile0 = (long long)blockIdx.x * kTile;
-    const int n_tile = (int)((d.n_out - tile0) < kTile ? (d.n_out - tile0) : kTile);
+    const long long tile0 = (long long)blockIdx.x * d.tile;
+    const int n_tile = (int)((d.n_out - tile0) < d.tile ? (d.n_out - tile0) : d.tile);
     // absolute input range needed by this tile: [n_lo, n_hi]
     const unsigned long long o_first = d.o0 + (unsigned long long)tile0, o_last = o_first + (unsigned long long)(n_tile - 1);
     const unsigned long long n_hi = (o_last * (unsigned long long)d.M) / (unsigned long long)d.L;
@@ -288,6 +411,10 @@ struct fmd_channelizer_s {
     bool have_done = false;
     float* taps = nullptr;            // [T][L]
     float* atab = nullptr;            // k_channelize16_mfma's operand A, per wavefront, K-step and lane; null: that form does not apply
+    float* hrev = nullptr;            // k_channelize_band_mfma's prototype, [L][T] with each phase reversed; null: that form does not apply
+    BandPlan band{};
+    int tile = kTile;                 // outputs per workgroup of k_channelize
+    bool legacy = true;               // a pair whose window of kTile outputs fits kMaxWindow: the kernel selection of before the band form
     unsigned long long* inc = nullptr;
     std::vector<float> h_taps;
     std::string err;
@@ -300,7 +427,37 @@ static int chan_fail(fmd_channelizer h, int code, const char* fmt, ...) {
     return code;
 }
 
+// k_channelize_band_mfma's tile for this configuration: the most groups (8, 4, 2) whose rails and prototype fit kBandLds; G = 0: none does
+static BandPlan band_plan(int L, int M, int T) {
+    BandPlan bp{};
+    const int S = 16 * M / L, K = (15 * M) / L + T;
+    const int ks = (K + 3) / 4;
+    const int kw = (ks + 31) / 32 * 8;
+    for (int G = 8; G >= 2; G /= 2) {
+        const int n_win = (G - 1) * S + 16 * kw;
+        int rail = n_win + (n_win >> 8) + 1;                              // band_pos(n_win - 1) < rail
+        rail += ((16 - (rail + L * T)) % 32 + 32) % 32;                   // the imaginary rail 16 banks from the real one
+        if ((size_t)sizeof(float) * (2 * (size_t)rail + (size_t)L * T) <= (size_t)kBandLds) {
+            bp.G = G; bp.KW = kw; bp.S = S; bp.n_win = n_win; bp.rail = rail;
+            return bp;
+        }
+    }
+    return bp;
+}
+
+static size_t band_lds_bytes(const BandPlan& bp, int L, int T) { return sizeof(float) * (2 * (size_t)bp.rail + (size_t)L * T); }
+
 extern "C" {
+
+int fmd_chan_default_taps_per_phase(double fs_in, double fs_out) {
+    int L = 0, M = 0;
+    const int rc = fmd_chan_design(fs_in, fs_out, 4, nullptr, &L, &M);
+    if (rc != FMD_OK) return rc;
+    if ((long long)kTile * M / L + 640 + 2 <= kMaxWindow) return 640;     // every pair accepted with 640 before keeps it
+    // 64 us of capture, as 640 taps per phase are at 10 MSa/s: T = 4 ceil(16.384 (M / L) / 4) = 4 ceil(512 M / (125 L))
+    const long long q = (512LL * M + 125LL * L - 1) / (125LL * L);
+    return (int)(4 * q);
+}
 
 int fmd_chan_design(double fs_in, double fs_out, int taps_per_phase, float* taps /* [T][L], may be NULL */, int* L_out, int* M_out) {
     if (!(fs_in > 0) || !(fs_out > 0) || fs_out > fs_in || taps_per_phase <= 0 || taps_per_phase % 4 != 0) return FMD_ERR_ARG;
@@ -338,12 +495,28 @@ int fmd_chan_create(const fmd_chan_config* cfg, fmd_channelizer* out) {
     if (fmd_device_count() <= 0) return chan_fail(nullptr, FMD_ERR_NO_DEVICE, "no gfx950 device");
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return chan_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
-    const int T = cfg->taps_per_phase > 0 ? cfg->taps_per_phase : 640;
+    int T = cfg->taps_per_phase;
+    if (T <= 0) {
+        T = fmd_chan_default_taps_per_phase(cfg->fs_in, cfg->fs_out);
+        if (T <= 0) T = 640;                        // (unsupported rates: refused just below)
+    }
     int L = 0, M = 0;
-    if (fmd_chan_design(cfg->fs_in, cfg->fs_out, T, nullptr, &L, &M) != FMD_OK) return chan_fail(nullptr, FMD_ERR_ARG, "unsupported rates %g -> %g (need integer rates, L <= 64)", cfg->fs_in, cfg->fs_out);
-    if ((long long)kTile * M / L + T + 2 > kMaxWindow) return chan_fail(nullptr, FMD_ERR_ARG, "decimation %d/%d with %d taps per phase needs a larger staging window", M, L, T);
+    if (fmd_chan_design(cfg->fs_in, cfg->fs_out, T, nullptr, &L, &M) != FMD_OK) return chan_fail(nullptr, FMD_ERR_ARG, "unsupported rates %g -> %g with %d taps per phase (need integer rates, L <= 64, taps per phase a multiple of 4)", cfg->fs_in, cfg->fs_out, T);
+    // pairs whose window of kTile outputs fits: the kernels and tiles they always had.  Beyond: M / L <= 128 and T <= 4096, on the band
+    // form where L divides 16 and its tile fits kBandLds, else on k_channelize with a tile of 64, 32 or 16 outputs
+    const bool legacy = (long long)kTile * M / L + T + 2 <= kMaxWindow;
+    int tile = kTile;
+    BandPlan bp{};
+    if (!legacy) {
+        if (M > 128 * L) return chan_fail(nullptr, FMD_ERR_ARG, "decimation %d/%d exceeds the channeliser's limit M / L <= 128", M, L);
+        if (T > 4096) return chan_fail(nullptr, FMD_ERR_ARG, "%d taps per phase exceed the channeliser's limit of 4096 at decimation %d/%d", T, M, L);
+        if (16 % L == 0) bp = band_plan(L, M, T);
+        while (tile > 16 && (long long)tile * M / L + T + 2 > kMaxWindow) tile /= 2;
+        if ((long long)tile * M / L + T + 2 > kMaxWindow) return chan_fail(nullptr, FMD_ERR_ARG, "decimation %d/%d with %d taps per phase needs a staging window over %d samples", M, L, T, kMaxWindow);
+    }
     fmd_channelizer h = new fmd_channelizer_s();
     h->device = dev; h->L = L; h->M = M; h->T = T; h->C = cfg->n_stations; h->fs_in = cfg->fs_in; h->fs_out = cfg->fs_out;
+    h->legacy = legacy; h->tile = tile; h->band = bp;
     h->max_in = (size_t)cfg->max_input_samples;
     h->h_taps.resize((size_t)T * L);
     fmd_chan_design(cfg->fs_in, cfg->fs_out, T, h->h_taps.data(), nullptr, nullptr);
@@ -376,6 +549,14 @@ int fmd_chan_create(const fmd_chan_config* cfg, fmd_channelizer* out) {
              hipMemcpy(h->atab, at.data(), sizeof(float) * at.size(), hipMemcpyHostToDevice) == hipSuccess &&
              hipFuncSetAttribute(reinterpret_cast<const void*>(k_channelize16_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * (2 * kMRail + 4 * 256))) == hipSuccess;
     }
+    if (ok && bp.G > 0) {
+        std::vector<float> hr((size_t)L * T);
+        for (int p = 0; p < L; p++)
+            for (int u = 0; u < T; u++) hr[(size_t)p * T + u] = h->h_taps[(size_t)(T - 1 - u) * L + p];
+        ok = hipMalloc(&h->hrev, sizeof(float) * hr.size()) == hipSuccess &&
+             hipMemcpy(h->hrev, hr.data(), sizeof(float) * hr.size(), hipMemcpyHostToDevice) == hipSuccess &&
+             hipFuncSetAttribute(reinterpret_cast<const void*>(k_channelize_band_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)band_lds_bytes(bp, L, T)) == hipSuccess;
+    }
     if (!ok) { fmd_chan_destroy(h); return chan_fail(nullptr, FMD_ERR_DEVICE, "device allocation failed"); }
     *out = h;
     return FMD_OK;
@@ -388,6 +569,7 @@ int fmd_chan_destroy(fmd_channelizer h) {
     if (h->done) (void)hipEventDestroy(h->done);
     if (h->taps) (void)hipFree(h->taps);
     if (h->atab) (void)hipFree(h->atab);
+    if (h->hrev) (void)hipFree(h->hrev);
     if (h->inc) (void)hipFree(h->inc);
     delete h;
     return FMD_OK;
@@ -430,9 +612,18 @@ int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_i
     if (h->have_done && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "stream wait failed");
     // window = [T-1 history samples][this block], read in place; its first sample has absolute input index n_abs - (T-1)
     const ChanWin win{h->win[h->cur], reinterpret_cast<const float2*>(d_wide), h->win[h->cur ^ 1]};
-    ChanDims d{h->L, h->M, T, h->C, (long long)no, (long long)out_capacity_per_station, h->o_abs, h->n_abs - (unsigned long long)(T - 1), (long long)n_in};
+    ChanDims d{h->L, h->M, T, h->C, (long long)no, (long long)out_capacity_per_station, h->o_abs, h->n_abs - (unsigned long long)(T - 1), (long long)n_in, h->tile};
     // outputs o0 .. o0+no-1 need inputs up to floor((o0+no-1) M / L) <= n_abs + n_in - 1 by construction
-    if (h->atab) {
+    if (h->hrev) {
+        // whole groups of 16 outputs from the one holding the call's first output; each workgroup keeps the prototype in LDS over ~4 tiles.
+        // One workgroup per CU (kBandLds), like two of k_channelize16_mfma's, leaves the demodulator's kernels their room beside it
+        const BandPlan& bp = h->band;
+        const unsigned long long g_first = h->o_abs / 16, g_last = (h->o_abs + no - 1) / 16;
+        const int n_tiles = (int)((g_last - g_first) / (unsigned long long)bp.G + 1);
+        const int gx = (n_tiles + 3) / 4;
+        hipLaunchKernelGGL(k_channelize_band_mfma, dim3((unsigned)gx, (unsigned)h->C), dim3(256), band_lds_bytes(bp, h->L, T), s, d, win, h->hrev, h->inc,
+                           reinterpret_cast<float2*>(d_out), bp, n_tiles);
+    } else if (h->atab) {
         // every workgroup keeps its operand registers over several tiles
         const int n_tiles = (int)((no + kTile - 1) / kTile);
         // two workgroups per CU: three (what its 164 registers and 49 KB of LDS allow) leave no wavefront slot and no LDS for the
@@ -442,11 +633,11 @@ int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_i
         gx = gx < 1 ? 1 : (gx > n_tiles ? n_tiles : gx);
         hipLaunchKernelGGL(k_channelize16_mfma, dim3((unsigned)gx, (unsigned)h->C), dim3(256), sizeof(float) * (2 * kMRail + 4 * 256), s, d, win, h->atab, h->inc,
                            reinterpret_cast<float2*>(d_out), n_tiles);
-    } else if (h->L == 16 && T % 64 == 0 && T <= 1024)
+    } else if (h->legacy && h->L == 16 && T % 64 == 0 && T <= 1024)
         hipLaunchKernelGGL(k_channelize16, dim3((unsigned)((no + kTile - 1) / kTile), (unsigned)h->C), dim3(256), 0, s, d, win, h->taps, h->inc,
                            reinterpret_cast<float2*>(d_out));
     else
-        hipLaunchKernelGGL(k_channelize, dim3((unsigned)((no + kTile - 1) / kTile), (unsigned)h->C), dim3(256), 0, s, d, win, h->taps, h->inc,
+        hipLaunchKernelGGL(k_channelize, dim3((unsigned)((no + h->tile - 1) / h->tile), (unsigned)h->C), dim3(256), 0, s, d, win, h->taps, h->inc,
                            reinterpret_cast<float2*>(d_out));
     if (hipGetLastError() != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "k_channelize launch failed");
     // (the last T-1 samples of [history ++ block] are the next call's history: the launch's first workgroup has written them into the

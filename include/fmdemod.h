@@ -368,13 +368,18 @@ typedef struct {
     double        fs_out;            /* per-station rate handed to the demodulator, integer Hz (256000) */
     int           n_stations;
     const double* center_hz;         /* [n_stations] station centres relative to the capture's centre, |f| < fs_in / 2 */
-    int           taps_per_phase;    /* 0 = default (640), multiple of 4 */
+    int           taps_per_phase;    /* 0 = default (fmd_chan_default_taps_per_phase), else a multiple of 4 */
     long long     max_input_samples; /* largest n_in of a process call */
     int           device;            /* HIP device ordinal, -1 = current */
 } fmd_chan_config;
 
 /* host-only filter design (no GPU needed): L/M and, if taps != NULL, the prototype stored [t][p] (t = tap within phase p) */
 int fmd_chan_design(double fs_in, double fs_out, int taps_per_phase, float* taps, int* L, int* M);
+/* host-only (no GPU needed): the taps per phase fmd_chan_create uses when taps_per_phase == 0.  640 for every pair with
+ * 128 M / L + 642 <= 7168 (all of them up to 12.8 MSa/s -> 256 kSa/s); above, 4 ceil(16.384 (M / L) / 4), which keeps the 64 us of
+ * capture 640 taps per phase span at 10 MSa/s (20.48 MSa/s -> 1312, 32.768 MSa/s -> 2100).  FMD_ERR_ARG for rates fmd_chan_design refuses.
+ * fmd_chan_create accepts every pair with M / L <= 128 and L <= 64, with 4 to 4096 taps per phase. */
+int fmd_chan_default_taps_per_phase(double fs_in, double fs_out);
 int fmd_chan_create(const fmd_chan_config* cfg, fmd_channelizer* out);
 int fmd_chan_destroy(fmd_channelizer h);
 int fmd_chan_reset(fmd_channelizer h);
