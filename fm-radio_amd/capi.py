@@ -185,7 +185,8 @@ def load_library():
     L.fmd_chan_reset.argtypes = [C.c_void_p]
     L.fmd_chan_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
     L.fmd_chan_get_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
-    L.fmd_chan_process_cf32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
+    for fmt in ("cf32", "u8", "s8", "s16"):
+        getattr(L, f"fmd_chan_process_{fmt}_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
     L.fmd_chan_last_error.restype = C.c_char_p
     L.fmd_chan_last_error.argtypes = [C.c_void_p]
     L.fmd_resampler_design.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
@@ -658,7 +659,7 @@ def chan_default_taps(fs_in: float, fs_out: float = 256_000.0) -> int:
 
 
 class Channelizer:
-    """Wideband capture -> [C][n_out] cf32 stations at fs_out on the GPU (fmd_chan_*); feeds BatchDemod.process directly.
+    """Wideband capture (cf32, u8, s8 or s16) -> [C][n_out] cf32 stations at fs_out on the GPU (fmd_chan_*); feeds BatchDemod.process directly.
 
     Accepts every pair of integer rates with fs_out / fs_in = L / M, L <= 64 and M / L <= 128 (fs_in up to 32.768 MSa/s at 256 kSa/s:
     the whole FM band in one capture), with 4 to 4096 taps per phase; taps_per_phase=0 takes chan_default_taps(fs_in, fs_out).  Kernels:
@@ -686,10 +687,14 @@ class Channelizer:
         return a
 
     def process(self, wide, out=None, stream=None):
-        """wide: contiguous CUDA float32 tensor [n_in, 2]; returns a CUDA tensor [C, n_out, 2] (asynchronous on the stream)."""
+        """wide: contiguous CUDA tensor [n_in, 2] of interleaved I, Q: float32, or a receiver's uint8 (RTL-SDR: v - 127), int8 (HackRF) or
+        int16 (Airspy, SDRplay, USRP sc16), read as is (no conversion pass); returns a CUDA float32 tensor [C, n_out, 2] (asynchronous on
+        the stream).  An integer capture gives the bits the float32 call gives on its conversion; formats may change from call to call."""
         import torch
-        if not (wide.is_cuda and wide.is_contiguous() and wide.dtype == torch.float32 and wide.dim() == 2 and wide.shape[1] == 2):
-            raise ValueError("wide must be a contiguous CUDA float32 tensor [n_in, 2]")
+        fns = {torch.float32: self.L.fmd_chan_process_cf32_dev, torch.uint8: self.L.fmd_chan_process_u8_dev,
+               torch.int8: self.L.fmd_chan_process_s8_dev, torch.int16: self.L.fmd_chan_process_s16_dev}
+        if not (wide.is_cuda and wide.is_contiguous() and wide.dtype in fns and wide.dim() == 2 and wide.shape[1] == 2):
+            raise ValueError("wide must be a contiguous CUDA tensor [n_in, 2] of float32, uint8, int8 or int16")
         n_in = int(wide.shape[0])
         n_out = n_in * self.interp // self.decim
         if out is None:
@@ -697,7 +702,7 @@ class Channelizer:
         if stream is None:
             stream = torch.cuda.current_stream(wide.device).cuda_stream
         got = C.c_size_t(0)
-        rc = self.L.fmd_chan_process_cf32_dev(self.h, wide.data_ptr(), n_in, out.data_ptr(), int(out.shape[1]), C.byref(got), C.c_void_p(stream))
+        rc = fns[wide.dtype](self.h, wide.data_ptr(), n_in, out.data_ptr(), int(out.shape[1]), C.byref(got), C.c_void_p(stream))
         if rc != FMD_OK:
             raise FmdError(rc, self.L.fmd_chan_last_error(self.h).decode())
         return out[:, :got.value]

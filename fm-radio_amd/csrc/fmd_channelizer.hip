@@ -21,6 +21,12 @@
 //     in a fixed order.
 // Requires L == 16 (10 MSa/s -> 256 kSa/s and every other pair of rates with fs_out / gcd = 16) for this mapping; other ratios
 // take the general kernel below (one output per thread), which is what round 1 had.
+//
+// Sample formats.  The caller's block is interleaved I, Q of one of four types: cf32, or a receiver's integers — u8 (RTL-SDR), s8
+// (HackRF), s16 (Airspy, SDRplay, USRP sc16).  Every kernel is a template over that type (Iq<S> below), which only changes the block's
+// loads: a lane fetches a pair with ONE load of its width (8, 2 or 4 bytes) at the same sample the cf32 form fetches, and converts it
+// exactly ((float)v - 127 for u8, (float)v otherwise) before any arithmetic.  So a call on integers writes the bits a cf32 call writes on
+// the converted samples, and the history buffers stay cf32: consecutive calls on one handle may change format.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -30,6 +36,7 @@
 #include <cstring>
 #include <numeric>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 #include "fmdemod.h"
@@ -51,23 +58,57 @@ struct ChanDims {
     int tile;                   // outputs per workgroup of k_channelize: kTile, fewer where its window would not fit (whole-band rates)
 };
 
+// One I / Q pair of the caller's block: `raw`, what one load fetches (all of the pair), and cf32(), its exact conversion.  A conversion
+// is a separate rounding-free step: every integer of these types is a float, and v - 127 of a u8 is exact (-ffp-contract=off keeps it
+// out of the mixer's fmaf).  zero() is the raw pair that converts to (+0, +0): what a window sample outside the data reads as.
+template <typename S> struct Iq;
+template <> struct Iq<float2> {
+    using raw = float2;
+    static __device__ __forceinline__ raw zero() { return make_float2(0.f, 0.f); }
+    static __device__ __forceinline__ const float2& cf32(const raw& v) { return v; }   // (no copy: the cf32 kernels' code stays as it was)
+};
+template <> struct Iq<uint8_t> {          // RTL-SDR: the reference's (float)u8 - 127 (src/app.cpp), as fmd_process_u8_* takes it
+    using raw = unsigned short;
+    static __device__ __forceinline__ raw zero() { return 0x7f7f; }
+    static __device__ __forceinline__ float2 cf32(raw v) { return make_float2((float)(v & 0xffu) - 127.0f, (float)(v >> 8) - 127.0f); }
+};
+template <> struct Iq<int8_t> {           // HackRF
+    using raw = unsigned short;
+    static __device__ __forceinline__ raw zero() { return 0; }
+    static __device__ __forceinline__ float2 cf32(raw v) { return make_float2((float)(signed char)(v & 0xffu), (float)(signed char)(v >> 8)); }
+};
+template <> struct Iq<int16_t> {          // Airspy, SDRplay, USRP sc16
+    using raw = unsigned int;
+    static __device__ __forceinline__ raw zero() { return 0; }
+    static __device__ __forceinline__ float2 cf32(raw v) { return make_float2((float)(short)(v & 0xffffu), (float)(short)(v >> 16)); }
+};
+
 // The window of a call is [T - 1 history samples][the caller's block]: two buffers, read in place (round 5: staging the block behind the
 // history and copying the new history out were two device copies around every launch — 5 us each plus the queue's gaps, a quarter of a
 // 10 MSa/s block's 100 us on the channeliser's queue).  The launch's first workgroup hands the last T - 1 samples over to the OTHER
-// history buffer, which no workgroup of this launch reads.
-struct ChanWin { const float2* hist; const float2* blk; float2* next_hist; };
-__device__ __forceinline__ float2 win_at(const ChanDims& d, const ChanWin& w, long long j) {
-    // (base and index are selected, then ONE load, no branch; the address is never formed from `blk` with a negative offset — ADVICE r5)
+// history buffer, which no workgroup of this launch reads.  The history is cf32 whatever the block's type: it holds converted samples.
+template <typename S> struct ChanWin { const float2* hist; const typename Iq<S>::raw* blk; float2* next_hist; };
+template <typename S>
+__device__ __forceinline__ float2 win_at(const ChanDims& d, const ChanWin<S>& w, long long j) {
     const long long jb = j - (d.T - 1);
-    const float2* base = jb < 0 ? w.hist : w.blk;
-    return base[jb < 0 ? j : jb];
+    if constexpr (std::is_same<S, float2>::value) {
+        // (base and index are selected, then ONE load, no branch; the address is never formed from `blk` with a negative offset — ADVICE r5)
+        const float2* base = jb < 0 ? w.hist : w.blk;
+        return base[jb < 0 ? j : jb];
+    } else {
+        // two buffers of two types: a lane loads from the one its sample is in (the history only in front of a call's first windows)
+        if (jb < 0) return w.hist[j];
+        return Iq<S>::cf32(w.blk[jb]);
+    }
 }
-__device__ __forceinline__ void hand_over_history(const ChanDims& d, const ChanWin& w) {
+template <typename S>
+__device__ __forceinline__ void hand_over_history(const ChanDims& d, const ChanWin<S>& w) {
     if (blockIdx.x == 0 && blockIdx.y == 0)
         for (int i = threadIdx.x; i < d.T - 1; i += 256) w.next_hist[i] = win_at(d, w, d.n_in + i);
 }
 // window staging shared by both kernels: xs[i] = win[n_lo + i] * exp(-j 2 pi f n / fs)
-__device__ __forceinline__ void stage_mixed(const ChanDims& d, const ChanWin& win, unsigned long long n_lo, int n_win,
+template <typename S>
+__device__ __forceinline__ void stage_mixed(const ChanDims& d, const ChanWin<S>& win, unsigned long long n_lo, int n_win,
                                             unsigned long long inc, float2* xs) {
     // phase in turns = frac(n_abs * f_k / fs_in), exact in 64-bit modular arithmetic, then one rounding to float
     const unsigned long long n_first = n_lo + (unsigned long long)threadIdx.x;
@@ -86,7 +127,8 @@ __device__ __forceinline__ void stage_mixed(const ChanDims& d, const ChanWin& wi
 }
 
 // L == 16: see the header comment
-__global__ __launch_bounds__(256) void k_channelize16(ChanDims d, ChanWin win, const float* __restrict__ taps /* [T][16] */,
+template <typename S>
+__global__ __launch_bounds__(256) void k_channelize16(ChanDims d, ChanWin<S> win, const float* __restrict__ taps /* [T][16] */,
                                                       const unsigned long long* __restrict__ phase_inc, float2* __restrict__ out) {
     constexpr int L = 16, PER = kTile / L;                    // 8 outputs of a branch per tile
     constexpr int kMaxSlice = 64;                             // taps per slice held in registers (T <= 1024)
@@ -137,6 +179,9 @@ __global__ __launch_bounds__(256) void k_channelize16(ChanDims d, ChanWin win, c
     }
 }
 
+// (instantiated here rather than at its launch: emitted in this order, the cf32 form is the instruction stream the kernel had before it was a template)
+template __global__ void k_channelize16<float2>(ChanDims, ChanWin<float2>, const float*, const unsigned long long*, float2*);
+
 // L == 16 on the matrix cores (round 4).  The 16 consecutive outputs o = 16 g + m of a "group" g use each polyphase branch once
 // (p = m M mod 16) and read the input window x[g M - (T - 1) + tau], tau < K = floor(15 M / 16) + T (1225 at 625 / 640):
 //     y[16 g + m] = sum_tau A[m][tau] x[g M - (T - 1) + tau],   A[m][tau] = h[p(m) + 16 t],  t = floor(m M / 16) + T - 1 - tau  (0 <= t < T, else 0)
@@ -155,7 +200,8 @@ typedef float f32x4_t __attribute__((ext_vector_type(4)));
 // Non-finite input: the banded operand multiplies EVERY staged sample of a group's 1232-sample window, its structural zeros included, so
 // one Inf / NaN input sample makes all 16 outputs of every group whose window holds it NaN (the VALU form only those with a real tap on
 // it).  A capture from a device is u8 / finite by construction; a host that may feed non-finite floats filters them at its boundary.
-__global__ __launch_bounds__(256, 3) void k_channelize16_mfma(ChanDims d, ChanWin win, const float* __restrict__ atab /* [4][77][64] */,
+template <typename S>
+__global__ __launch_bounds__(256, 3) void k_channelize16_mfma(ChanDims d, ChanWin<S> win, const float* __restrict__ atab /* [4][77][64] */,
                                                            const unsigned long long* __restrict__ phase_inc, float2* __restrict__ out, int n_tiles) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* xr = smem;                       // mixed window, real rail: xr[i] = Re x_k[n_lo + i]
@@ -182,20 +228,25 @@ __global__ __launch_bounds__(256, 3) void k_channelize16_mfma(ChanDims d, ChanWi
             sincospif((float)(unsigned int)(((n_lo + (unsigned long long)tid) * inc) >> 32) * 4.656612873077393e-10f, &s, &c);
             const long long j0 = (long long)(n_lo - d.n_base);
             constexpr int PER = (kMRail + 255) / 256;
-            float2 x[PER];
+            using raw = typename Iq<S>::raw;
+            raw x[PER];                                   // (as loaded: one register a sample for u8 / s8 / s16, converted where it is mixed)
             // the caller's block through ONE base and immediate offsets (per-sample pointers for all 22 spilled registers); the history's
             // samples — in front of a call's first windows only — are patched in behind, a sample at a time
             const long long jb = j0 - (d.T - 1);          // where the window starts in the block: negative in front of a call's first windows
-            // (the base of the immediate offsets, made by INTEGER arithmetic: with jb < 0 it lies in front of the block and `win.blk + jb` would be
-            //  pointer arithmetic out of the array — ADVICE r5; only elements i >= -jb are ever read through it)
-            const float2* src = reinterpret_cast<const float2*>(reinterpret_cast<uintptr_t>(win.blk) + (uintptr_t)(jb * (long long)sizeof(float2)));
+            // (the base of the immediate offsets, made by INTEGER arithmetic in bytes of the block's pairs: with jb < 0 it lies in front of the block
+            //  and `win.blk + jb` would be pointer arithmetic out of the array — ADVICE r5; only elements i >= -jb are ever read through it)
+            const raw* src = reinterpret_cast<const raw*>(reinterpret_cast<uintptr_t>(win.blk) + (uintptr_t)(jb * (long long)sizeof(raw)));
             const int i_lo = jb < 0 ? (int)(-jb) : 0;     // (one unsigned compare per sample: i_lo <= i < n_valid)
 #pragma unroll
-            for (int r = 0; r < PER; r++) { const int i = tid + 256 * r; x[r] = ((unsigned)(i - i_lo) < (unsigned)(n_valid - i_lo)) ? src[i] : make_float2(0.f, 0.f); }
+            for (int r = 0; r < PER; r++) { const int i = tid + 256 * r; x[r] = ((unsigned)(i - i_lo) < (unsigned)(n_valid - i_lo)) ? src[i] : Iq<S>::zero(); }
 #pragma unroll
             for (int r = 0; r < PER; r++) {
                 const int i = tid + 256 * r;
-                if (i < kMRail) { xr[i] = fmaf(x[r].x, c, x[r].y * s); xi[i] = fmaf(x[r].y, c, -(x[r].x * s)); }   // x * (cos - j sin)
+                // (integers: an empty asm pins the loaded value here, after all the loads — without it the compiler moved s8's conversion into
+                //  the conditional loads, each load waited for in turn: 1.44x the cf32 kernel's time)
+                if constexpr (!std::is_same<S, float2>::value) asm("" : "+v"(x[r]));
+                const float2& v = Iq<S>::cf32(x[r]);
+                if (i < kMRail) { xr[i] = fmaf(v.x, c, v.y * s); xi[i] = fmaf(v.y, c, -(v.x * s)); }   // x * (cos - j sin)
                 const float cn = fmaf(c, cs, -(s * ss)), sn = fmaf(s, cs, c * ss);
                 c = cn; s = sn;
             }
@@ -257,7 +308,8 @@ struct BandPlan {
 };
 __device__ __forceinline__ int band_pos(int i) { return i + (i >> 8); }
 
-__global__ __launch_bounds__(256) void k_channelize_band_mfma(ChanDims d, ChanWin win, const float* __restrict__ hrev /* [L][T] reversed */,
+template <typename S>
+__global__ __launch_bounds__(256) void k_channelize_band_mfma(ChanDims d, ChanWin<S> win, const float* __restrict__ hrev /* [L][T] reversed */,
                                                               const unsigned long long* __restrict__ phase_inc, float2* __restrict__ out,
                                                               BandPlan bp, int n_tiles) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -295,13 +347,35 @@ __global__ __launch_bounds__(256) void k_channelize_band_mfma(ChanDims d, ChanWi
 #pragma unroll 1
         for (int ib = 0; ib < bp.n_win; ib += 16 * 256) {
             float2 x[16];
+            if constexpr (std::is_same<S, float2>::value) {
 #pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const int i = ib + tid + 256 * r;
-                const long long j = j0 + i;
-                const bool ok = i < bp.n_win && j >= 0 && j < n_have;
-                const float2 v = win_at(d, win, j < 0 ? 0 : (j < n_have ? j : n_have - 1));   // (an address inside [history ++ block] either way)
-                x[r] = ok ? v : make_float2(0.f, 0.f);
+                for (int r = 0; r < 16; r++) {
+                    const int i = ib + tid + 256 * r;
+                    const long long j = j0 + i;
+                    const bool ok = i < bp.n_win && j >= 0 && j < n_have;
+                    const float2 v = win_at(d, win, j < 0 ? 0 : (j < n_have ? j : n_have - 1));   // (an address inside [history ++ block] either way)
+                    x[r] = ok ? v : make_float2(0.f, 0.f);
+                }
+            } else {
+                // the block's samples as loaded, all 16 in flight (each lane loads from the block — element 0 for a sample in the history, a
+                // read inside the block — and converts after the loads: a load and conversion under a branch per sample waited for each load
+                // in turn, 1.3x the cf32 kernel's time); then the history's samples, in front of a call's first windows only, patched in
+                typename Iq<S>::raw xw[16];
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const long long j = j0 + (ib + tid + 256 * r);
+                    const long long jb = (j < n_have ? j : n_have - 1) - (T - 1);
+                    xw[r] = win.blk[jb < 0 ? 0 : jb];
+                }
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int i = ib + tid + 256 * r;
+                    const long long j = j0 + i;
+                    const bool ok = i < bp.n_win && j >= 0 && j < n_have;
+                    float2 v = Iq<S>::cf32(xw[r]);
+                    if (ok && j < T - 1) v = win.hist[j];
+                    x[r] = ok ? v : make_float2(0.f, 0.f);
+                }
             }
             float s, c;
             sincospif((float)(unsigned int)(((n_lo + (unsigned long long)(ib + tid)) * inc) >> 32) * 4.656612873077393e-10f, &s, &c);
@@ -355,7 +429,8 @@ __global__ __launch_bounds__(256) void k_channelize_band_mfma(ChanDims d, ChanWi
 // any L <= 64: one output per thread (the first d.tile <= 128 threads), taps read from global memory.  A tile is kTile outputs for every
 // rate pair whose window of 128 outputs fits kMaxWindow; beyond that (M / L up to 128, T up to 4096) 64, 32 or 16 outputs, whatever fits.
 // An output's sum does not depend on the tile.
-__global__ __launch_bounds__(256) void k_channelize(ChanDims d, ChanWin win, const float* __restrict__ taps /* [T][L] */,
+template <typename S>
+__global__ __launch_bounds__(256) void k_channelize(ChanDims d, ChanWin<S> win, const float* __restrict__ taps /* [T][L] */,
                                                     const unsigned long long* __restrict__ phase_inc /* [C], turns * 2^64 per input sample */,
                                                     float2* __restrict__ out /* [C][out_stride] */) {
     __shared__ float2 xs[kMaxWindow];
@@ -446,6 +521,16 @@ static BandPlan band_plan(int L, int M, int T) {
 }
 
 static size_t band_lds_bytes(const BandPlan& bp, int L, int T) { return sizeof(float) * (2 * (size_t)bp.rail + (size_t)L * T); }
+
+// the dynamic LDS limit of a matrix-core form, for each sample type's instantiation
+template <typename K> static bool set_max_lds(K kernel, size_t bytes) {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) == hipSuccess;
+}
+template <template <typename> class F> static bool set_max_lds_all(size_t bytes) {
+    return set_max_lds(F<float2>::k, bytes) && set_max_lds(F<uint8_t>::k, bytes) && set_max_lds(F<int8_t>::k, bytes) && set_max_lds(F<int16_t>::k, bytes);
+}
+template <typename S> struct MfmaForm { static constexpr auto k = k_channelize16_mfma<S>; };
+template <typename S> struct BandForm { static constexpr auto k = k_channelize_band_mfma<S>; };
 
 extern "C" {
 
@@ -547,7 +632,7 @@ int fmd_chan_create(const fmd_chan_config* cfg, fmd_channelizer* out) {
                 }
         ok = hipMalloc(&h->atab, sizeof(float) * at.size()) == hipSuccess &&
              hipMemcpy(h->atab, at.data(), sizeof(float) * at.size(), hipMemcpyHostToDevice) == hipSuccess &&
-             hipFuncSetAttribute(reinterpret_cast<const void*>(k_channelize16_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * (2 * kMRail + 4 * 256))) == hipSuccess;
+             set_max_lds_all<MfmaForm>(sizeof(float) * (2 * kMRail + 4 * 256));
     }
     if (ok && bp.G > 0) {
         std::vector<float> hr((size_t)L * T);
@@ -555,7 +640,7 @@ int fmd_chan_create(const fmd_chan_config* cfg, fmd_channelizer* out) {
             for (int u = 0; u < T; u++) hr[(size_t)p * T + u] = h->h_taps[(size_t)(T - 1 - u) * L + p];
         ok = hipMalloc(&h->hrev, sizeof(float) * hr.size()) == hipSuccess &&
              hipMemcpy(h->hrev, hr.data(), sizeof(float) * hr.size(), hipMemcpyHostToDevice) == hipSuccess &&
-             hipFuncSetAttribute(reinterpret_cast<const void*>(k_channelize_band_mfma), hipFuncAttributeMaxDynamicSharedMemorySize, (int)band_lds_bytes(bp, L, T)) == hipSuccess;
+             set_max_lds_all<BandForm>(band_lds_bytes(bp, L, T));
     }
     if (!ok) { fmd_chan_destroy(h); return chan_fail(nullptr, FMD_ERR_DEVICE, "device allocation failed"); }
     *out = h;
@@ -599,7 +684,11 @@ int fmd_chan_reset(fmd_channelizer h) {
     return FMD_OK;
 }
 
-int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_in, float* d_out, size_t out_capacity_per_station, size_t* n_out, void* stream) {
+}  // extern "C"
+
+// the body of every fmd_chan_process_*_dev: S is the block's sample type (Iq<S>); checks, kernel selection and state are the same for all
+template <typename S>
+static int chan_process(fmd_channelizer h, const void* d_wide, size_t n_in, float* d_out, size_t out_capacity_per_station, size_t* n_out, void* stream) {
     if (!h || !d_wide || !d_out || !n_out) return FMD_ERR_ARG;
     if (n_in == 0 || n_in > h->max_in) return chan_fail(h, FMD_ERR_SIZE, "n_in %zu outside (0, %zu]", n_in, h->max_in);
     if ((n_in * (size_t)h->L) % (size_t)h->M != 0) return chan_fail(h, FMD_ERR_SIZE, "n_in must be a multiple of %d so that a whole number of output samples results", h->M / std::gcd(h->L, h->M));
@@ -611,7 +700,7 @@ int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_i
     // the windows carry state from call to call: a caller that switches streams is ordered behind the previous call's work
     if (h->have_done && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "stream wait failed");
     // window = [T-1 history samples][this block], read in place; its first sample has absolute input index n_abs - (T-1)
-    const ChanWin win{h->win[h->cur], reinterpret_cast<const float2*>(d_wide), h->win[h->cur ^ 1]};
+    const ChanWin<S> win{h->win[h->cur], static_cast<const typename Iq<S>::raw*>(d_wide), h->win[h->cur ^ 1]};
     ChanDims d{h->L, h->M, T, h->C, (long long)no, (long long)out_capacity_per_station, h->o_abs, h->n_abs - (unsigned long long)(T - 1), (long long)n_in, h->tile};
     // outputs o0 .. o0+no-1 need inputs up to floor((o0+no-1) M / L) <= n_abs + n_in - 1 by construction
     if (h->hrev) {
@@ -621,7 +710,7 @@ int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_i
         const unsigned long long g_first = h->o_abs / 16, g_last = (h->o_abs + no - 1) / 16;
         const int n_tiles = (int)((g_last - g_first) / (unsigned long long)bp.G + 1);
         const int gx = (n_tiles + 3) / 4;
-        hipLaunchKernelGGL(k_channelize_band_mfma, dim3((unsigned)gx, (unsigned)h->C), dim3(256), band_lds_bytes(bp, h->L, T), s, d, win, h->hrev, h->inc,
+        hipLaunchKernelGGL(k_channelize_band_mfma<S>, dim3((unsigned)gx, (unsigned)h->C), dim3(256), band_lds_bytes(bp, h->L, T), s, d, win, h->hrev, h->inc,
                            reinterpret_cast<float2*>(d_out), bp, n_tiles);
     } else if (h->atab) {
         // every workgroup keeps its operand registers over several tiles
@@ -631,13 +720,13 @@ int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_i
         // with three, x571-581 with two (profiles/round5/rds_stage_ab.txt)
         int gx = (2 * 256) / h->C;
         gx = gx < 1 ? 1 : (gx > n_tiles ? n_tiles : gx);
-        hipLaunchKernelGGL(k_channelize16_mfma, dim3((unsigned)gx, (unsigned)h->C), dim3(256), sizeof(float) * (2 * kMRail + 4 * 256), s, d, win, h->atab, h->inc,
+        hipLaunchKernelGGL(k_channelize16_mfma<S>, dim3((unsigned)gx, (unsigned)h->C), dim3(256), sizeof(float) * (2 * kMRail + 4 * 256), s, d, win, h->atab, h->inc,
                            reinterpret_cast<float2*>(d_out), n_tiles);
     } else if (h->legacy && h->L == 16 && T % 64 == 0 && T <= 1024)
-        hipLaunchKernelGGL(k_channelize16, dim3((unsigned)((no + kTile - 1) / kTile), (unsigned)h->C), dim3(256), 0, s, d, win, h->taps, h->inc,
+        hipLaunchKernelGGL(k_channelize16<S>, dim3((unsigned)((no + kTile - 1) / kTile), (unsigned)h->C), dim3(256), 0, s, d, win, h->taps, h->inc,
                            reinterpret_cast<float2*>(d_out));
     else
-        hipLaunchKernelGGL(k_channelize, dim3((unsigned)((no + h->tile - 1) / h->tile), (unsigned)h->C), dim3(256), 0, s, d, win, h->taps, h->inc,
+        hipLaunchKernelGGL(k_channelize<S>, dim3((unsigned)((no + h->tile - 1) / h->tile), (unsigned)h->C), dim3(256), 0, s, d, win, h->taps, h->inc,
                            reinterpret_cast<float2*>(d_out));
     if (hipGetLastError() != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "k_channelize launch failed");
     // (the last T-1 samples of [history ++ block] are the next call's history: the launch's first workgroup has written them into the
@@ -648,6 +737,21 @@ int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_i
     h->n_abs += n_in; h->o_abs += no;
     *n_out = no;
     return FMD_OK;
+}
+
+extern "C" {
+
+int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_in, float* d_out, size_t out_capacity_per_station, size_t* n_out, void* stream) {
+    return chan_process<float2>(h, d_wide, n_in, d_out, out_capacity_per_station, n_out, stream);
+}
+int fmd_chan_process_u8_dev(fmd_channelizer h, const uint8_t* d_wide, size_t n_in, float* d_out, size_t out_capacity_per_station, size_t* n_out, void* stream) {
+    return chan_process<uint8_t>(h, d_wide, n_in, d_out, out_capacity_per_station, n_out, stream);
+}
+int fmd_chan_process_s8_dev(fmd_channelizer h, const int8_t* d_wide, size_t n_in, float* d_out, size_t out_capacity_per_station, size_t* n_out, void* stream) {
+    return chan_process<int8_t>(h, d_wide, n_in, d_out, out_capacity_per_station, n_out, stream);
+}
+int fmd_chan_process_s16_dev(fmd_channelizer h, const int16_t* d_wide, size_t n_in, float* d_out, size_t out_capacity_per_station, size_t* n_out, void* stream) {
+    return chan_process<int16_t>(h, d_wide, n_in, d_out, out_capacity_per_station, n_out, stream);
 }
 
 const char* fmd_chan_last_error(fmd_channelizer h) { return h ? h->err.c_str() : g_chan_error.c_str(); }

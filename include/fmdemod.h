@@ -357,8 +357,8 @@ const char* fmd_rdsdec_last_error(fmd_rdsdec d);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Wideband channeliser (SURVEY.md §8f row 3 / BASELINE configs[4]; NOT part of the reference, which tunes one station in
- * the RTL-SDR hardware): splits one wideband cf32 capture into n_stations channels at fs_out, laid out [C][n_out] cf32 —
- * the input layout of fmd_process_cf32_dev.  Per station: mix the centre frequency to 0, then a rational polyphase
+ * the RTL-SDR hardware): splits one wideband capture — cf32, or a receiver's interleaved u8 (RTL-SDR), s8 (HackRF) or s16
+ * (Airspy, SDRplay, USRP sc16) — into n_stations channels at fs_out, laid out [C][n_out] cf32 — the input layout of fmd_process_cf32_dev.  Per station: mix the centre frequency to 0, then a rational polyphase
  * decimator L/M = fs_out/fs_in (256 k / 10 M = 16 / 625) built from one Kaiser-windowed prototype (cut-off fs_out / 2,
  * 60 dB).  Streaming: histories and the mixers' phases carry over from call to call.
  * ------------------------------------------------------------------------------------------------------------------ */
@@ -392,6 +392,18 @@ int fmd_chan_get_taps(fmd_channelizer h, float* taps, size_t cap_floats);
  * kernel (no staging copy): like d_out it belongs to the call until its work on `stream` has completed. */
 int fmd_chan_process_cf32_dev(fmd_channelizer h, const float* d_wide, size_t n_in, float* d_out, size_t out_capacity_per_station,
                               size_t* n_out, void* stream);
+/* The same call on a receiver's integer capture, d_wide [n_in][2] interleaved I, Q on the device, read without a conversion pass.
+ * Each pair becomes a float exactly: u8 as (float)v - 127 (the reference's and fmd_process_u8_*'s convention), s8 and s16 as (float)v,
+ * unscaled (the discriminator and the RDS AGC do not depend on level).  A call on integer samples writes exactly the bits that
+ * fmd_chan_process_cf32_dev writes when given the converted samples, for every rate pair, kernel and split of the input into calls.
+ * The history holds converted samples, so consecutive calls on one handle may use different formats; arguments, errors, streams
+ * and fmd_chan_reset are those of fmd_chan_process_cf32_dev. */
+int fmd_chan_process_u8_dev(fmd_channelizer h, const uint8_t* d_wide, size_t n_in, float* d_out, size_t out_capacity_per_station,
+                            size_t* n_out, void* stream);
+int fmd_chan_process_s8_dev(fmd_channelizer h, const int8_t* d_wide, size_t n_in, float* d_out, size_t out_capacity_per_station,
+                            size_t* n_out, void* stream);
+int fmd_chan_process_s16_dev(fmd_channelizer h, const int16_t* d_wide, size_t n_in, float* d_out, size_t out_capacity_per_station,
+                             size_t* n_out, void* stream);
 const char* fmd_chan_last_error(fmd_channelizer h);
 
 /* ------------------------------------------------------------------------------------------------------------------
