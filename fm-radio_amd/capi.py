@@ -85,6 +85,11 @@ class ResamplerConfig(C.Structure):
 FMD_RESAMPLE_REFERENCE, FMD_RESAMPLE_POLYPHASE = 0, 1
 
 
+class MixerConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("n_buses", C.c_int), ("bus_offsets", C.c_void_p), ("bus_sources", C.c_void_p),
+                ("gains", C.c_void_p), ("device", C.c_int)]
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("total_ms", C.c_double), ("launches", C.c_int)]
 
@@ -199,6 +204,15 @@ def load_library():
         getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]
     L.fmd_resampler_last_error.restype = C.c_char_p
     L.fmd_resampler_last_error.argtypes = [C.c_void_p]
+    L.fmd_mixer_create.argtypes = [C.POINTER(MixerConfig), C.POINTER(C.c_void_p)]
+    L.fmd_mixer_destroy.argtypes = [C.c_void_p]
+    L.fmd_mixer_set_sources.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
+    L.fmd_mixer_set_gain.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    L.fmd_mixer_get_gain.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
+    for name in ("fmd_mixer_process_f32_dev", "fmd_mixer_process_f32_host"):
+        getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
+    L.fmd_mixer_last_error.restype = C.c_char_p
+    L.fmd_mixer_last_error.argtypes = [C.c_void_p]
     L.fmd_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.argtypes = [C.c_void_p]
@@ -818,3 +832,88 @@ class AudioResampler:
         """The same as the scraper's 16-bit PCM frames: [C, n_out, 2] int16."""
         import torch
         return self._run(self.L.fmd_resampler_process_pcm16_dev, x, n_in, torch.int16, out, stream)
+
+
+class AudioMixer:
+    """B output buses on the GPU (fmd_mixer_*), each one reference AudioMixer: bus b plays
+    clamp(sum over its delivering sources, in order, of fmaf(x, gain_b / log10f(10 k), acc)), bit-identical to the reference's build.
+    buses: a list of B lists of station rows in registration (CreateManagedBuffer) order; a row may appear in many buses.
+    Feed it the same [C, n, 2] float32 CUDA tensors as AudioResampler (BatchDemod.audio_tensor() or a resampler's output)."""
+
+    def __init__(self, n_channels: int, buses, gains=None, device: int = -1):
+        self.L = load_library()
+        buses = [list(map(int, b)) for b in buses]
+        offs = np.zeros(len(buses) + 1, np.int32)
+        offs[1:] = np.cumsum([len(b) for b in buses])
+        src = np.array([r for b in buses for r in b] or [0], np.int32)
+        g = None if gains is None else np.ascontiguousarray(gains, np.float32)
+        if g is not None and g.shape != (len(buses),):
+            raise ValueError("gains must hold one value per bus")
+        cfg = MixerConfig(int(n_channels), len(buses), offs.ctypes.data, src.ctypes.data, None if g is None else g.ctypes.data, device)
+        self.m = C.c_void_p()
+        rc = self.L.fmd_mixer_create(C.byref(cfg), C.byref(self.m))
+        if rc != FMD_OK:
+            self.m = None
+            raise FmdError(rc, self.L.fmd_mixer_last_error(None).decode() or self.L.fmd_status_string(rc).decode())
+        self.n_channels, self.n_buses = int(n_channels), len(buses)
+
+    def close(self):
+        if getattr(self, "m", None):
+            self.L.fmd_mixer_destroy(self.m)
+            self.m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc < 0:
+            raise FmdError(rc, (self.L.fmd_mixer_last_error(self.m) or b"").decode() or self.L.fmd_status_string(rc).decode())
+        return rc
+
+    def set_sources(self, bus: int, sources):
+        """replace a bus's sources (registration order); applies from the next process call"""
+        rows = [int(r) for r in sources]
+        src = np.array(rows or [0], np.int32)
+        self._check(self.L.fmd_mixer_set_sources(self.m, int(bus), src.ctypes.data_as(C.c_void_p), len(rows)))
+
+    def set_gain(self, bus: int, g: float):
+        """AudioMixer::GetOutputGain() = g for one bus (-1: every bus); applies from the next process call"""
+        self._check(self.L.fmd_mixer_set_gain(self.m, int(bus), C.c_float(g)))
+
+    def gain(self, bus: int) -> float:
+        g = C.c_float(0.0)
+        self._check(self.L.fmd_mixer_get_gain(self.m, int(bus), C.byref(g)))
+        return g.value
+
+    def process(self, x, n: int | None = None, active=None, out=None, stream=None):
+        """AudioMixer::UpdateMixer for every bus.  x: [C, >= n, 2] float32 on the device, contiguous frames (the first n frames are
+        read, default all); active: None (every station delivered) or a [C] uint8 / bool CUDA tensor; out: [B, >= n, 2] float32.
+        Returns [B, n, 2] float32, asynchronous on `stream` (default: torch's current stream)."""
+        import torch
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
+                and x.stride(2) == 1 and x.stride(1) == 2):
+            raise ValueError("x must be a CUDA float32 tensor [C, n, 2] with contiguous frames")
+        n = int(x.shape[1]) if n is None else int(n)
+        if out is None:
+            out = torch.empty((self.n_buses, max(n, 1), 2), dtype=torch.float32, device=x.device)
+        if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and out.shape[0] == self.n_buses and out.stride(2) == 1
+                and out.stride(1) == 2):
+            raise ValueError("out must be a CUDA float32 tensor [B, n, 2] with contiguous frames")
+        if active is not None:
+            if active.dtype == torch.bool:
+                active = active.view(torch.uint8)
+            if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (self.n_channels,) and active.is_contiguous()):
+                raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
+        out_stride = out.stride(0) // 2 if out.shape[0] > 1 else out.shape[1]
+        self._check(self.L.fmd_mixer_process_f32_dev(self.m, C.c_void_p(x.data_ptr()), in_stride, n,
+                                                     None if active is None else C.c_void_p(active.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                     out_stride, C.c_void_p(stream)))
+        return out[:, :n]

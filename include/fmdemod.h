@@ -467,6 +467,48 @@ int fmd_resampler_process_f32_host(fmd_resampler r, const float* d_in, long long
                                    float* out, long long out_stride, long long* n_out, void* stream);
 const char* fmd_resampler_last_error(fmd_resampler r);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Batched audio mixer: the stage between the listener's ring buffers and PortAudio (reference AudioMixer::UpdateMixer,
+ * src/audio/audio_mixer.cpp:33-79; src/audio/portaudio_output.cpp:84).  B independent buses, each one reference AudioMixer; every bus
+ * reads the same device array of station audio [C][in_stride][2] (fmd_audio_dev's view at 32 kHz, or a resampler's output at the
+ * playback rate) and changes nothing in the stage that wrote it.  Per call and bus, bit-identical to the reference's build:
+ *   k      = the bus's sources whose station delivered (d_active[row] != 0; a row listed twice counts twice)
+ *   k == 0 : every output is +0
+ *   scale  = gain / log10f((float)k * 10.0f)   (host libm's log10f, on the host; denormal gain or scale -> zero of its sign)
+ *   acc    = +0; for each delivering source in registration order: acc = fmaf(x, scale, acc), denormal inputs and results
+ *            flushed to zeros of their sign (the reference links crtfastmath: FTZ + DAZ)
+ *   out    = t < 1 ? t : 1 with t = (-1 > acc) ? -1 : acc   (x86 vmaxss / vminss order: NaN -> +1, +-inf -> +-1)
+ * No state carries over between calls, so a bus's output does not depend on how its frames are split into calls, on the batch or on
+ * the bus's row.  Splitting frames into ring-buffer blocks is the caller's business.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_mixer_s* fmd_mixer;
+typedef struct {
+    int          n_channels;    /* C: station rows of the input */
+    int          n_buses;       /* B */
+    const int*   bus_offsets;   /* [B + 1]: bus b's sources are bus_sources[bus_offsets[b] .. bus_offsets[b + 1]) */
+    const int*   bus_sources;   /* station rows in registration (CreateManagedBuffer) order; a row may appear in many buses */
+    const float* gains;         /* [B] AudioMixer::GetOutputGain, NULL = 1.0f each */
+    int          device;        /* HIP device ordinal, -1 = current */
+} fmd_mixer_config;
+/* AudioMixer::AudioMixer + CreateManagedBuffer per source, for every bus */
+int fmd_mixer_create(const fmd_mixer_config* cfg, fmd_mixer* out);
+int fmd_mixer_destroy(fmd_mixer m);
+/* replace bus `bus`'s sources (registration order); takes effect at the next process call */
+int fmd_mixer_set_sources(fmd_mixer m, int bus, const int* sources, int n_sources);
+/* AudioMixer::GetOutputGain() = gain for bus `bus` (-1 = every bus); takes effect at the next process call */
+int fmd_mixer_set_gain(fmd_mixer m, int bus, float gain);
+int fmd_mixer_get_gain(fmd_mixer m, int bus, float* gain);
+/* AudioMixer::UpdateMixer for every bus on n frames.  d_in [C][in_stride][2] f32 on the device; d_active: [C] uint8 on the device,
+ * non-zero = the station delivered a block this call (the reference's non-empty ring buffer), NULL = all; d_out [B][out_stride][2] on
+ * the device.  n < 0, n > in_stride or out_stride < n return FMD_ERR_ARG and write nothing; n == 0 and empty buses are valid.
+ * Asynchronous on `stream`; consecutive calls may use different streams (the library orders them). */
+int fmd_mixer_process_f32_dev(fmd_mixer m, const float* d_in, long long in_stride, long long n, const uint8_t* d_active,
+                              float* d_out, long long out_stride, void* stream);
+/* the same, delivered to HOST memory out [B][out_stride][2] after `stream` has finished (what a PortAudio-style callback consumes) */
+int fmd_mixer_process_f32_host(fmd_mixer m, const float* d_in, long long in_stride, long long n, const uint8_t* d_active,
+                               float* out, long long out_stride, void* stream);
+const char* fmd_mixer_last_error(fmd_mixer m);
+
 #ifdef __cplusplus
 }
 #endif
