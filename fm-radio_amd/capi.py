@@ -77,6 +77,19 @@ class ChanConfig(C.Structure):
                 ("taps_per_phase", C.c_int), ("max_input_samples", C.c_longlong), ("device", C.c_int)]
 
 
+class ScanConfig(C.Structure):
+    _fields_ = [("fs_in", C.c_double), ("nfft", C.c_int), ("max_input_samples", C.c_longlong), ("device", C.c_int)]
+
+
+class ScanParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("raster_hz", "raster_origin_hz", "channel_bw_hz", "min_snr_db", "usable_fraction", "noise_quantile",
+                                          "min_spacing_hz")]
+
+
+# include/fmdemod.h fmd_scan_station
+SCAN_STATION_DTYPE = np.dtype([("offset_hz", "<f8"), ("power_db", "<f8"), ("snr_db", "<f8")])
+
+
 class ResamplerConfig(C.Structure):
     _fields_ = [("n_channels", C.c_int), ("fs_in", C.c_int), ("fs_out", C.c_int), ("method", C.c_int), ("taps_per_phase", C.c_int),
                 ("max_input_frames", C.c_longlong), ("device", C.c_int)]
@@ -194,6 +207,20 @@ def load_library():
         getattr(L, f"fmd_chan_process_{fmt}_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
     L.fmd_chan_last_error.restype = C.c_char_p
     L.fmd_chan_last_error.argtypes = [C.c_void_p]
+    L.fmd_scan_default_nfft.restype = C.c_int
+    L.fmd_scan_default_nfft.argtypes = [C.c_double]
+    L.fmd_scan_default_params.restype = None
+    L.fmd_scan_default_params.argtypes = [C.POINTER(ScanParams)]
+    L.fmd_scan_detect.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(ScanParams), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.fmd_scan_create.argtypes = [C.POINTER(ScanConfig), C.POINTER(C.c_void_p)]
+    L.fmd_scan_destroy.argtypes = [C.c_void_p]
+    L.fmd_scan_reset.argtypes = [C.c_void_p]
+    for fmt in ("cf32", "u8", "s8", "s16"):
+        getattr(L, f"fmd_scan_process_{fmt}_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.fmd_scan_get_psd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]
+    L.fmd_scan_stations.argtypes = [C.c_void_p, C.POINTER(ScanParams), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
+    L.fmd_scan_last_error.restype = C.c_char_p
+    L.fmd_scan_last_error.argtypes = [C.c_void_p]
     L.fmd_resampler_design.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.fmd_resampler_create.argtypes = [C.POINTER(ResamplerConfig), C.POINTER(C.c_void_p)]
     L.fmd_resampler_destroy.argtypes = [C.c_void_p]
@@ -729,6 +756,122 @@ class Channelizer:
     def close(self):
         if self.h:
             self.L.fmd_chan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def scan_default_nfft(fs_in: float) -> int:
+    """The FFT size BandScanner(fs_in, nfft=0) uses (fmd_scan_default_nfft): the smallest power of two with fs_in / N <= 5 kHz, clamped
+    to 256 ... 16384.  Needs no GPU."""
+    n = load_library().fmd_scan_default_nfft(float(fs_in))
+    if n <= 0:
+        raise FmdError(n, f"fs_in {fs_in} must be > 0")
+    return n
+
+
+def scan_default_params() -> dict:
+    """The detection parameters fmd_scan_default_params gives, as a dict (the keyword arguments of scan_detect / BandScanner.stations)."""
+    p = ScanParams()
+    load_library().fmd_scan_default_params(C.byref(p))
+    return {name: getattr(p, name) for name, _ in ScanParams._fields_}
+
+
+def _scan_params(params: dict) -> ScanParams:
+    p = ScanParams()
+    load_library().fmd_scan_default_params(C.byref(p))
+    for k, v in params.items():
+        if k not in scan_default_params():
+            raise TypeError(f"unknown detection parameter {k!r}")
+        setattr(p, k, float(v))
+    return p
+
+
+def _stations(call, msg) -> np.ndarray:
+    """run a detection call (out, cap, n_found) -> rc twice if needed: the count first, then every station"""
+    n = C.c_int(0)
+    out = np.zeros(64, SCAN_STATION_DTYPE)
+    rc = call(out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
+    if rc == FMD_OK and n.value > out.size:
+        out = np.zeros(n.value, SCAN_STATION_DTYPE)
+        rc = call(out.ctypes.data_as(C.c_void_p), out.size, C.byref(n))
+    if rc != FMD_OK:
+        raise FmdError(rc, msg())
+    return out[:n.value].copy()
+
+
+def scan_detect(psd, fs_in: float, **params) -> np.ndarray:
+    """Host-only detection (fmd_scan_detect) on an fft-shifted PSD [nfft] (BandScanner.psd()'s layout): a structured array of stations
+    (offset_hz, power_db, snr_db) ascending by offset.  params override fmd_scan_default_params (scan_default_params()).  Needs no GPU."""
+    lib = load_library()
+    a = np.ascontiguousarray(psd, np.float64)
+    if a.ndim != 1:
+        raise ValueError("psd must be one-dimensional")
+    p = _scan_params(params)
+    return _stations(lambda out, cap, n: lib.fmd_scan_detect(a.ctypes.data_as(C.c_void_p), int(a.size), float(fs_in), C.byref(p), out, cap, n),
+                     lambda: lib.fmd_scan_last_error(None).decode())
+
+
+class BandScanner:
+    """Finds the stations of a wideband capture (fmd_scan_*): an averaged periodogram on the GPU (Hann window, N = nfft, hop N / 2, fp64
+    sums in frame order: bit-identical however the capture is split into calls), then detection on an FM raster on the host.
+    stations()["offset_hz"] goes straight to Channelizer(fs_in, ...)."""
+
+    def __init__(self, fs_in: float, nfft: int = 0, max_input_samples: int = 2_097_152, device: int = -1):
+        self.L = load_library()
+        self.fs_in = float(fs_in)
+        cfg = ScanConfig(self.fs_in, int(nfft), int(max_input_samples), int(device))
+        self.h = C.c_void_p()
+        rc = self.L.fmd_scan_create(C.byref(cfg), C.byref(self.h))
+        if rc != FMD_OK:
+            raise FmdError(rc, self.L.fmd_scan_last_error(None).decode())
+        self.nfft = int(nfft) if nfft else scan_default_nfft(fs_in)
+
+    def _check(self, rc: int):
+        if rc != FMD_OK:
+            raise FmdError(rc, self.L.fmd_scan_last_error(self.h).decode())
+
+    def process(self, wide, stream=None) -> None:
+        """wide: contiguous CUDA tensor [n_in, 2] of interleaved I, Q: float32, or a receiver's uint8 (v - 127), int8 or int16, read in place
+        and asynchronously on the stream (the tensor belongs to the call until its work there has completed)."""
+        import torch
+        fns = {torch.float32: self.L.fmd_scan_process_cf32_dev, torch.uint8: self.L.fmd_scan_process_u8_dev,
+               torch.int8: self.L.fmd_scan_process_s8_dev, torch.int16: self.L.fmd_scan_process_s16_dev}
+        if not (wide.is_cuda and wide.is_contiguous() and wide.dtype in fns and wide.dim() == 2 and wide.shape[1] == 2):
+            raise ValueError("wide must be a contiguous CUDA tensor [n_in, 2] of float32, uint8, int8 or int16")
+        if stream is None:
+            stream = torch.cuda.current_stream(wide.device).cuda_stream
+        self._check(fns[wide.dtype](self.h, wide.data_ptr(), int(wide.shape[0]), C.c_void_p(stream)))
+
+    def psd(self) -> tuple[np.ndarray, np.ndarray]:
+        """(freqs_hz, psd) float64 [nfft], low to high frequency: bin i at (i - nfft / 2) fs_in / nfft.  Synchronises with the scanner."""
+        a = np.empty(self.nfft, np.float64)
+        self._check(self.L.fmd_scan_get_psd(self.h, a.ctypes.data_as(C.c_void_p), a.size, None))
+        return (np.arange(self.nfft, dtype=np.float64) - self.nfft // 2) * (self.fs_in / self.nfft), a
+
+    @property
+    def n_frames(self) -> int:
+        a = np.empty(self.nfft, np.float64)
+        n = C.c_longlong(0)
+        self._check(self.L.fmd_scan_get_psd(self.h, a.ctypes.data_as(C.c_void_p), a.size, C.byref(n)))
+        return n.value
+
+    def stations(self, **params) -> np.ndarray:
+        """Detection on the PSD so far: structured array (offset_hz, power_db, snr_db) ascending by offset; params as scan_detect."""
+        p = _scan_params(params)
+        return _stations(lambda out, cap, n: self.L.fmd_scan_stations(self.h, C.byref(p), out, cap, n),
+                         lambda: self.L.fmd_scan_last_error(self.h).decode())
+
+    def reset(self):
+        self._check(self.L.fmd_scan_reset(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.fmd_scan_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

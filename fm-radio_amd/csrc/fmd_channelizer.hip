@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "fmdemod.h"
+#include "fmd_iq.h"
 
 namespace {
 
@@ -58,30 +59,7 @@ struct ChanDims {
     int tile;                   // outputs per workgroup of k_channelize: kTile, fewer where its window would not fit (whole-band rates)
 };
 
-// One I / Q pair of the caller's block: `raw`, what one load fetches (all of the pair), and cf32(), its exact conversion.  A conversion
-// is a separate rounding-free step: every integer of these types is a float, and v - 127 of a u8 is exact (-ffp-contract=off keeps it
-// out of the mixer's fmaf).  zero() is the raw pair that converts to (+0, +0): what a window sample outside the data reads as.
-template <typename S> struct Iq;
-template <> struct Iq<float2> {
-    using raw = float2;
-    static __device__ __forceinline__ raw zero() { return make_float2(0.f, 0.f); }
-    static __device__ __forceinline__ const float2& cf32(const raw& v) { return v; }   // (no copy: the cf32 kernels' code stays as it was)
-};
-template <> struct Iq<uint8_t> {          // RTL-SDR: the reference's (float)u8 - 127 (src/app.cpp), as fmd_process_u8_* takes it
-    using raw = unsigned short;
-    static __device__ __forceinline__ raw zero() { return 0x7f7f; }
-    static __device__ __forceinline__ float2 cf32(raw v) { return make_float2((float)(v & 0xffu) - 127.0f, (float)(v >> 8) - 127.0f); }
-};
-template <> struct Iq<int8_t> {           // HackRF
-    using raw = unsigned short;
-    static __device__ __forceinline__ raw zero() { return 0; }
-    static __device__ __forceinline__ float2 cf32(raw v) { return make_float2((float)(signed char)(v & 0xffu), (float)(signed char)(v >> 8)); }
-};
-template <> struct Iq<int16_t> {          // Airspy, SDRplay, USRP sc16
-    using raw = unsigned int;
-    static __device__ __forceinline__ raw zero() { return 0; }
-    static __device__ __forceinline__ float2 cf32(raw v) { return make_float2((float)(short)(v & 0xffffu), (float)(short)(v >> 16)); }
-};
+using fmd::Iq;   // one I / Q pair of the caller's block and its exact conversion (fmd_iq.h)
 
 // The window of a call is [T - 1 history samples][the caller's block]: two buffers, read in place (round 5: staging the block behind the
 // history and copying the new history out were two device copies around every launch — 5 us each plus the queue's gaps, a quarter of a

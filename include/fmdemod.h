@@ -407,6 +407,81 @@ int fmd_chan_process_s16_dev(fmd_channelizer h, const int16_t* d_wide, size_t n_
 const char* fmd_chan_last_error(fmd_channelizer h);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Band scan (NOT part of the reference, whose RTL-SDR hardware tunes one known station): finds the occupied channels of a
+ * wideband capture, whose offsets configure fmd_chan_create (fmd_chan_config.center_hz) directly.  Two steps:
+ *  1. an averaged periodogram on the GPU.  N = nfft (power of two, 256 ... 16384), hop H = N / 2; frame f covers the absolute input
+ *     samples [f H, f H + N) counted since create / reset (no zero padding at the start) and counts once its last sample has arrived.
+ *     w[n] = 0.5 - 0.5 cos(2 pi n / N) (periodic Hann, computed in double, stored as fp32); P_f[k] = |sum_n w[n] x[f H + n] e^{-j 2 pi k n / N}|^2
+ *     (fp32 FFT); S[k] = sum_f P_f[k] accumulated in fp64 in frame order, so S does not depend, bit for bit, on how the capture is split
+ *     into calls.  Reported: PSD[i] = S[k] / (F fs_in sum w^2), i = (k + N / 2) mod N: bin i is at (i - N / 2) fs_in / N Hz, low to
+ *     high (F frames; sum w^2 over the fp32 window values, in double; before the first frame the PSD is all zero).
+ *     A non-finite sample makes the frames that hold it non-finite, and the PSD stays non-finite until fmd_scan_reset.
+ *  2. detection on the host, a pure function of the PSD in double (fmd_scan_detect): channel power over a raster, SNR against a noise
+ *     quantile of the usable band, one detection per station (rules: fmd_scan_params below).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_scanner_s* fmd_scanner;
+typedef struct {
+    double    fs_in;             /* capture rate, Hz (> 0) */
+    int       nfft;              /* N, a power of two in 256 ... 16384; 0 = fmd_scan_default_nfft(fs_in) */
+    long long max_input_samples; /* largest n_in of a process call */
+    int       device;            /* HIP device ordinal, -1 = current */
+} fmd_scan_config;
+/* Detection rules, with D = fs_in / N the bin width and f_i = (i - N / 2) D:
+ *   usable bins     |f_i| <= usable_fraction fs_in / 2; noise floor v = the value at 0-based rank floor(noise_quantile (m - 1)) of the
+ *                   m usable bins sorted ascending
+ *   raster points   f_c = raster_origin_hz + j raster_hz for every integer j with |f_c| + channel_bw_hz / 2 <= usable_fraction fs_in / 2
+ *                   (at most 1000000 raster points: a finer raster is refused)
+ *   channel         bins max(0, ceil((f_c - bw / 2) / D) + N / 2) ... min(N - 1, floor((f_c + bw / 2) / D) + N / 2), n_c of them (the
+ *                   clip matters only where usable_fraction = 1 lets a channel end exactly at +fs_in / 2, which is no bin of its own);
+ *                   P_c = D sum PSD over them;
+ *                   snr_db = 10 log10(P_c / (v D n_c)) (+inf where v = 0); a channel with P_c = 0 is never reported
+ *   candidates      snr_db >= min_snr_db, taken by descending P_c (ties: lower offset first); one is accepted unless an accepted
+ *                   station lies closer than min_spacing_hz (the +-raster neighbours of a strong station are not reported)
+ *   output          { offset_hz = f_c, power_db = 10 log10 P_c, snr_db }, ascending by offset */
+typedef struct {
+    double raster_hz;         /* 100e3 (200e3 in the Americas; 50e3 allowed): > 0 */
+    double raster_origin_hz;  /* 0: the offset of one raster point from the capture's centre */
+    double channel_bw_hz;     /* 100e3: > 0 */
+    double min_snr_db;        /* 10 */
+    double usable_fraction;   /* 0.8: in (0, 1] */
+    double noise_quantile;    /* 0.1: in [0, 1] */
+    double min_spacing_hz;    /* 150e3: >= 0 */
+} fmd_scan_params;
+typedef struct {
+    double offset_hz;         /* from the capture's centre: pass straight to fmd_chan_config.center_hz */
+    double power_db;          /* 10 log10 P_c, P_c in the capture's units squared */
+    double snr_db;
+} fmd_scan_station;
+
+/* host-only (no GPU needed): the smallest power of two N with fs_in / N <= 5 kHz, clamped to [256, 16384]; FMD_ERR_ARG for fs_in <= 0 */
+int fmd_scan_default_nfft(double fs_in);
+void fmd_scan_default_params(fmd_scan_params* p);
+/* host-only (no GPU needed): the detection rules on psd [nfft] (fmd_scan_get_psd's layout).  Writes min(cap, n) stations to out and
+ * always sets *n_found = n.  FMD_ERR_ARG with a message (fmd_scan_last_error(NULL)) for a non-finite or negative PSD and invalid
+ * parameters. */
+int fmd_scan_detect(const double* psd, int nfft, double fs_in, const fmd_scan_params* p,
+                    fmd_scan_station* out, int cap, int* n_found);
+int fmd_scan_create(const fmd_scan_config* cfg, fmd_scanner* out);
+int fmd_scan_destroy(fmd_scanner h);
+/* back to the freshly created scanner: no history, no frames (waits for the scanner's earlier work) */
+int fmd_scan_reset(fmd_scanner h);
+/* d_wide: [n_in][2] on the device, read IN PLACE, 0 < n_in <= max_input_samples.  The integer forms convert each pair exactly as
+ * fmd_chan_process_u8_dev / _s8_dev / _s16_dev do (u8: v - 127; s8, s16: v) and give the bits the cf32 call gives on the converted
+ * samples; formats may change from call to call.  The scanner keeps up to N - 1 converted samples between calls.  Asynchronous on
+ * `stream`; consecutive calls may use different streams (the library orders them); d_wide belongs to the call until its work on
+ * `stream` has completed.  A channeliser may read the same block on another stream. */
+int fmd_scan_process_cf32_dev(fmd_scanner h, const float* d_wide, size_t n_in, void* stream);
+int fmd_scan_process_u8_dev(fmd_scanner h, const uint8_t* d_wide, size_t n_in, void* stream);
+int fmd_scan_process_s8_dev(fmd_scanner h, const int8_t* d_wide, size_t n_in, void* stream);
+int fmd_scan_process_s16_dev(fmd_scanner h, const int16_t* d_wide, size_t n_in, void* stream);
+/* the averaged PSD of every frame so far into psd [cap >= nfft] (layout above) and the frame count F; synchronises with the
+ * scanner's work */
+int fmd_scan_get_psd(fmd_scanner h, double* psd, int cap, long long* n_frames);
+/* fmd_scan_get_psd, then fmd_scan_detect with p (NULL = fmd_scan_default_params) */
+int fmd_scan_stations(fmd_scanner h, const fmd_scan_params* p, fmd_scan_station* out, int cap, int* n_found);
+const char* fmd_scan_last_error(fmd_scanner h);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Batched audio resampler: the stage between OnAudioOut and the listener (reference Resampled_PCM_Player,
  * src/audio/resampled_pcm_player.cpp:15-54, fed every OnAudioOut block at src/fm_demod_tuner.cpp:145-165).  C stations'
  * stereo f32 frames at fs_in (fmd_rates.fs_audio) in, [C][n_out][2] at fs_out out, on the GPU.  Standalone: it reads the
