@@ -13,6 +13,7 @@ from .capi import (  # noqa: F401
     FMD_AUDIO_LMR, FMD_AUDIO_LPR, FMD_AUDIO_STEREO, FMD_FLAG_KEEP_TAPS, FMD_FLAG_NO_PIPELINE, BatchDemod, Coeffs, Config, Controls, FmdError,
     AudioResampler, FMD_RESAMPLE_POLYPHASE, FMD_RESAMPLE_REFERENCE, resampler_design, AudioMixer,
     BandScanner, SCAN_STATION_DTYPE, scan_default_nfft, scan_default_params, scan_detect,
+    IqCorrector, IqCorrection, IqMoments, IqcorrConfig, iqcorr_solve,
     Channelizer, Rates, build_library, chan_default_taps, chan_design, declared_symbols, default_config, default_controls, lib_path, load_library, selftest_atan2, selftest_atan2_small, selftest_fast_math,
 )
 from .sharding import AudioGather, channel_range, padded_shard  # noqa: F401,E402

@@ -11,6 +11,7 @@ import ctypes as C
 import re
 import subprocess
 from pathlib import Path
+from typing import NamedTuple
 
 import numpy as np
 
@@ -96,6 +97,36 @@ class ResamplerConfig(C.Structure):
 
 
 FMD_RESAMPLE_REFERENCE, FMD_RESAMPLE_POLYPHASE = 0, 1
+
+
+class IqcorrConfig(C.Structure):
+    _fields_ = [("max_input_samples", C.c_longlong), ("device", C.c_int)]
+
+
+class _IqMomentsC(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("n", "sum_i", "sum_q", "sum_ii", "sum_qq", "sum_iq")]
+
+
+class _IqCorrectionC(C.Structure):
+    _fields_ = [(n, C.c_float) for n in ("dc_i", "dc_q", "w_re", "w_im")]
+
+
+class IqMoments(NamedTuple):
+    """include/fmdemod.h fmd_iq_moments: the count and the five fp64 sums over the raw converted samples"""
+    n: float
+    sum_i: float
+    sum_q: float
+    sum_ii: float
+    sum_qq: float
+    sum_iq: float
+
+
+class IqCorrection(NamedTuple):
+    """include/fmdemod.h fmd_iq_correction (fp32 values): y = z + (w_re + j w_im) conj(z), z = x - (dc_i + j dc_q)"""
+    dc_i: float = 0.0
+    dc_q: float = 0.0
+    w_re: float = 0.0
+    w_im: float = 0.0
 
 
 class MixerConfig(C.Structure):
@@ -221,6 +252,18 @@ def load_library():
     L.fmd_scan_stations.argtypes = [C.c_void_p, C.POINTER(ScanParams), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.fmd_scan_last_error.restype = C.c_char_p
     L.fmd_scan_last_error.argtypes = [C.c_void_p]
+    L.fmd_iqcorr_create.argtypes = [C.POINTER(IqcorrConfig), C.POINTER(C.c_void_p)]
+    for name in ("fmd_iqcorr_destroy", "fmd_iqcorr_reset", "fmd_iqcorr_reset_moments"):
+        getattr(L, name).argtypes = [C.c_void_p]
+    for fmt in ("cf32", "u8", "s8", "s16"):
+        getattr(L, f"fmd_iqcorr_process_{fmt}_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_iqcorr_get_moments.argtypes = [C.c_void_p, C.POINTER(_IqMomentsC)]
+    L.fmd_iqcorr_solve.argtypes = [C.POINTER(_IqMomentsC), C.POINTER(_IqCorrectionC)]
+    L.fmd_iqcorr_set_correction.argtypes = [C.c_void_p, C.POINTER(_IqCorrectionC)]
+    L.fmd_iqcorr_get_correction.argtypes = [C.c_void_p, C.POINTER(_IqCorrectionC)]
+    L.fmd_iqcorr_calibrate.argtypes = [C.c_void_p, C.POINTER(_IqCorrectionC)]
+    L.fmd_iqcorr_last_error.restype = C.c_char_p
+    L.fmd_iqcorr_last_error.argtypes = [C.c_void_p]
     L.fmd_resampler_design.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.fmd_resampler_create.argtypes = [C.POINTER(ResamplerConfig), C.POINTER(C.c_void_p)]
     L.fmd_resampler_destroy.argtypes = [C.c_void_p]
@@ -872,6 +915,107 @@ class BandScanner:
     def close(self):
         if self.h:
             self.L.fmd_scan_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def iqcorr_solve(moments) -> IqCorrection:
+    """Host-only solve step (fmd_iqcorr_solve): the six moments (IqMoments, or n, sum i, sum q, sum i^2, sum q^2, sum i q in that order)
+    -> the correction that removes the DC term and the image, exactly the root of E[(z + w conj(z))^2] = 0.  Needs no GPU."""
+    lib = load_library()
+    m = _IqMomentsC(*(float(v) for v in moments))
+    c = _IqCorrectionC()
+    rc = lib.fmd_iqcorr_solve(C.byref(m), C.byref(c))
+    if rc != FMD_OK:
+        raise FmdError(rc, lib.fmd_iqcorr_last_error(None).decode())
+    return IqCorrection(c.dc_i, c.dc_q, c.w_re, c.w_im)
+
+
+class IqCorrector:
+    """Removes a receiver's DC offset and IQ imbalance from a wideband capture on the GPU (fmd_iqcorr_*), ahead of BandScanner and
+    Channelizer.  process() adds every raw sample to fp64 moments (a fixed summation order: bit-identical however the capture is split into
+    calls) and returns the samples as float32, corrected with the correction in force: identity until calibrate() or `correction` sets one."""
+
+    solve = staticmethod(iqcorr_solve)
+
+    def __init__(self, max_input_samples: int = 2_097_152, device: int = -1):
+        self.L = load_library()
+        cfg = IqcorrConfig(int(max_input_samples), int(device))
+        self.h = C.c_void_p()
+        rc = self.L.fmd_iqcorr_create(C.byref(cfg), C.byref(self.h))
+        if rc != FMD_OK:
+            self.h = C.c_void_p()
+            raise FmdError(rc, self.L.fmd_iqcorr_last_error(None).decode())
+        self.max_input_samples = int(max_input_samples)
+
+    def _check(self, rc: int):
+        if rc != FMD_OK:
+            raise FmdError(rc, self.L.fmd_iqcorr_last_error(self.h).decode())
+
+    def process(self, wide, out=None, stream=None):
+        """wide: contiguous CUDA tensor [n_in, 2] of interleaved I, Q: float32, or a receiver's uint8 (v - 127), int8 or int16.  Returns the
+        corrected samples, a CUDA float32 tensor [n_in, 2] (asynchronous on the stream).  out: the tensor to write (`wide` itself is allowed
+        for float32), or False to measure only (returns None)."""
+        import torch
+        fns = {torch.float32: self.L.fmd_iqcorr_process_cf32_dev, torch.uint8: self.L.fmd_iqcorr_process_u8_dev,
+               torch.int8: self.L.fmd_iqcorr_process_s8_dev, torch.int16: self.L.fmd_iqcorr_process_s16_dev}
+        if not (wide.is_cuda and wide.is_contiguous() and wide.dtype in fns and wide.dim() == 2 and wide.shape[1] == 2):
+            raise ValueError("wide must be a contiguous CUDA tensor [n_in, 2] of float32, uint8, int8 or int16")
+        n_in = int(wide.shape[0])
+        if out is None:
+            out = torch.empty((n_in, 2), dtype=torch.float32, device=wide.device)
+        if out is not False and not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (n_in, 2)):
+            raise ValueError("out must be a contiguous CUDA float32 tensor [n_in, 2]")
+        if stream is None:
+            stream = torch.cuda.current_stream(wide.device).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        self._check(fns[wide.dtype](self.h, C.c_void_p(wide.data_ptr()), n_in, None if out is False else C.c_void_p(out.data_ptr()),
+                                    C.c_void_p(stream)))
+        return None if out is False else out
+
+    def measure(self, wide, stream=None) -> None:
+        """process(wide, out=False): adds the samples to the moments and writes nothing"""
+        self.process(wide, out=False, stream=stream)
+
+    def moments(self) -> IqMoments:
+        """the moments of every sample since create / reset; synchronises with the corrector's work"""
+        m = _IqMomentsC()
+        self._check(self.L.fmd_iqcorr_get_moments(self.h, C.byref(m)))
+        return IqMoments(m.n, m.sum_i, m.sum_q, m.sum_ii, m.sum_qq, m.sum_iq)
+
+    def calibrate(self) -> IqCorrection:
+        """moments() -> solve() -> correction: applies from the next process call; the moments are kept"""
+        c = _IqCorrectionC()
+        self._check(self.L.fmd_iqcorr_calibrate(self.h, C.byref(c)))
+        return IqCorrection(c.dc_i, c.dc_q, c.w_re, c.w_im)
+
+    @property
+    def correction(self) -> IqCorrection:
+        c = _IqCorrectionC()
+        self._check(self.L.fmd_iqcorr_get_correction(self.h, C.byref(c)))
+        return IqCorrection(c.dc_i, c.dc_q, c.w_re, c.w_im)
+
+    @correction.setter
+    def correction(self, value):
+        c = _IqCorrectionC(*(float(v) for v in value))
+        self._check(self.L.fmd_iqcorr_set_correction(self.h, C.byref(c)))
+
+    def reset(self):
+        """moments to zero and the correction to identity"""
+        self._check(self.L.fmd_iqcorr_reset(self.h))
+
+    def reset_moments(self):
+        self._check(self.L.fmd_iqcorr_reset_moments(self.h))
+
+    def close(self):
+        if self.h:
+            self.L.fmd_iqcorr_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

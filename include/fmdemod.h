@@ -584,6 +584,73 @@ int fmd_mixer_process_f32_host(fmd_mixer m, const float* d_in, long long in_stri
                                float* out, long long out_stride, void* stream);
 const char* fmd_mixer_last_error(fmd_mixer m);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * DC offset and IQ imbalance correction of a wideband capture (NOT part of the reference, whose RTL-SDR hardware is low-IF and tunes
+ * one station): one pass over the capture, ahead of the band scanner and the channeliser.  A zero-IF front end leaves a DC term (the
+ * scanner sees a carrier at offset 0; u8 read as v - 127 has one of 0.5) and a gain / phase imbalance between I and Q, which mirrors
+ * every station to the negated offset 25 - 40 dB down.  The corrector measures both from second-order moments and removes them with
+ * y = z + w conj(z), z = x - dc.  Arithmetic, restated in C by tests/cpp/iqcorr_ref.c:
+ *   conversion  as fmd_chan_process_*_dev: cf32 as is; u8 v - 127; s8, s16 (float)v.  All exact.
+ *   moments     n, sum i, sum q, sum i^2, sum q^2, sum i q over the raw (uncorrected) converted samples since create / reset, in fp64.
+ *               Every term is formed in double from the converted floats (a product of two floats is exact in double: only the
+ *               additions round), and added in a fixed order that does not depend on how the capture is split into calls, on streams
+ *               or on the formats:
+ *                 - samples are counted absolutely since reset, in chunks of 4096;
+ *                 - within a chunk, 256 partial sums p_j = sum_k term[j + 256 k], k ascending, starting from +0;
+ *                 - the partials are combined by the halving tree: p_j += p_{j + 128} for j < 128, then 64, ... 1; the chunk's sum is p_0;
+ *                 - chunk sums are added to the running total in chunk order;
+ *                 - an unfinished chunk carries its 256 partials per moment to the next call; fmd_iqcorr_get_moments reports
+ *                   total + tree(open chunk) and leaves the chunk open.
+ *               No floating-point atomics.  For the integer formats every sum is an exact integer while it stays below 2^53: for s16
+ *               that is at least 2^23 samples (|v|^2 <= 2^30), for u8 and s8 at least 2^39.  A non-finite sample makes its moments
+ *               non-finite until fmd_iqcorr_reset / _reset_moments.
+ *   solve       host, double, a pure function of the moments (fmd_iqcorr_solve):
+ *                 m = (sum i, sum q) / n;  vii = sum i^2 / n - m_i^2;  vqq = sum q^2 / n - m_q^2;  viq = sum i q / n - m_i m_q
+ *                 p = vii + vqq;  c = (vii - vqq) + 2j viq;  s = sqrt(max(0, p^2 - |c|^2));  w = -c / (p + s), w = 0 where p + s <= 0
+ *                 (p = 0: a constant capture)
+ *               { dc_i, dc_q, w_re, w_im } = (m_i, m_q, Re w, Im w) rounded to fp32.  This w is the exact root of
+ *               E[(z + w conj(z))^2] = 0 (the circularity condition), not the first-order -c / 2p.
+ *   apply       fp32, every FMA an explicit fmaf:
+ *                 zi = i - dc_i;  zq = q - dc_q
+ *                 yi = fmaf(w_re, zi, fmaf(w_im, zq, zi));  yq = fmaf(w_im, zi, fmaf(-w_re, zq, zq))
+ *               No gain normalisation.  The identity correction (all zero: the state after create and reset) reproduces the conversion
+ *               in value.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_iqcorr_s* fmd_iqcorr;
+typedef struct {
+    long long max_input_samples; /* largest n_in of a process call, in (0, 2^32] */
+    int       device;            /* HIP device ordinal, -1 = current */
+} fmd_iqcorr_config;
+typedef struct { double n, sum_i, sum_q, sum_ii, sum_qq, sum_iq; } fmd_iq_moments;
+typedef struct { float dc_i, dc_q, w_re, w_im; } fmd_iq_correction;
+
+int fmd_iqcorr_create(const fmd_iqcorr_config* cfg, fmd_iqcorr* out);
+int fmd_iqcorr_destroy(fmd_iqcorr h);
+/* moments to zero and the correction to identity (waits for the corrector's earlier work) */
+int fmd_iqcorr_reset(fmd_iqcorr h);
+/* moments to zero; the correction stays */
+int fmd_iqcorr_reset_moments(fmd_iqcorr h);
+/* d_in: [n_in][2] on the device, starting at any sample (aligned to one I / Q pair of its format), 0 < n_in <= max_input_samples.  One
+ * fused kernel reads each raw sample once, adds it to the moments and writes d_out [n_in][2] cf32 (8-byte aligned) corrected with the
+ * correction in force when the call was made.  d_out == NULL measures only; d_out == d_in is allowed for cf32 (each thread writes only
+ * what it read).  Formats may change from call to call.  An n_in outside its range or a misaligned pointer returns FMD_ERR_ARG, and
+ * nothing is written or counted.  Asynchronous on `stream`; consecutive calls may use different streams (the library orders them). */
+int fmd_iqcorr_process_cf32_dev(fmd_iqcorr h, const float* d_in, long long n_in, float* d_out, void* stream);
+int fmd_iqcorr_process_u8_dev(fmd_iqcorr h, const uint8_t* d_in, long long n_in, float* d_out, void* stream);
+int fmd_iqcorr_process_s8_dev(fmd_iqcorr h, const int8_t* d_in, long long n_in, float* d_out, void* stream);
+int fmd_iqcorr_process_s16_dev(fmd_iqcorr h, const int16_t* d_in, long long n_in, float* d_out, void* stream);
+/* the moments of every sample so far (an open chunk included, and left open); synchronises with the corrector's work */
+int fmd_iqcorr_get_moments(fmd_iqcorr h, fmd_iq_moments* out);
+/* host-only (no GPU needed): the solve step.  FMD_ERR_ARG (message: fmd_iqcorr_last_error(NULL)) for n <= 0, a non-finite moment or a
+ * result that is not finite in fp32 */
+int fmd_iqcorr_solve(const fmd_iq_moments* m, fmd_iq_correction* out);
+/* takes effect at the next process call; non-finite values are refused (FMD_ERR_ARG) */
+int fmd_iqcorr_set_correction(fmd_iqcorr h, const fmd_iq_correction* c);
+int fmd_iqcorr_get_correction(fmd_iqcorr h, fmd_iq_correction* c);
+/* fmd_iqcorr_get_moments, fmd_iqcorr_solve, fmd_iqcorr_set_correction; the moments are kept.  out may be NULL */
+int fmd_iqcorr_calibrate(fmd_iqcorr h, fmd_iq_correction* out);
+const char* fmd_iqcorr_last_error(fmd_iqcorr h);
+
 #ifdef __cplusplus
 }
 #endif
