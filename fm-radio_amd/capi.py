@@ -134,6 +134,22 @@ class MixerConfig(C.Structure):
                 ("gains", C.c_void_p), ("device", C.c_int)]
 
 
+class MeterConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
+
+
+class MeterDesign(C.Structure):
+    """include/fmdemod.h fmd_meter_design_t"""
+    _fields_ = [("pre_b", C.c_double * 3), ("pre_a", C.c_double * 3), ("rlb_b", C.c_double * 3), ("rlb_a", C.c_double * 3),
+                ("frames_per_subblock", C.c_int), ("edge", C.c_double * 1001), ("centre", C.c_double * 1000)]
+
+
+# include/fmdemod.h fmd_meter_status (280 bytes)
+METER_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("subblocks", "<u8"), ("energy_ring", "<f8", (30,)), ("peak_call", "<f4", (2,)),
+                               ("peak_hold", "<f4", (2,)), ("below_gate", "<u4"), ("nonfinite", "<u4")])
+METER_BINS = 1000
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("total_ms", C.c_double), ("launches", C.c_int)]
 
@@ -283,6 +299,22 @@ def load_library():
         getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
     L.fmd_mixer_last_error.restype = C.c_char_p
     L.fmd_mixer_last_error.argtypes = [C.c_void_p]
+    L.fmd_meter_design.argtypes = [C.c_int, C.POINTER(MeterDesign)]
+    L.fmd_meter_lufs.restype = C.c_double
+    L.fmd_meter_lufs.argtypes = [C.c_double]
+    L.fmd_meter_integrated.argtypes = [C.c_void_p, C.POINTER(MeterDesign), C.POINTER(C.c_double)]
+    L.fmd_meter_momentary.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.fmd_meter_short_term.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
+    L.fmd_meter_create.argtypes = [C.POINTER(MeterConfig), C.POINTER(C.c_void_p)]
+    L.fmd_meter_destroy.argtypes = [C.c_void_p]
+    L.fmd_meter_reset.argtypes = [C.c_void_p, C.c_int]
+    L.fmd_meter_reset_peaks.argtypes = [C.c_void_p, C.c_int]
+    L.fmd_meter_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_meter_get_status.argtypes = [C.c_void_p, C.c_void_p]
+    L.fmd_meter_get_histogram.argtypes = [C.c_void_p, C.c_void_p]
+    L.fmd_meter_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.fmd_meter_last_error.restype = C.c_char_p
+    L.fmd_meter_last_error.argtypes = [C.c_void_p]
     L.fmd_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.argtypes = [C.c_void_p]
@@ -1204,3 +1236,137 @@ class AudioMixer:
                                                      None if active is None else C.c_void_p(active.data_ptr()), C.c_void_p(out.data_ptr()),
                                                      out_stride, C.c_void_p(stream)))
         return out[:, :n]
+
+
+def meter_design(fs: int) -> MeterDesign:
+    """fmd_meter_design (host only, no GPU needed): the K-weighting biquads, the sub-block length and the histogram's edges and centres"""
+    L = load_library()
+    d = MeterDesign()
+    rc = L.fmd_meter_design(int(fs), C.byref(d))
+    if rc != FMD_OK:
+        raise FmdError(rc, L.fmd_meter_last_error(None).decode() or L.fmd_status_string(rc).decode())
+    return d
+
+
+def meter_lufs(energy: float) -> float:
+    """fmd_meter_lufs: -0.691 + 10 log10(energy); -inf for 0"""
+    return load_library().fmd_meter_lufs(float(energy))
+
+
+def meter_integrated(hist, design: MeterDesign) -> float:
+    """fmd_meter_integrated (host only): the gated programme loudness, in LUFS, of one station's [1000] histogram; -inf when it is empty"""
+    L = load_library()
+    h = np.ascontiguousarray(hist, np.uint32)
+    if h.shape != (METER_BINS,):
+        raise ValueError("hist must hold 1000 bins")
+    out = C.c_double(0.0)
+    rc = L.fmd_meter_integrated(h.ctypes.data_as(C.c_void_p), C.byref(design), C.byref(out))
+    if rc != FMD_OK:
+        raise FmdError(rc, L.fmd_meter_last_error(None).decode() or L.fmd_status_string(rc).decode())
+    return out.value
+
+
+def _meter_window(fn, record) -> float:
+    L = load_library()
+    r = np.ascontiguousarray(record, METER_STATUS_DTYPE).reshape(-1)
+    if r.size != 1:
+        raise ValueError("one status record at a time")
+    out = C.c_double(0.0)
+    rc = getattr(L, fn)(r.ctypes.data_as(C.c_void_p), C.byref(out))
+    if rc != FMD_OK:
+        raise FmdError(rc, L.fmd_meter_last_error(None).decode() or L.fmd_status_string(rc).decode())
+    return out.value
+
+
+def meter_momentary(record) -> float:
+    """fmd_meter_momentary of one METER_STATUS_DTYPE record: the last 400 ms, in LUFS (FMD_ERR_STATE before 4 sub-blocks)"""
+    return _meter_window("fmd_meter_momentary", record)
+
+
+def meter_short_term(record) -> float:
+    """fmd_meter_short_term of one METER_STATUS_DTYPE record: the last 3 s, in LUFS (FMD_ERR_STATE before 30 sub-blocks)"""
+    return _meter_window("fmd_meter_short_term", record)
+
+
+class LoudnessMeter:
+    """ITU-R BS.1770 loudness and sample peak of C stations' audio on the GPU (fmd_meter_*).  Feed it the same [C, n, 2] float32 CUDA
+    tensors as AudioResampler and AudioMixer (BatchDemod.audio_tensor() at 32 kHz, or a resampler's output at fs); it changes nothing in
+    them.  status() returns METER_STATUS_DTYPE records, histogram() the gating blocks' [C, 1000] counts; momentary / short_term /
+    integrated turn them into LUFS on the host."""
+
+    def __init__(self, n_channels: int, fs: int, max_input_frames: int = 1 << 16, device: int = -1):
+        self.L = load_library()
+        cfg = MeterConfig(int(n_channels), int(fs), int(max_input_frames), device)
+        self.m = C.c_void_p()
+        rc = self.L.fmd_meter_create(C.byref(cfg), C.byref(self.m))
+        if rc != FMD_OK:
+            self.m = None
+            raise FmdError(rc, self.L.fmd_meter_last_error(None).decode() or self.L.fmd_status_string(rc).decode())
+        self.n_channels, self.fs = int(n_channels), int(fs)
+        self.design = meter_design(fs)
+
+    def close(self):
+        if getattr(self, "m", None):
+            self.L.fmd_meter_destroy(self.m)
+            self.m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc < 0:
+            raise FmdError(rc, (self.L.fmd_meter_last_error(self.m) or b"").decode() or self.L.fmd_status_string(rc).decode())
+        return rc
+
+    def process(self, x, n: int | None = None, active=None, stream=None):
+        """meters the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
+        uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole).  Asynchronous on `stream` (default: torch's current)."""
+        import torch
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
+                and x.stride(2) == 1 and x.stride(1) == 2):
+            raise ValueError("x must be a CUDA float32 tensor [C, n, 2] with contiguous frames")
+        n = int(x.shape[1]) if n is None else int(n)
+        if active is not None:
+            if active.dtype == torch.bool:
+                active = active.view(torch.uint8)
+            if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (self.n_channels,) and active.is_contiguous()):
+                raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
+        self._check(self.L.fmd_meter_process_f32_dev(self.m, C.c_void_p(x.data_ptr()), in_stride, n,
+                                                     None if active is None else C.c_void_p(active.data_ptr()), C.c_void_p(stream)))
+
+    def reset(self, channel: int = -1):
+        self._check(self.L.fmd_meter_reset(self.m, int(channel)))
+
+    def reset_peaks(self, channel: int = -1):
+        self._check(self.L.fmd_meter_reset_peaks(self.m, int(channel)))
+
+    def status(self) -> np.ndarray:
+        """[C] METER_STATUS_DTYPE records; waits for the meter's work"""
+        out = np.zeros(self.n_channels, METER_STATUS_DTYPE)
+        self._check(self.L.fmd_meter_get_status(self.m, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def histogram(self) -> np.ndarray:
+        """[C, 1000] uint32 counts of gating blocks per 0.1 LU bin from -70 LUFS; waits for the meter's work"""
+        out = np.zeros((self.n_channels, METER_BINS), np.uint32)
+        self._check(self.L.fmd_meter_get_histogram(self.m, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def status_dev_ptr(self) -> int:
+        """fmd_meter_status_dev: the address of the device's own [C] records, valid until the next process call"""
+        p = C.c_void_p()
+        self._check(self.L.fmd_meter_status_dev(self.m, C.byref(p)))
+        return p.value
+
+    def integrated(self, hist=None) -> np.ndarray:
+        """[C] float64 LUFS: the gated programme loudness since reset (-inf where no gating block passed -70 LUFS)"""
+        hist = self.histogram() if hist is None else hist
+        return np.array([meter_integrated(h, self.design) for h in hist], np.float64)

@@ -651,6 +651,99 @@ int fmd_iqcorr_get_correction(fmd_iqcorr h, fmd_iq_correction* c);
 int fmd_iqcorr_calibrate(fmd_iqcorr h, fmd_iq_correction* out);
 const char* fmd_iqcorr_last_error(fmd_iqcorr h);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Batched loudness meter (NOT part of the reference): ITU-R BS.1770 / EBU R 128 programme loudness and sample peak of every station's
+ * audio, measured where the audio already is.  It reads the same device array [C][in_stride][2] as the resampler and the mixer
+ * (fmd_audio_dev's view, or a resampler's output), changes nothing in the stage that wrote it, and keeps one fmd_meter_status record and
+ * a 1000-bin histogram per station.  It measures the audio, not the RF signal.  No true peak, no loudness range; channel weights are 1.0
+ * for L and R.  Arithmetic, restated in C by tests/cpp/meter_ref.c:
+ *   design      host, double, host libm (fmd_meter_design); pi = 3.14159265358979323846:
+ *                 pre-filter (high shelf): f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196
+ *                   K = tan(pi * f0 / fs);  Vh = pow(10, G / 20);  Vb = pow(Vh, 0.4996667741545416);  a0 = 1 + K / Q + K * K
+ *                   pre_b = { (Vh + Vb * K / Q + K * K) / a0, 2 * (K * K - Vh) / a0, (Vh - Vb * K / Q + K * K) / a0 }
+ *                   pre_a = { 1, 2 * (K * K - 1) / a0, (1 - K / Q + K * K) / a0 }
+ *                 RLB high-pass: f0 = 38.13547087602444, Q = 0.5003270373238773, K and a0 by the same two formulas
+ *                   rlb_b = { 1, -2, 1 };  rlb_a = { 1, 2 * (K * K - 1) / a0, (1 - K / Q + K * K) / a0 }
+ *                 frames_per_subblock Nsb = fs / 10 (100 ms)
+ *                 edge[j]   = pow(10, ((-70 + 0.1 * j) + 0.691) / 10),          j = 0 ... 1000   (-70 LUFS ... +30 LUFS in 0.1 LU steps)
+ *                 centre[j] = pow(10, (((-70 + 0.1 * j) + 0.05) + 0.691) / 10), j = 0 ... 999
+ *               At 48 kHz the formulas give BS.1770's printed coefficients to better than 1e-14.
+ *   filter      per (station, rail), all state in fp64 (denormals kept), direct form II transposed, every multiply-add an explicit fma.
+ *               With v = (double)x, pb = pre_b, pa = pre_a, rb = rlb_b, ra = rlb_a:
+ *                 o1 = fma(pb0, v, s1);   s1 = fma(-pa1, o1, fma(pb1, v, s2));   s2 = fma(-pa2, o1, pb2 * v)
+ *                 o2 = fma(rb0, o1, t1);  t1 = fma(-ra1, o2, fma(rb1, o1, t2));  t2 = fma(-ra2, o2, rb2 * o1)
+ *                 acc = fma(o2, o2, acc)              frame order, from +0 at each sub-block start
+ *                 peak = fmaxf(peak, fabsf(x))        fp32, on the raw sample (a NaN sample leaves peak as it is)
+ *               peak_call starts at 0 in every process call that meters the station; peak_hold only at create, reset and reset_peaks.
+ *   sub-blocks  frames are counted per station, absolutely since the station's reset; sub-block g is frames [g Nsb, (g + 1) Nsb).  An
+ *               unfinished sub-block carries acc of both rails and the filter states to the next call, so no result depends, bit for bit,
+ *               on how the frames are split into calls, on streams, on the batch or on the station's row.  When sub-block g completes:
+ *                 E_g = (accL + accR) / (double)Nsb, stored at energy_ring[g % 30]
+ *                 if g >= 3: B = (((E_{g-3} + E_{g-2}) + E_{g-1}) + E_g) * 0.25   (a 400 ms gating block, 75 % overlap)
+ *                   B not finite -> nonfinite++;  else B < edge[0] -> below_gate++;  else hist[j]++ for the j with
+ *                   edge[j] <= B < edge[j + 1] (B >= edge[1000] -> j = 999)
+ *               Only comparisons run on the device: no logarithm there.  No floating-point atomics.
+ *   read-out    host, double, pure functions:
+ *                 fmd_meter_lufs(e)  = -0.691 + 10 * log10(e);  e == 0 -> -inf
+ *                 momentary          = lufs((((E_{G-4} + E_{G-3}) + E_{G-2}) + E_{G-1}) / 4), G = subblocks
+ *                 short-term         = lufs(s / 30), s = +0, s += E_g for g = G - 30 ... G - 1
+ *                 integrated         : n = sum of hist; n == 0 -> -inf.  Gamma = (sum over j ascending, from +0, of (double)hist[j] * centre[j])
+ *                                      / (double)n.  Keep the bins with centre[j] >= 0.1 * Gamma (the -10 LU relative gate); with the same
+ *                                      two sums over the kept bins, I = lufs(sum hist[j] centre[j] / (double)(sum hist[j])).
+ *               The histogram quantises a gating block's loudness to its bin's centre, at most 0.05 LU away: inside the +-0.1 LU of EBU
+ *               Tech 3341, and what makes the memory per station fixed.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_meter_s* fmd_meter;
+typedef struct {
+    int       n_channels;         /* C: station rows of the input */
+    int       fs;                 /* the audio's rate: a multiple of 10 in 8000 ... 192000 */
+    long long max_input_frames;   /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_meter_config;
+typedef struct {
+    double pre_b[3], pre_a[3], rlb_b[3], rlb_a[3];   /* a[0] == 1 */
+    int    frames_per_subblock;                      /* fs / 10 */
+    double edge[1001], centre[1000];
+} fmd_meter_design_t;
+/* one per station, 280 bytes: frames at byte 0, subblocks 8, energy_ring 16, peak_call 256, peak_hold 264, below_gate 272, nonfinite 276 */
+typedef struct {
+    unsigned long long frames;        /* frames metered since reset */
+    unsigned long long subblocks;     /* completed 100 ms sub-blocks G */
+    double   energy_ring[30];         /* E_g of sub-block g at [g % 30] */
+    float    peak_call[2], peak_hold[2];   /* L, R: of the last call that metered the station / since reset or reset_peaks */
+    unsigned below_gate, nonfinite;   /* gating blocks under -70 LUFS / non-finite */
+} fmd_meter_status;
+
+/* host-only (no GPU needed).  FMD_ERR_ARG unless fs is a multiple of 10 in 8000 ... 192000 */
+int fmd_meter_design(int fs, fmd_meter_design_t* out);
+double fmd_meter_lufs(double energy);
+/* hist [1000]: one station's histogram */
+int fmd_meter_integrated(const unsigned* hist, const fmd_meter_design_t* d, double* lufs);
+/* FMD_ERR_STATE before 4 (momentary) and 30 (short-term) completed sub-blocks */
+int fmd_meter_momentary(const fmd_meter_status* s, double* lufs);
+int fmd_meter_short_term(const fmd_meter_status* s, double* lufs);
+
+int fmd_meter_create(const fmd_meter_config* cfg, fmd_meter* out);
+int fmd_meter_destroy(fmd_meter m);
+/* everything of station `channel` (-1 = every station) as after create: counters, ring, filter states, histogram, peaks.  Waits for the
+ * meter's earlier work */
+int fmd_meter_reset(fmd_meter m, int channel);
+/* peak_call and peak_hold of station `channel` (-1 = every station) to 0; nothing else */
+int fmd_meter_reset_peaks(fmd_meter m, int channel);
+/* meters n frames of every station.  d_in [C][in_stride][2] f32 on the device, 8-byte aligned; d_active: [C] uint8 on the device,
+ * NULL = all: a station whose byte is 0 is skipped whole (no state, counter or peak of it changes).  n < 0, n > in_stride or
+ * n > max_input_frames return FMD_ERR_ARG and change nothing; n == 0 is valid (it sets the metered stations' peak_call to 0).
+ * Asynchronous on `stream`; consecutive calls may use different streams (the library orders them). */
+int fmd_meter_process_f32_dev(fmd_meter m, const float* d_in, long long in_stride, long long n, const uint8_t* d_active, void* stream);
+/* out [C]; synchronises with the meter's work */
+int fmd_meter_get_status(fmd_meter m, fmd_meter_status* out);
+/* hist [C][1000]; synchronises with the meter's work */
+int fmd_meter_get_histogram(fmd_meter m, unsigned* hist);
+/* the device's own [C] records, for a consumer on the device: ordered behind the meter's work on the stream of its last process call,
+ * valid until the next process call */
+int fmd_meter_status_dev(fmd_meter m, const fmd_meter_status** d_status);
+const char* fmd_meter_last_error(fmd_meter m);
+
 #ifdef __cplusplus
 }
 #endif
