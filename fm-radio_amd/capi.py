@@ -150,6 +150,14 @@ METER_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("subblocks", "<u8"), ("energy
 METER_BINS = 1000
 
 
+class PlanInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("effective_channels", "pilot_power_rows", "pll_k_adaptive", "pll_chained", "pll_waves", "lmr_inline", "lazy_capable",
+                                       "front_lds_pad", "front_big_tile", "extract_auto_pair", "pll_kernel")]
+
+
+PLL_KERNELS = ("low-work", 16, 8)      # fmd_plan_info.pll_kernel (FMD_PLL_KERNEL_*): the low-work kernel, the time-parallel one's lanes a station
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("total_ms", C.c_double), ("launches", C.c_int)]
 
@@ -241,6 +249,7 @@ def load_library():
     L.fmd_debug_split_front.argtypes = [H, C.c_int]
     L.fmd_debug_pll_adaptive.argtypes = [H, C.c_int, C.c_int]
     L.fmd_debug_extract_pairing.argtypes = [H, C.c_int]
+    L.fmd_debug_plan.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int, C.POINTER(PlanInfo)]
     L.fmd_profile_read.argtypes = [H, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]
     L.fmd_chan_design.argtypes = [C.c_double, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.fmd_chan_default_taps_per_phase.restype = C.c_int
@@ -373,6 +382,17 @@ def default_config(n_channels: int, fs_baseband: int = 1_024_000) -> "Config":
     if rc != FMD_OK:
         raise FmdError(rc, "unsupported configuration")
     return cfg
+
+
+def plan(cfg: "Config", pll_thresholds=None, unlocked_now: bool = False) -> PlanInfo:
+    """fmd_debug_plan (host only, no GPU): which kernels the library picks for cfg; pll_thresholds = (k16_max, time_parallel_max) as after
+    BatchDemod.pll_adaptive, None = the defaults.  PLL_KERNELS[info.pll_kernel] is what tests read off spec_stats."""
+    out = PlanInfo()
+    k16, tp = (-1, -1) if pll_thresholds is None else pll_thresholds
+    rc = load_library().fmd_debug_plan(C.byref(cfg), int(k16), int(tp), 1 if unlocked_now else 0, C.byref(out))
+    if rc != FMD_OK:
+        raise FmdError(rc, "unsupported configuration")
+    return out
 
 
 def _groups_view(raw: np.ndarray) -> np.ndarray:

@@ -17,6 +17,7 @@
 
 #include "fmd_design.h"
 #include "fmd_kernels.h"
+#include "fmd_plan.h"
 #include "fmd_math.h"
 #include "fmdemod.h"
 #include "fmdemod_debug.h"
@@ -49,16 +50,13 @@ struct fmd_handle_s {
     hipStream_t last_stream = nullptr;
     hipStream_t sF = nullptr, sA = nullptr, sB = nullptr, sB2 = nullptr, sX = nullptr, sR = nullptr, sD = nullptr;   // sD: the optional de-emphasis stage
     unsigned pll_seq = 0;                    // k_pilot_pll launches handed over per wavefront so far (0: hand-over by stream order)
-    // exact mode, 3585 .. 4096 effective stations: the pilot-PLL kernel's lane count follows what is out of lock — 8 lanes a station while every
+    // exact mode, Plan::pll_k_adaptive (above kPllK16MaxEff, up to kPllK16UnlockedMaxEff effective stations): the pilot-PLL kernel's lane count follows what is out of lock — 8 lanes a station while every
     // loop holds lock (fewest instructions beside the FIR kernels), 16 while some do not (a loop out of lock costs its wavefront ~1.8x, and
     // the kernel lasts as long as its slowest wavefront: 1.55 -> 1.12 ms a block with 16).  The kernel counts the wavefronts that ran out
     // of lock (Buffers::pll_hint[C]); a 4-byte copy of the counter comes back every other block, and the host looks at it without waiting.
     // The host may be queueing many blocks ahead of the GPU: what it goes by is the pair that came back — the newest launch that had wavefronts out
     // of lock and the newest launch that has run: out of lock "now" while the two are fewer than 8 launches apart; no news, no change.
-    bool pll_k_adaptive = false;
     unsigned* pll_unl_host = nullptr;        // pinned: [0] newest launch with wavefronts out of lock, [1] newest launch that has run
-    bool pll_chained = false;
-    int pll_waves = 0;
     hipEvent_t ev_in = nullptr, ev_P[kSlots] = {}, ev_F[kSlots] = {}, ev_A[kSlots] = {}, ev_B[kSlots] = {}, ev_E[kSlots] = {}, ev_X[kSlots] = {};
     hipEvent_t ev_D[kSlots] = {};            // k_front done, de-emphasis stage may start
     hipEvent_t ev_C[kSlots] = {};            // fmd_release_outputs: the consumer of a slot's outputs has finished with them
@@ -69,7 +67,7 @@ struct fmd_handle_s {
     bool pipelined = true;
     // Tolerance mode, fmd_submit_*: k_extract_bp shares k_front_mfma's stream and a block's extract + RDS stages are queued when the
     // NEXT block is submitted (behind that block's front end) or when somebody asks for the outputs — see process_dev
-    bool lazy_extract = false, lazy_capable = false;
+    bool lazy_extract = false;
     // pll_pending: the block's pilot stage has not been queued either — it rides in the next block's front-end launch (k_front_mfma<FUSED>) or,
     // where that is not possible (a start-up block, the getters' per-sample streams, a flush), goes in front of the extract stage on its own;
     // front_dep: the event behind the stage that made the block's fm_out; pll_dep / pll_stream: where the pilot stage was queued (NULL event: same
@@ -161,6 +159,16 @@ bool config_ok(const fmd_config* c, int* m) {
     *m = c->fs_baseband / 256000;
     if (c->block_size <= 0 || (c->block_size % (1024 * *m)) != 0) return false;
     return true;
+}
+
+// the block's lengths along the pipeline (m from config_ok)
+Dims dims_of(const fmd_config& c, int m) {
+    Dims d{};
+    d.C = c.n_channels; d.N = c.block_size; d.m = m;
+    d.n_fm_in = d.N / m; d.n_fm_out = d.n_fm_in / 2; d.n_rds = d.n_fm_out / 8; d.n_audio = d.n_fm_out / 4;
+    d.n_est = (d.n_audio + 9) / 10;
+    d.tail_base = front_tail_len(m, (c.flags & FMD_FLAG_FAST_MATH) != 0);
+    return d;
 }
 
 // Operand images of k_front_mfma's FIRs (fmd_kernels.hip FrontGeomM): v_mfma_f32_16x16x32_bf16's A operand, lane l = row l % 16,
@@ -612,7 +620,7 @@ int zero_history(fmd_handle h, hipStream_t s) {
     if (h->ctx.rds_decode) HIP_TRY(h, rds_dec_upload_initial(h->ctx.rds_dec.f, d.C, s));
     HIP_TRY(h, launch_reset_state(h->ctx, s));
     // everything is idle here (callers synchronise first): restart the per-wavefront PLL hand-over chain, watchdog flag included
-    if (b.pll_chain) HIP_TRY(h, hipMemsetAsync(b.pll_chain, 0, sizeof(unsigned) * ((size_t)h->pll_waves + 1 + (size_t)d.C + 2), s));      // (and the body hints behind it)
+    if (b.pll_chain) HIP_TRY(h, hipMemsetAsync(b.pll_chain, 0, sizeof(unsigned) * ((size_t)h->ctx.plan.pll_waves + 1 + (size_t)d.C + 2), s));      // (and the body hints behind it)
     if (h->pll_unl_host) h->pll_unl_host[0] = h->pll_unl_host[1] = 0u;
     h->ctx.pll_unlocked_now = false; h->ctx.pll_launch_no = 0;
     h->pll_seq = 0;
@@ -716,12 +724,12 @@ int sync_all(fmd_handle h) {
     h->last_p_event = nullptr;
     for (hipEvent_t& e : h->x_done) e = nullptr;
     if (!h->pipelined && h->n_blocks > 0) HIP_TRY(h, hipStreamSynchronize(h->last_stream));
-    if (h->pll_chained && h->pll_seq) {   // the hand-over watchdog of k_pilot_pll
+    if (h->ctx.plan.pll_chained && h->pll_seq) {   // the hand-over watchdog of k_pilot_pll
         unsigned timed_out = 0;
-        HIP_TRY(h, hipMemcpy(&timed_out, h->ctx.b.pll_chain + h->pll_waves, sizeof(unsigned), hipMemcpyDeviceToHost));
+        HIP_TRY(h, hipMemcpy(&timed_out, h->ctx.b.pll_chain + h->ctx.plan.pll_waves, sizeof(unsigned), hipMemcpyDeviceToHost));
         if (timed_out) {
             // reported once; the flag is cleared so that later calls do not fail for good, and the handle asks for a reset
-            (void)hipMemset(h->ctx.b.pll_chain + h->pll_waves, 0, sizeof(unsigned));
+            (void)hipMemset(h->ctx.b.pll_chain + h->ctx.plan.pll_waves, 0, sizeof(unsigned));
             h->poisoned = true;
             return fail(h, FMD_ERR_DEVICE, "k_pilot_pll: a wavefront's predecessor never published its state (call fmd_reset)");
         }
@@ -754,7 +762,7 @@ int process_dev(fmd_handle h, const InT* d_iq, int n_channels, int n_samples, vo
     hipStream_t sF = pipe ? h->sF : s, sA = pipe ? h->sA : s, sX = pipe ? h->sX : s, sR = pipe ? h->sR : s;
     const bool lazy = pipe && h->lazy_extract && !ordered;
     // consecutive blocks' PLL launches alternate between two streams when they hand over per wavefront (fmd_kernels.hip)
-    const bool chained = pipe && h->pll_chained;
+    const bool chained = pipe && h->ctx.plan.pll_chained;
     hipStream_t sB = pipe ? ((chained && (h->n_blocks & 1)) ? h->sB2 : h->sB) : s;
     ProfiledBlock* pm = nullptr;
     if (h->profiling) {
@@ -861,7 +869,7 @@ int process_dev(fmd_handle h, const InT* d_iq, int n_channels, int n_samples, vo
         if ((input_done ? input_done : front_dep) != persistent) HIP_TRY(h, hipEventRecord(persistent, predecim ? sP : sFq));
         h->ev_consumed = persistent;
     }
-    if (h->pll_k_adaptive) {
+    if (h->ctx.plan.pll_k_adaptive) {
         const unsigned done = reinterpret_cast<volatile unsigned*>(h->pll_unl_host)[1], heavy = reinterpret_cast<volatile unsigned*>(h->pll_unl_host)[0];
         h->ctx.pll_unlocked_now = heavy != 0u && (heavy > done || done - heavy < 8u);      // (heavy > done: the launch that is still running has such wavefronts)
         h->ctx.pll_launch_no++;
@@ -1042,30 +1050,17 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
             if (e != hipSuccess) return bail(fail(h, FMD_ERR_DEVICE, "event: %s", hipGetErrorString(e)));
         }
     }
-    Dims& d = h->ctx.d;
-    d.C = cfg->n_channels; d.N = cfg->block_size; d.m = m;
-    // Which pilot-PLL kernel: the time-parallel one halves a lone wavefront's latency for 2.6x the VALU work.  Once the chip's
-    // VALU throughput bounds the step the low-work kernel is faster (measured cross-over: between 7168 and 8192 channels at
-    // 256 kSa/s, about 8192 at 1.024 MSa/s).
-    h->ctx.pll_time_parallel_max_channels = (cfg->flags & FMD_FLAG_PLL_LOW_WORK) ? 0 : ((cfg->flags & FMD_FLAG_PLL_TIME_PARALLEL) ? 0x7fffffff : 7168);
-    // within the time-parallel kernel: 16 lanes per channel while a lone wavefront's latency is what matters (same-box A/B:
-    // 8 % faster at 2560 channels, 6 % at 3072), 8 lanes per channel (30 % fewer VALU instructions) beyond (2 % faster at 4096)
-    h->ctx.pll_k16_max_channels = (cfg->flags & FMD_FLAG_PLL_K8) ? 0 : 3584;
+    h->ctx.d = dims_of(*cfg, m);
+    const Dims& d = h->ctx.d;
+    h->ctx.plan = make_plan(d.C, d.m, d.n_fm_out, d.n_est, cfg->flags);
     h->ctx.pll_unlocked_now = false; h->ctx.pll_launch_no = 0;
-    d.n_fm_in = d.N / m; d.n_fm_out = d.n_fm_in / 2; d.n_rds = d.n_fm_out / 8; d.n_audio = d.n_fm_out / 4;
-    d.n_est = (d.n_audio + 9) / 10;
-    d.tail_base = front_tail_len(m, (cfg->flags & FMD_FLAG_FAST_MATH) != 0);
     h->bytes_cap = 16 * (d.n_rds / 256 + 1);
     h->ctx.bytes_cap = h->bytes_cap;
     h->ctx.keep_taps = (cfg->flags & FMD_FLAG_KEEP_TAPS) ? 1 : 0;
     h->ctx.rds_decode = (cfg->flags & FMD_FLAG_RDS_DECODE) ? 1 : 0;
     h->ctx.fast = (cfg->flags & FMD_FLAG_FAST_MATH) ? 1 : 0;
     if (const char* e = dev_env("FMD_DEBUG_SKIP_STAGES")) h->debug_skip = (unsigned)strtoul(e, nullptr, 0);   // development knob
-    // fmd_submit_* puts a block's extract stage off until the next block's front end is queued (launch_deferred) from 1024 stations'
-    // worth of 256 kSa/s blocks on (same-box A/B with the three-wavefront RDS stage: +-0 at 1024 stations, +1 % at 1536, +6 % at 2048,
-    // +10 % at 2560, +6-7 % from 3072 on; smaller batches are pure stage latency and keep every stage on a queue of its own)
-    h->lazy_capable = h->pipelined && h->ctx.fast && (size_t)d.C * d.n_fm_out >= (size_t)1024 * 8192;
-    h->lazy_extract = h->lazy_capable;
+    h->lazy_extract = h->ctx.plan.lazy_capable;
 
     fmd_controls def;
     fmd_default_controls(&def);
@@ -1162,22 +1157,9 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
                 hipStreamSynchronize(h->own_stream) != hipSuccess) rc = fail(h, FMD_ERR_DEVICE, "pilot table upload failed");
         }
     }
-    // per-wavefront hand-over between consecutive k_pilot_pll launches: the time-parallel kernel only, pipelined mode only
-    // (the low-work kernel k_pilot_pll_pairs has no chain argument: its launches must stay ordered by the stream)
-    const bool time_parallel = d.C <= h->ctx.pll_time_parallel_max_channels;
-    // (two ranges: 3585 .. 4096 effective stations — 8 or 16 lanes of the time-parallel kernel; above pll_time_parallel_max_channels, up to 16384 stations —
-    //  the low-work kernel or the time-parallel one with 8 lanes, whose sequence form gets through loops out of lock: 8192 stations with 1 % unlocked
-    //  2.87 -> 1.9 ms a block.  The FMD_FLAG_PLL_* selectors switch the choice off.)
-    h->pll_k_adaptive = !h->ctx.fast &&
-                        ((time_parallel && !(cfg->flags & (FMD_FLAG_PLL_K8 | FMD_FLAG_PLL_LOW_WORK)) && effective_channels(d) > h->ctx.pll_k16_max_channels && effective_channels(d) <= 4096) ||
-                         (!time_parallel && !(cfg->flags & FMD_FLAG_PLL_LOW_WORK) && d.C <= 16384));
-    // (FMD_FLAG_KEEP_TAPS: k_pll_taps reads the loop's start state ahead of the PLL kernel — consecutive blocks' launches stay in stream order;
-    //  the hand-over is indexed by wavefront, so it never runs beside the adaptive lane count)
-    h->pll_chained = h->pipelined && !h->ctx.fast && !h->ctx.keep_taps && time_parallel && effective_channels(d) <= 3328 && !(cfg->flags & (FMD_FLAG_PLL_STREAM_ORDER | FMD_FLAG_PLL_LOW_WORK)) &&
-                     !h->pll_k_adaptive;
-    h->pll_waves = (effective_channels(d) <= h->ctx.pll_k16_max_channels || (h->pll_k_adaptive && time_parallel)) ? (d.C + 3) / 4 : (d.C + 7) / 8;
-    if (!rc) rc = dev_alloc(h, &b.pll_chain, (size_t)h->pll_waves + 1 + (size_t)d.C + 2);
-    if (!rc) b.pll_hint = b.pll_chain + h->pll_waves + 1;
+    const int pll_waves = h->ctx.plan.pll_waves;      // per-wavefront hand-over between consecutive k_pilot_pll launches (Plan::pll_chained)
+    if (!rc) rc = dev_alloc(h, &b.pll_chain, (size_t)pll_waves + 1 + (size_t)d.C + 2);
+    if (!rc) b.pll_hint = b.pll_chain + pll_waves + 1;
     if (!rc && !h->ctx.fast) {
         if (hipHostMalloc(reinterpret_cast<void**>(&h->pll_unl_host), 64, hipHostMallocDefault) != hipSuccess) rc = fail(h, FMD_ERR_DEVICE, "pinned allocation failed");
         else h->pll_unl_host[0] = h->pll_unl_host[1] = 0u;
@@ -1293,7 +1275,7 @@ int fmd_set_output_lag(fmd_handle h, int on) {
     int rc = sync_all(h);
     if (rc) return rc;
     h->lag_outputs = on != 0;
-    h->lazy_extract = h->lazy_capable;        // (a caller that asked for every block's outputs at once had switched it off)
+    h->lazy_extract = h->ctx.plan.lazy_capable;        // (a caller that asked for every block's outputs at once had switched it off)
     return FMD_OK;
 }
 
@@ -1745,15 +1727,26 @@ int fmd_debug_split_front(fmd_handle h, int on) {
 
 int fmd_debug_pll_adaptive(fmd_handle h, int k16_max_channels, int time_parallel_max_channels) {
     if (!h || k16_max_channels < 0 || time_parallel_max_channels < 0) return FMD_ERR_ARG;
-    if (h->ctx.fast || !h->pll_unl_host || effective_channels(h->ctx.d) > 4096) return fail(h, FMD_ERR_ARG, "the exact mode, up to 4096 stations");
+    if (h->ctx.fast || !h->pll_unl_host || h->ctx.plan.effective > kPllK16UnlockedMaxEff) return fail(h, FMD_ERR_ARG, "the exact mode, up to 4096 stations");
     int rc = fmd_synchronize(h);
     if (rc) return rc;
-    h->ctx.pll_k16_max_channels = k16_max_channels;
-    h->ctx.pll_time_parallel_max_channels = time_parallel_max_channels;
-    const bool time_parallel = h->ctx.d.C <= time_parallel_max_channels;
-    h->pll_k_adaptive = !time_parallel || effective_channels(h->ctx.d) > k16_max_channels;
-    h->pll_chained = false;                  // (the per-wavefront hand-over is indexed by wavefront: one kernel, one lane count only)
+    const Dims& d = h->ctx.d;
+    const PllThresholds moved{k16_max_channels, time_parallel_max_channels};
+    h->ctx.plan = make_plan(d.C, d.m, d.n_fm_out, d.n_est, h->cfg.flags, &moved);
     h->ctx.pll_unlocked_now = false;
+    return FMD_OK;
+}
+
+int fmd_debug_plan(const fmd_config* cfg, int k16_max_channels, int time_parallel_max_channels, int unlocked_now, fmd_plan_info* out) {
+    int m = 0;
+    if (!out || !config_ok(cfg, &m) || (k16_max_channels < 0) != (time_parallel_max_channels < 0)) return FMD_ERR_ARG;
+    const Dims d = dims_of(*cfg, m);
+    const PllThresholds moved{k16_max_channels, time_parallel_max_channels};
+    const bool is_moved = k16_max_channels >= 0;
+    if (is_moved && ((cfg->flags & FMD_FLAG_FAST_MATH) || effective_channels(d.C, d.m) > kPllK16UnlockedMaxEff)) return FMD_ERR_ARG;   // (as fmd_debug_pll_adaptive)
+    const Plan p = make_plan(d.C, d.m, d.n_fm_out, d.n_est, cfg->flags, is_moved ? &moved : nullptr);
+    *out = fmd_plan_info{p.effective, p.power_rows, p.pll_k_adaptive, p.pll_chained, p.pll_waves, p.lmr_inline, p.lazy_capable, p.front_lds_pad,
+                         p.front_big_tile, p.extract_auto_pair, (int)pll_kernel(p, unlocked_now != 0)};
     return FMD_OK;
 }
 

@@ -6,6 +6,7 @@
 #include <stdint.h>
 #include <cstdlib>
 
+#include "fmd_plan.h"
 #include "fmdemod.h"
 
 namespace fmd {
@@ -261,10 +262,6 @@ inline int rds_groups_cap(int cap_bytes) { return cap_bytes * 8 / 79 + 2; }
 // t1: optional event that receives the kernel's end timestamp / completion (as FMD_LAUNCH's last-kernel event)
 hipError_t launch_rds_decode(const RdsDecArgs& a, hipStream_t s, hipEvent_t t1 = nullptr);
 
-// Batch size the latency/throughput switches are keyed on: the stages behind the first decimator cost the same at every input
-// rate; the decimator itself (m > 1) adds FIR work and HBM traffic that compete with the serial kernels (measured cross-overs: x 1.5).
-inline int effective_channels(const Dims& d) { return d.m == 1 ? d.C : d.C + d.C / 2; }
-
 struct LaunchCtx {
     Dims d;
     Buffers b;
@@ -281,10 +278,9 @@ struct LaunchCtx {
     RdsDecBufs rds_dec;
     int uniform_cutoffs;                  // every station has the same L+R / L-R cut-offs: one set of k_extract_bp's tap tables serves any of them
     int extract_pairing;                  // k_extract_bp with two stations per workgroup: 0 = where it pays (launch_extract_ta), 1 = wherever possible (tests), 2 = never
-    int pll_time_parallel_max_channels;   // batches up to this size use the time-parallel PLL kernel, larger ones the low-work one
-    int pll_k16_max_channels;             // (channels x m) up to this: 16 lanes per channel, above: 8
+    Plan plan;                            // which kernels this batch gets (fmd_plan.h): made once, by fmd_create
     unsigned pll_launch_no;               // 1-based number of the pilot-PLL launch being queued (exact mode)
-    bool pll_unlocked_now;                // wavefronts ran out of lock in the last blocks the host has seen (fmd_api.cpp): 16 lanes up to 4096 stations, and the time-parallel kernel instead of the low-work one above pll_time_parallel_max_channels
+    bool pll_unlocked_now;                // wavefronts ran out of lock in the last blocks the host has seen (fmd_api.cpp): pll_kernel()'s second argument
 };
 
 // where a slot's traces lie inside Buffers::taps[buf] (null pointers when the handle keeps none)

@@ -1389,7 +1389,7 @@ __device__ __forceinline__ void pilot_pll_body(Dims d, const float2* __restrict_
     // packet, no kernel boundary and no launch ramp between the two ends of the serial chain any more.  The predecessor was
     // submitted earlier and never waits on anything later, and 2 x 512 such workgroups cannot fill the chip, so the wait
     // cannot deadlock; a 2 s watchdog turns a lost predecessor (a failed launch) into an error flag instead of a hang.
-    // Used for effective batches up to 3328 stations (fmd_api.cpp, effective_channels): beyond, two launches' workgroups resident at once take more
+    // Used for batches up to kPllChainMaxEff effective stations (fmd_plan.h): beyond, two launches' workgroups resident at once take more
     // from the FIR kernels than the hand-over gap gives back (same-box A/B: -13 % at 1024 stations, -7 % at 3072, +4 % at 4096).
     if (chain) {
         const unsigned long long w0 = __builtin_amdgcn_s_memrealtime();
@@ -2193,8 +2193,6 @@ __device__ __forceinline__ void fir8_quad(const float* __restrict__ ph, int P, i
 #pragma unroll
     for (int v = 0; v < 4; v++) out[v] = (acc[v][0] + acc[v][2]) + (acc[v][1] + acc[v][3]);
 }
-
-constexpr int kLmrInlineMax = 512;   // estimates per block (n_audio / 10) up to which k_extract integrates the L-R phase itself
 
 // reference ExtractComponents :511-516 — avg = sum / n; phase = fmod(phase + 0.1 avg, 2 pi)
 __device__ __forceinline__ float lmr_phase_finish(float sum, int n_est, float cur) {
@@ -3008,14 +3006,6 @@ __global__ void k_reset(Dims d, float* __restrict__ state) {
 // ---------------------------------------------------------------------------------------------
 // host-side stage launchers
 // ---------------------------------------------------------------------------------------------
-// Batches of 1024 .. 1792 stations at 256 kSa/s (the smallest on the deferred schedule — fmd_api.cpp — up to where the front end's own length takes over): the serial RDS stage's launch is the step (0.092 ms alone, 0.12 beside the throughput kernels)
-// and the front end has slack.  With 44 KB of extra dynamic LDS its workgroups come two to a CU instead of six and leave the serial stages'
-// wavefronts the issue slots: 1024 stations 0.125 -> 0.114 ms (RDS launch 0.121 -> 0.102, the front end itself 0.060 -> 0.053), 1536 stations
-// 0.135 -> 0.126, 1792: 0.144 -> 0.136, 1024 x u8 0.117 -> 0.110; 512 stations and the 40 of configs[4]: no difference; 640: slower (0.111 ->
-// 0.120: no deferred schedule there), 2048: slower (0.148 -> 0.154) (profiles/round5/rds_stage_ab.txt).
-static size_t front_lds_pad(const Dims& d) {
-    return (d.m == 1 && d.C >= 1024 && d.C <= 1792) ? 45056 : 0;
-}
 template <typename InT, int TT = 512, bool FAST = false>
 static hipError_t launch_front(const LaunchCtx& ctx, SlotRef r, const InT* d_iq, hipStream_t s, const SlotRef* pll = nullptr) {
     using G = FrontGeom<TT>;
@@ -3025,12 +3015,8 @@ static hipError_t launch_front(const LaunchCtx& ctx, SlotRef r, const InT* d_iq,
     }
     if constexpr (TT == 512) {
         if constexpr (FAST && sizeof(InT) == 8) {
-            // cf32 captures, round 6: 2048-output tiles for batches that still give the chip 12 288 workgroups (3072 stations' worth of 64 ms blocks) —
-            // half as many workgroups fetch the FIR's operand images (7 KB each from L2: 230 MB a block at 1024-output tiles) and recompute a
-            // tile's 63-sample halo: k_front_mfma 0.154 -> 0.142 ms in the step, 268 -> 278 GSa/s at 4096 stations, +2.5 % at 8192; at 2048 stations
-            // (8192 workgroups) 1024-output tiles are 1 % better (profiles/round6/front_tile_ab.txt).
-            const bool big = (long)d.C * (d.n_fm_out / 2048) >= 12288;
-            if (big && d.n_fm_out % 2048 == 0 && !ctx.deemph_in_tile) return launch_front<InT, 2048, FAST>(ctx, r, d_iq, s, pll);
+            // cf32 captures: 2048-output tiles for the batches of kFrontBigTileMinWorkgroups
+            if (ctx.plan.front_big_tile && d.n_fm_out % 2048 == 0 && !ctx.deemph_in_tile) return launch_front<InT, 2048, FAST>(ctx, r, d_iq, s, pll);
         }
         if constexpr (FAST && sizeof(InT) == 2) {   // u8 captures: 2048-output tiles (4 KB of input per 1024-output workgroup leaves too few bytes in flight per CU)
             if (d.n_fm_out % 2048 == 0 && !ctx.deemph_in_tile) return launch_front<InT, 2048, FAST>(ctx, r, d_iq, s, pll);
@@ -3048,15 +3034,15 @@ static hipError_t launch_front(const LaunchCtx& ctx, SlotRef r, const InT* d_iq,
         const unsigned grid = (unsigned)(tiles * d.C + pf.n_wg);
         if (ctx.deemph_in_tile) {
             using GM = FrontGeomM<TT, kDeemphWarmup>;
-            if (pll) FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, kDeemphWarmup, true>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + front_lds_pad(d), s, d, d_iq,
+            if (pll) FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, kDeemphWarmup, true>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + ctx.plan.front_lds_pad, s, d, d_iq,
                                 ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1], ctx.b.fo_pl[r.buf], ctx.front.fm_gain, ctx.b.deemph, ctx.b.front_mfma, ctx.b.pv_pl[r.buf], ctx.b.sparse_tab, pf);
-            else FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, kDeemphWarmup, false>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + front_lds_pad(d), s, d, d_iq,
+            else FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, kDeemphWarmup, false>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + ctx.plan.front_lds_pad, s, d, d_iq,
                             ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1], ctx.b.fo_pl[r.buf], ctx.front.fm_gain, ctx.b.deemph, ctx.b.front_mfma, ctx.b.pv_pl[r.buf], ctx.b.sparse_tab, pf);
         } else {
             using GM = FrontGeomM<TT, 0>;
-            if (pll) FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, 0, true>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + front_lds_pad(d), s, d, d_iq,
+            if (pll) FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, 0, true>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + ctx.plan.front_lds_pad, s, d, d_iq,
                                 ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1], ctx.b.fo_pl[r.buf], ctx.front.fm_gain, ctx.b.deemph, ctx.b.front_mfma, ctx.b.pv_pl[r.buf], ctx.b.sparse_tab, pf);
-            else FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, 0, false>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + front_lds_pad(d), s, d, d_iq,
+            else FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, 0, false>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + ctx.plan.front_lds_pad, s, d, d_iq,
                             ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1], ctx.b.fo_pl[r.buf], ctx.front.fm_gain, ctx.b.deemph, ctx.b.front_mfma, ctx.b.pv_pl[r.buf], ctx.b.sparse_tab, pf);
         }
         return hipGetLastError();
@@ -3141,6 +3127,7 @@ hipError_t launch_stage_front(const LaunchCtx& ctx, SlotRef r, const void* d_iq,
     if (ctx.d.m > 1) {
         LaunchCtx c1 = ctx;
         c1.d.N = ctx.d.n_fm_in; c1.d.m = 1;
+        c1.plan.front_lds_pad = front_lds_pad(c1.d.C, c1.d.m);      // (the front end sees a 256 kSa/s batch: the pad goes by the station count alone)
         if (ctx.fast) return launch_front<float>(c1, r, reinterpret_cast<const float*>(ctx.b.fm_in[r.buf]), s, pll);   // (phases: k_predecim<.., true>)
         return launch_front<float2>(c1, r, ctx.b.fm_in[r.buf], s);
     }
@@ -3167,7 +3154,7 @@ hipError_t launch_stage_deemph(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
 
 hipError_t launch_stage_power(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
     const Dims& d = ctx.d;
-    if (effective_channels(d) <= 2816) {   // the batches whose step is this kernel's latency (and whose PLL launches hand over per wavefront)
+    if (ctx.plan.power_rows) {
         FMD_LAUNCH(r, true, true, k_pilot_power<true>, dim3(serial_waves(d)), dim3(kWave), 0, s, d, ctx.b.fm_out_iq[r.buf], ctx.b.pilot[r.buf], ctx.b.state,
                    ctx.loops, (int)S_PILOT_POWER0 + r.buf);
     } else {
@@ -3196,15 +3183,14 @@ hipError_t launch_stage_pll(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
     // FMD_FLAG_KEEP_TAPS: the loop's traces, from the state the block starts from (ahead of the kernel that advances it)
     if (ctx.b.taps[r.buf]) hipLaunchKernelGGL(k_pll_taps, dim3((unsigned)((d.C + kWave - 1) / kWave)), dim3(kWave), 0, s, d, ctx.b.pilot[r.buf], ctx.b.state, ctx.loops,
                                               (int)S_PILOT_POWER0 + r.buf, tap_ptrs(ctx, r.buf));
-    // (ctx.pll_unlocked_now: wavefronts ran out of lock in the last blocks the host has seen — the low-work kernel gives way to the time-parallel one,
-    //  whose sequence form gets through such loops; the time-parallel kernel takes 16 lanes a station up to 4096 stations)
-    if (d.C > ctx.pll_time_parallel_max_channels && !ctx.pll_unlocked_now) {
+    const PllKernel kernel = pll_kernel(ctx.plan, ctx.pll_unlocked_now);
+    if (kernel == PllKernel::LowWork) {
         FMD_LAUNCH(r, true, true, k_pilot_pll_pairs, dim3((unsigned)((d.C + kPllCh - 1) / kPllCh)), dim3(2 * kWave), 0, s, d, ctx.b.pilot[r.buf], ctx.b.pll_dt[r.buf],
                    ctx.b.state, ctx.loops, (int)S_PILOT_POWER0 + r.buf, ctx.b.spec_stats, ctx.b.pll_hint, ctx.pll_launch_no);
         return hipGetLastError();
     }
     unsigned int* chain = r.seq ? ctx.b.pll_chain : nullptr;
-    if (effective_channels(d) <= ctx.pll_k16_max_channels || (ctx.pll_unlocked_now && effective_channels(d) <= 4096)) {
+    if (kernel == PllKernel::TimeParallel16) {
         FMD_LAUNCH(r, true, true, k_pilot_pll<16>, dim3((unsigned)((d.C + 3) / 4)), dim3(kWave), 0, s, d, ctx.b.pilot[r.buf], ctx.b.pll_dt[r.buf], ctx.b.state,
                    ctx.loops, (int)S_PILOT_POWER0 + r.buf, ctx.b.spec_stats, chain, r.seq, ctx.b.pll_hint, ctx.pll_launch_no);
     } else {
@@ -3214,10 +3200,6 @@ hipError_t launch_stage_pll(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
     return hipGetLastError();
 }
 
-// Tolerance mode, batches up to 6144 stations: same-box A/B +3 % at 4096 stations, but -3 % at 8192 and -4 % at 16384 (there the
-// k_extract launches running back to back crowd k_front out: its launches take 1.7x as long); and in the exact mode the pilot
-// PLL's launch chain sets the step, which k_extract launches without gaps between them slow down (-8 %).
-static inline bool lmr_inline(const LaunchCtx& ctx) { return ctx.fast && ctx.d.n_est <= kLmrInlineMax && effective_channels(ctx.d) <= 6144; }
 static inline int lmr_field(int par) { return par ? (int)S_LMR_PHASE_PREV : (int)S_LMR_PHASE_CUR; }   // state field holding P_k, k & 1 == par
 
 template <int TA, bool FAST = false>
@@ -3231,40 +3213,40 @@ static void launch_extract_ta(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
         // round 5: the mixers behind the FIRs, a wavefront per tile (fmd_kernels_bp.inc)
         const int tiles = d.n_audio / TA;
         // a workgroup = station x 4 nt tiles, nt per wavefront (the station's tap tables are staged once per workgroup): the largest nt that
-        // still leaves 1536 workgroups for the chip (4 per CU: a round and a half)
+        // still leaves kExtractMinWorkgroups for the chip
         int nt = 1;
         // (nt travels in the low 16 bits of one kernel argument, the development switch in bit 16: block_size has no cap, so the search is
         //  clamped — ADVICE r5: at 8 bits a block of a million samples could wrap nt to 0)
         constexpr int kNtMax = 0x7fff;
-        for (int v = (tiles + 3) / 4 < kNtMax ? (tiles + 3) / 4 : kNtMax; v >= 1; v--) if ((long)((tiles + 4 * v - 1) / (4 * v)) * d.C >= 1536) { nt = v; break; }
+        for (int v = (tiles + 3) / 4 < kNtMax ? (tiles + 3) / 4 : kNtMax; v >= 1; v--) if ((long)((tiles + 4 * v - 1) / (4 * v)) * d.C >= kExtractMinWorkgroups) { nt = v; break; }
         int grid_x = (tiles + 4 * nt - 1) / (4 * nt) * d.C;
         // round 6: two stations per workgroup (tables and the block edge's matrix fetched once for both) where a station is one workgroup anyway,
-        // every station has the same cut-offs and the pairs still are 1536 workgroups; ctx.extract_pairing: 1 forces it (tests), 2 switches it off
+        // every station has the same cut-offs and the pairs still are kExtractMinWorkgroups (Plan::extract_auto_pair); ctx.extract_pairing: 1 forces it (tests), 2 switches it off
         const bool one_wg_per_station = 4 * nt >= tiles;
         const bool pair = ctx.uniform_cutoffs && one_wg_per_station && 2 * tiles <= 4 * kNtMax && d.C >= 2 &&
-                          (ctx.extract_pairing == 1 || (ctx.extract_pairing == 0 && (d.C + 1) / 2 >= 1536));
+                          (ctx.extract_pairing == 1 || (ctx.extract_pairing == 0 && ctx.plan.extract_auto_pair));
         if (pair) { nt = (2 * tiles + 3) / 4; grid_x = (d.C + 1) / 2; }
         if (dev_env("FMD_BP_NOEDGE")) nt |= 0x10000;                     // (development, timing only: the first tile's sums over the previous block skipped)
         if (pair) FMD_LAUNCH(r, true, true, k_extract_bp<2>, dim3((unsigned)grid_x), dim3(TA), 0, s, d, nt, b.fo_pl[r.buf], b.pll_poly[r.buf],
                    b.bp_tab, b.aud_idx, b.rds_bp_tab, b.bp_edge, b.mix,
                    b.state, b.audio[r.buf], b.rds[r.buf], b.lmr_est[r.par], b.lpr[r.buf], b.lmr[r.buf], ctx.keep_taps,
-                   lmr_inline(ctx) ? b.lmr_est[r.par ^ 1] : (const float*)nullptr, lmr_field(r.par), lmr_field(r.par ^ 1), b.rds_pow[r.buf]);
+                   ctx.plan.lmr_inline ? b.lmr_est[r.par ^ 1] : (const float*)nullptr, lmr_field(r.par), lmr_field(r.par ^ 1), b.rds_pow[r.buf]);
         else FMD_LAUNCH(r, true, true, k_extract_bp<1>, dim3((unsigned)grid_x), dim3(TA), 0, s, d, nt, b.fo_pl[r.buf], b.pll_poly[r.buf],
                    b.bp_tab, b.aud_idx, b.rds_bp_tab, b.bp_edge, b.mix,
                    b.state, b.audio[r.buf], b.rds[r.buf], b.lmr_est[r.par], b.lpr[r.buf], b.lmr[r.buf], ctx.keep_taps,
-                   lmr_inline(ctx) ? b.lmr_est[r.par ^ 1] : (const float*)nullptr, lmr_field(r.par), lmr_field(r.par ^ 1), b.rds_pow[r.buf]);
+                   ctx.plan.lmr_inline ? b.lmr_est[r.par ^ 1] : (const float*)nullptr, lmr_field(r.par), lmr_field(r.par ^ 1), b.rds_pow[r.buf]);
         return;
     }
     FMD_LAUNCH(r, true, true, (k_extract<TA, FAST>), dim3((unsigned)(d.n_audio / TA * d.C)), dim3(TA), 0, s, d, b.fm_out_iq[r.buf], b.pll_dt[r.buf],
                        b.iq_tail[r.par], b.dt_tail[r.par], b.iq_tail[r.par ^ 1], b.dt_tail[r.par ^ 1], b.b_lpr, b.b_lmr, ctx.rds_taps, b.mix,
                        b.state, b.audio[r.buf], b.rds[r.buf], b.lmr_est[r.par], b.lpr[r.buf], b.lmr[r.buf], ctx.keep_taps,
-                       lmr_inline(ctx) ? b.lmr_est[r.par ^ 1] : (const float*)nullptr, lmr_field(r.par), lmr_field(r.par ^ 1));
+                       ctx.plan.lmr_inline ? b.lmr_est[r.par ^ 1] : (const float*)nullptr, lmr_field(r.par), lmr_field(r.par ^ 1));
 }
 
 hipError_t launch_stage_extract(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
     if (ctx.d.n_audio % 256 == 0) launch_extract_ta<256>(ctx, r, s);
     else launch_extract_ta<128>(ctx, r, s);
-    if (!lmr_inline(ctx)) {   // P_{b+1} behind block b
+    if (!ctx.plan.lmr_inline) {   // P_{b+1} behind block b
         if (ctx.fast && ctx.d.n_est <= kLmrInlineMax)
             hipLaunchKernelGGL(k_lmr_phase_fast, dim3((unsigned)ctx.d.C), dim3(kWave), 0, s, ctx.d, ctx.b.lmr_est[r.par], ctx.b.state, lmr_field(r.par),
                                ctx.b.state + (size_t)lmr_field(r.par ^ 1) * ctx.d.C);

@@ -81,6 +81,26 @@ int fmd_profile_read(fmd_handle h, fmd_kernel_time* out, int cap, int* n_out);
  * 8 lanes / the low-work kernel while every loop holds lock, 16 lanes (up to 4096 stations) / the time-parallel kernel while some do not.  With small
  * values a small batch exercises the switches (tests/test_gpu_parity.py); results are bit-identical whatever kernel runs. */
 int fmd_debug_pll_adaptive(fmd_handle h, int k16_max_channels, int time_parallel_max_channels);
+/* Host-only (no GPU needed): which kernels the library picks for a configuration (fm-radio_amd/csrc/fmd_plan.h, the one place where batch sizes
+ * decide).  k16_max_channels, time_parallel_max_channels: both negative = the defaults, both >= 0 = as after fmd_debug_pll_adaptive with them
+ * (FMD_ERR_ARG where that hook refuses).  unlocked_now: whether loops ran out of lock in the last blocks, which pll_kernel depends on.
+ * pll_kernel is the exact mode's; the tolerance mode runs k_pll_sparse whatever it says.  tests/test_plan_cpu.py compares every field with a
+ * restatement of the rules and aims the batch sizes of tests/test_gpu_every_station.py at the switches. */
+enum { FMD_PLL_KERNEL_LOW_WORK = 0, FMD_PLL_KERNEL_TIME_PARALLEL_16 = 1, FMD_PLL_KERNEL_TIME_PARALLEL_8 = 2 };
+typedef struct {
+    int effective_channels;   /* stations, x 1.5 at 1.024 and 2.048 MSa/s: what most switches compare */
+    int pilot_power_rows;     /* k_pilot_power<true> */
+    int pll_k_adaptive;       /* the pilot-PLL kernel follows what is out of lock */
+    int pll_chained;          /* consecutive k_pilot_pll launches hand over per wavefront */
+    int pll_waves;            /* wavefronts the hand-over array is allocated for */
+    int lmr_inline;           /* k_extract integrates the L-R phase itself */
+    int lazy_capable;         /* fmd_submit_*: the extract stage waits for the next block's front end */
+    int front_lds_pad;        /* bytes of extra dynamic LDS of k_front_mfma */
+    int front_big_tile;       /* cf32: 2048-output front-end tiles where the block length allows */
+    int extract_auto_pair;    /* k_extract_bp<2> where its other conditions hold */
+    int pll_kernel;           /* FMD_PLL_KERNEL_* */
+} fmd_plan_info;
+int fmd_debug_plan(const fmd_config* cfg, int k16_max_channels, int time_parallel_max_channels, int unlocked_now, fmd_plan_info* out);
 /* Tolerance mode: k_extract_bp with two stations per workgroup (the tap tables and the block edge's matrix fetched once for both; results bit-identical):
  * 0 = where it pays (3072 stations and more with equal cut-offs, the default), 1 = wherever possible (so that tests reach it with a few stations), 2 = never. */
 int fmd_debug_extract_pairing(fmd_handle h, int mode);

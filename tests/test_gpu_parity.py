@@ -415,6 +415,29 @@ def test_pilot_pll_kernel_follows_what_is_out_of_lock(pkg, thresholds, calm, bus
     assert seen[-2:] == [calm, calm], seen                                          # back in lock
 
 
+@pytest.mark.parametrize("n_ch,thresholds,kernel", [(12, (4, 7168), 8), (12, (4, 4), "low-work"), (5, None, 16)])
+def test_pilot_pll_kernel_in_lock_is_the_one_the_plan_names(pkg, n_ch, thresholds, kernel):
+    """The kernel the launcher picks while every loop holds lock is the one fmd_debug_plan (fm-radio_amd/csrc/fmd_plan.h, host only) names for the
+    configuration with unlocked_now = 0: read off the statistics of three blocks in lock, with the test hook's thresholds and with the defaults."""
+    bs, nb = 16384, 16
+    two = [synth.to_cf32(synth.fm_capture(nb * bs, fs=256_000.0, seed=1300 + c, channel=c)["iq"]) for c in range(2)]
+    caps = np.stack([two[c % 2] for c in range(n_ch)])
+    dm = pkg.BatchDemod(n_channels=n_ch, block_size=bs, fs_baseband=256_000)
+    if thresholds is not None:
+        dm.pll_adaptive(*thresholds)
+    seen = []
+    for b in range(nb):
+        dm.process(caps[:, b * bs:(b + 1) * bs])
+        dm.synchronize()
+        p = dm.spec_stats(reset=True)["pll"]
+        seen.append("low-work" if p["spans"] == 0 else (16 if p["samples_per_span"] > 8.0 else 8))
+    dm.close()
+    named = pkg.PLL_KERNELS[pkg.plan(pkg.Config(n_ch, bs, 256_000, -1, 0), thresholds, unlocked_now=False).pll_kernel]      # (flags 0: BatchDemod's defaults)
+    print(f"{n_ch} stations, thresholds {thresholds}: kernels seen {seen}, the plan names {named}")
+    assert named == kernel
+    assert seen[-3:] == [named] * 3, seen
+
+
 @pytest.mark.parametrize("thresholds,pipelined", [(None, True), ((2, 7168), True), ((2, 2), True), ((2, 2), False)])
 def test_loops_that_wander_in_and_out_of_lock(pkg, thresholds, pipelined):
     """Stations whose pilot loop neither holds lock nor loses it for good — receiver noise only, a pilot at the noise floor, a dead front end
@@ -482,7 +505,7 @@ def test_pcm16_audio_frames_match_the_scraper_conversion(pkg):
 
 
 def test_pll_handover_per_wavefront_equals_stream_order(pkg):
-    """Batches up to 2816 stations hand the PLL state from one block's k_pilot_pll launch to the next per wavefront, while both
+    """Batches up to 3328 effective stations (kPllChainMaxEff, fm-radio_amd/csrc/fmd_plan.h) hand the PLL state from one block's k_pilot_pll launch to the next per wavefront, while both
     launches are resident (two streams, release/acquire on a per-wavefront sequence number) — the same bits as ordering the two
     launches by the stream (FMD_FLAG_PLL_STREAM_ORDER), block after block, for a batch that spans many wavefronts."""
     import torch

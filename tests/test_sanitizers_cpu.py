@@ -86,3 +86,23 @@ def test_host_drivers_under_sanitizers(asan_build, tmp_path):
     pcm = np.frombuffer(wav[44:], np.int16)
     assert np.array_equal(pcm, (audio.reshape(-1) * (np.float32(32767.0) * np.float32(0.95))).astype(np.int32).astype(np.int16))
     assert (tmp_path / "o.bin").read_bytes() == g["rds_bytes"].tobytes()[:len(g["rds_bytes"]) // 16 * 16]
+
+
+def test_kernel_selection_plan_under_sanitizers_equals_the_model(asan_build, tmp_path):
+    """fm-radio_amd/csrc/fmd_plan.cpp built with plain g++ (no HIP, no library) under the sanitizers: the corners of tests/test_plan_cpu.py's sweep — the
+    station counts within 3 of every switch at each rate and block length, every FMD_FLAG_PLL_* selector, both modes, in and out of lock, and the
+    moved thresholds of the parity tests — give tests/plan_model.py's answers."""
+    import plan_model as M
+    cases = []
+    for fs in (256_000, 1_024_000, 2_048_000):
+        for bs in (16384, 10240, 65536):
+            m, n_fm_out, n_est = M.lengths(fs, bs * (fs // 256_000))
+            for flags in (0, M.FAST_MATH, M.KEEP_TAPS, M.NO_PIPELINE, M.PLL_TIME_PARALLEL, M.PLL_LOW_WORK, M.PLL_K8, M.PLL_TIME_PARALLEL | M.PLL_K8,
+                          M.PLL_STREAM_ORDER, M.FAST_MATH | M.NO_PIPELINE):
+                cases += [(c, m, n_fm_out, n_est, flags, None, u) for c in M.stations_to_try() for u in (0, 1)]
+    cases += [(c, 1, 8192, 205, 0, th, u) for c in (5, 12) for th in ((4, 7168), (4, 4), (2, 7168), (2, 2)) for u in (0, 1)]
+    (tmp_path / "cases.txt").write_text("".join(f"{c} {m} {nf} {ne} {fl} {th[0] if th else -1} {th[1] if th else -1} {u}\n" for c, m, nf, ne, fl, th, u in cases))
+    out = _run([asan_build / "plan_main", tmp_path / "cases.txt"]).stdout.split("\n")[:-1]
+    assert len(out) == len(cases) > 20_000
+    for line, (c, m, nf, ne, fl, th, u) in zip(out, cases):
+        assert tuple(map(int, line.split())) == M.plan(c, m, nf, ne, fl, th, bool(u)), (c, m, nf, ne, fl, th, u)
