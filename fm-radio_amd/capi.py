@@ -148,6 +148,16 @@ class MeterDesign(C.Structure):
 METER_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("subblocks", "<u8"), ("energy_ring", "<f8", (30,)), ("peak_call", "<f4", (2,)),
                                ("peak_hold", "<f4", (2,)), ("below_gate", "<u4"), ("nonfinite", "<u4")])
 METER_BINS = 1000
+# fmd_meter_create_ex's feature bits
+METER_TRUE_PEAK = 1
+METER_RANGE = 2
+# include/fmdemod.h fmd_meter_r128_status (24 bytes)
+METER_R128_DTYPE = np.dtype([("tp_call", "<f4", (2,)), ("tp_hold", "<f4", (2,)), ("st_below", "<u4"), ("st_nonfinite", "<u4")])
+
+
+class MeterTpDesign(C.Structure):
+    """include/fmdemod.h fmd_meter_tp_design_t"""
+    _fields_ = [("L", C.c_int), ("taps_per_phase", C.c_int), ("taps", (C.c_float * 12) * 3)]
 
 
 class PlanInfo(C.Structure):
@@ -322,6 +332,15 @@ def load_library():
     L.fmd_meter_get_status.argtypes = [C.c_void_p, C.c_void_p]
     L.fmd_meter_get_histogram.argtypes = [C.c_void_p, C.c_void_p]
     L.fmd_meter_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.fmd_meter_create_ex.argtypes = [C.POINTER(MeterConfig), C.c_uint, C.POINTER(C.c_void_p)]
+    L.fmd_meter_features.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
+    L.fmd_meter_tp_design.argtypes = [C.c_int, C.POINTER(MeterTpDesign)]
+    L.fmd_meter_dbtp.restype = C.c_double
+    L.fmd_meter_dbtp.argtypes = [C.c_float]
+    L.fmd_meter_get_r128_status.argtypes = [C.c_void_p, C.c_void_p]
+    L.fmd_meter_r128_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.fmd_meter_get_range_histogram.argtypes = [C.c_void_p, C.c_void_p]
+    L.fmd_meter_range.argtypes = [C.c_void_p, C.POINTER(MeterDesign), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.fmd_meter_last_error.restype = C.c_char_p
     L.fmd_meter_last_error.argtypes = [C.c_void_p]
     L.fmd_last_error.restype = C.c_char_p
@@ -1308,21 +1327,54 @@ def meter_short_term(record) -> float:
     return _meter_window("fmd_meter_short_term", record)
 
 
+def meter_tp_design(fs: int) -> MeterTpDesign:
+    """fmd_meter_tp_design (host only): the true-peak interpolator's oversampling factor L and its (L - 1) x 12 float taps"""
+    L = load_library()
+    d = MeterTpDesign()
+    rc = L.fmd_meter_tp_design(int(fs), C.byref(d))
+    if rc != FMD_OK:
+        raise FmdError(rc, L.fmd_meter_last_error(None).decode() or L.fmd_status_string(rc).decode())
+    return d
+
+
+def meter_dbtp(x):
+    """fmd_meter_dbtp: 20 log10 of a float32 peak, in dBTP (dBFS for a sample peak); -inf for 0.  Scalars or arrays"""
+    L = load_library()
+    a = np.asarray(x, np.float32)
+    out = np.array([L.fmd_meter_dbtp(C.c_float(float(v))) for v in a.reshape(-1)], np.float64).reshape(a.shape)
+    return float(out) if out.ndim == 0 else out
+
+
+def meter_range(hist, design: MeterDesign):
+    """fmd_meter_range (host only): (lra in LU, low, high in LUFS) of one station's [1000] range histogram.  FmdError with status
+    FMD_ERR_STATE when no bin survives the gates"""
+    L = load_library()
+    h = np.ascontiguousarray(hist, np.uint32)
+    if h.shape != (METER_BINS,):
+        raise ValueError("hist must hold 1000 bins")
+    lra, low, high = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
+    rc = L.fmd_meter_range(h.ctypes.data_as(C.c_void_p), C.byref(design), C.byref(lra), C.byref(low), C.byref(high))
+    if rc != FMD_OK:
+        raise FmdError(rc, L.fmd_meter_last_error(None).decode() or L.fmd_status_string(rc).decode())
+    return lra.value, low.value, high.value
+
+
 class LoudnessMeter:
     """ITU-R BS.1770 loudness and sample peak of C stations' audio on the GPU (fmd_meter_*).  Feed it the same [C, n, 2] float32 CUDA
     tensors as AudioResampler and AudioMixer (BatchDemod.audio_tensor() at 32 kHz, or a resampler's output at fs); it changes nothing in
     them.  status() returns METER_STATUS_DTYPE records, histogram() the gating blocks' [C, 1000] counts; momentary / short_term /
-    integrated turn them into LUFS on the host."""
+    integrated turn them into LUFS on the host.  features = METER_TRUE_PEAK | METER_RANGE adds the maximum true-peak level
+    (r128_status(), true_peak_dbtp()) and the loudness range (range_histogram(), loudness_range())."""
 
-    def __init__(self, n_channels: int, fs: int, max_input_frames: int = 1 << 16, device: int = -1):
+    def __init__(self, n_channels: int, fs: int, max_input_frames: int = 1 << 16, device: int = -1, features: int = 0):
         self.L = load_library()
         cfg = MeterConfig(int(n_channels), int(fs), int(max_input_frames), device)
         self.m = C.c_void_p()
-        rc = self.L.fmd_meter_create(C.byref(cfg), C.byref(self.m))
+        rc = self.L.fmd_meter_create_ex(C.byref(cfg), int(features), C.byref(self.m))
         if rc != FMD_OK:
             self.m = None
             raise FmdError(rc, self.L.fmd_meter_last_error(None).decode() or self.L.fmd_status_string(rc).decode())
-        self.n_channels, self.fs = int(n_channels), int(fs)
+        self.n_channels, self.fs, self.features = int(n_channels), int(fs), int(features)
         self.design = meter_design(fs)
 
     def close(self):
@@ -1390,3 +1442,41 @@ class LoudnessMeter:
         """[C] float64 LUFS: the gated programme loudness since reset (-inf where no gating block passed -70 LUFS)"""
         hist = self.histogram() if hist is None else hist
         return np.array([meter_integrated(h, self.design) for h in hist], np.float64)
+
+    def r128_status(self) -> np.ndarray:
+        """[C] METER_R128_DTYPE records (true peaks, the short-term values' counters); waits for the meter's work.  FMD_ERR_STATE on a
+        meter without features"""
+        out = np.zeros(self.n_channels, METER_R128_DTYPE)
+        self._check(self.L.fmd_meter_get_r128_status(self.m, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def r128_status_dev_ptr(self) -> int:
+        """fmd_meter_r128_status_dev: the address of the device's own [C] records, valid until the next process call"""
+        p = C.c_void_p()
+        self._check(self.L.fmd_meter_r128_status_dev(self.m, C.byref(p)))
+        return p.value
+
+    def range_histogram(self) -> np.ndarray:
+        """[C, 1000] uint32 counts of short-term values (one per 100 ms) per 0.1 LU bin from -70 LUFS; needs METER_RANGE"""
+        out = np.zeros((self.n_channels, METER_BINS), np.uint32)
+        self._check(self.L.fmd_meter_get_range_histogram(self.m, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def loudness_range(self, hist=None):
+        """(lra, low, high): three [C] float64 arrays, the loudness range in LU and its 10th / 95th percentiles in LUFS; NaN where no
+        short-term value survives the gates yet"""
+        hist = self.range_histogram() if hist is None else hist
+        out = np.full((3, len(hist)), np.nan, np.float64)
+        for c, h in enumerate(hist):
+            try:
+                out[:, c] = meter_range(h, self.design)
+            except FmdError as e:
+                if e.status != FMD_ERR_STATE:
+                    raise
+        return out[0], out[1], out[2]
+
+    def true_peak_dbtp(self) -> np.ndarray:
+        """[C, 2] float64: the held maximum true-peak level of L and R in dBTP (-inf for silence); needs METER_TRUE_PEAK"""
+        if not self.features & METER_TRUE_PEAK:
+            raise FmdError(FMD_ERR_STATE, "the meter was created without METER_TRUE_PEAK")
+        return meter_dbtp(self.r128_status()["tp_hold"])

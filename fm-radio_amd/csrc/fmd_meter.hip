@@ -13,7 +13,11 @@
 // depend on o1).  Sub-block ends fall at a different frame in every station (each counts its own frames), so they are a lane-divergent
 // branch taken once in Nsb frames.
 //
-// Denormals: fp64 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
+// With FMD_METER_RANGE the call runs k_meter<true>, which at each sub-block end from the 30th on also classifies the short-term window (the
+// ring's 30 energies) into a second histogram; k_meter<false> is the kernel as it was.  With FMD_METER_TRUE_PEAK a second kernel, k_meter_tp,
+// follows on the same stream: a 4x (or 2x) polyphase interpolator over every sample, parallel in time (below).
+//
+// Denormals: fp64 and fp32 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -46,10 +50,12 @@ struct MeterCoef {
     int Nsb;
 };
 
-// in [C][in_stride][2]; status [C]; carry [C][2][5]; hist [C][1000]; edge [1001]
+// in [C][in_stride][2]; status [C]; carry [C][2][5]; hist [C][1000]; edge [1001]; with kRange r128 [C] and range_hist [C][1000]
+template <bool kRange>
 __global__ __launch_bounds__(kT) void k_meter(const float* __restrict__ in, long long in_stride, long long n, const uint8_t* __restrict__ active, int C,
                                               MeterCoef k, const double* __restrict__ edge, fmd_meter_status* __restrict__ status,
-                                              double* __restrict__ carry, unsigned* __restrict__ hist) {
+                                              double* __restrict__ carry, unsigned* __restrict__ hist, fmd_meter_r128_status* __restrict__ r128,
+                                              unsigned* __restrict__ range_hist) {
     __shared__ __attribute__((aligned(16))) float xs[kT * kRow];
     const int lane = threadIdx.x, rail = lane & 1;
     const int c0 = blockIdx.x * kCh, c = c0 + (lane >> 1);
@@ -64,6 +70,7 @@ __global__ __launch_bounds__(kT) void k_meter(const float* __restrict__ in, long
     float peak_call = 0.0f, peak_hold = 0.0f;
     unsigned long long G = 0, frames = 0;
     unsigned below = 0, nonfin = 0;
+    unsigned st_below = 0, st_nonfin = 0;    // (kRange: the short-term values' counters)
     double e1 = 0.0, e2 = 0.0, e3 = 0.0;     // E_{G-1}, E_{G-2}, E_{G-3} (the owner's)
     int ri = 0;                              // G % 30
     int rem = 0x7fffffff;                    // frames to the end of the open sub-block
@@ -78,6 +85,7 @@ __global__ __launch_bounds__(kT) void k_meter(const float* __restrict__ in, long
         if (rail == 0) {
             below = st->below_gate;
             nonfin = st->nonfinite;
+            if (kRange) { st_below = r128[c].st_below; st_nonfin = r128[c].st_nonfinite; }
             ri = (int)(G % kMeterRing);
             e1 = st->energy_ring[(ri + kMeterRing - 1) % kMeterRing];
             e2 = st->energy_ring[(ri + kMeterRing - 2) % kMeterRing];
@@ -130,6 +138,25 @@ __global__ __launch_bounds__(kT) void k_meter(const float* __restrict__ in, long
                         hist[(size_t)c * kMeterBins + lo]++;
                     }
                 }
+                if (kRange && G >= (unsigned long long)(kMeterRing - 1)) {    // the short-term window: sub-blocks G - 29 ... G, oldest first
+                    double sum = 0.0;
+                    int i = ri + 1 == kMeterRing ? 0 : ri + 1;
+                    for (int j = 0; j < kMeterRing; j++) {
+                        sum += st->energy_ring[i];
+                        i = i + 1 == kMeterRing ? 0 : i + 1;
+                    }
+                    const double S = sum / 30.0;
+                    if (!(fabs(S) <= 1.7976931348623157e308)) st_nonfin++;
+                    else if (S < edge[0]) st_below++;
+                    else {
+                        int lo = 0, hi = kMeterBins;
+                        while (hi - lo > 1) {
+                            const int mid = (lo + hi) >> 1;
+                            if (edge[mid] <= S) lo = mid; else hi = mid;
+                        }
+                        range_hist[(size_t)c * kMeterBins + lo]++;
+                    }
+                }
                 e3 = e2; e2 = e1; e1 = E;
                 ri = ri + 1 == kMeterRing ? 0 : ri + 1;
             }
@@ -166,6 +193,145 @@ __global__ __launch_bounds__(kT) void k_meter(const float* __restrict__ in, long
         st->subblocks = G;
         st->below_gate = below;
         st->nonfinite = nonfin;
+        if (kRange) { r128[c].st_below = st_below; r128[c].st_nonfinite = st_nonfin; }
+    }
+}
+
+// ---- true peak ------------------------------------------------------------------------------------------------------------------------
+//
+// No recurrence in time: one workgroup of 256 threads per station walks the station's frames in tiles of 1024.  A tile and the 11 frames
+// before it (the station's history for the first tile, the input itself after it) are loaded coalesced, 16 bytes a lane where the station's
+// row is 16-byte aligned and 8 otherwise, and de-interleaved into one LDS row per rail; the row starts 12 floats before the tile, so the
+// thread that owns frames 4t ... 4t + 3 reads its 16-float window (x[4t - 12] ... x[4t + 3]) as four aligned 16-byte reads per rail,
+// consecutive lanes 16 bytes apart.  Per frame and rail the three phases are three independent chains of twelve fmas; the 36 taps are a
+// kernel argument and sit in SGPRs.  The maximum is folded per thread, across the wavefront by cross-lane moves, across the four wavefronts
+// through LDS; thread 0 alone stores the station's four floats, and threads 0 ... 21 the new history.  No atomics.
+constexpr int kTpT = 256;                        // threads per workgroup
+constexpr int kTpTile = 4 * kTpT;                // frames per tile
+constexpr int kTpLead = 12;                      // floats of an LDS row before the tile's first frame (11 of history behind one unused)
+constexpr int kTpRow = kTpLead + kTpTile;        // floats per LDS row
+constexpr int kTpH = fmd::kMeterTpHist;          // 11
+static_assert(kTpH == 11 && kTpLead == kTpH + 1 && 2 * kTpH <= kTpT, "k_meter_tp's window");
+static_assert(sizeof(fmd_meter_r128_status) == 24 && offsetof(fmd_meter_r128_status, tp_hold) == 8 && offsetof(fmd_meter_r128_status, st_below) == 16,
+              "fmd_meter_r128_status layout");
+
+struct TpTaps { float g[3][12]; };
+
+// in [C][in_stride][2]; r128 [C]; tphist [C][2][11]
+template <int L>
+__global__ __launch_bounds__(kTpT) void k_meter_tp(const float* __restrict__ in, long long in_stride, long long n, const uint8_t* __restrict__ active,
+                                                   TpTaps taps, fmd_meter_r128_status* __restrict__ r128, float* __restrict__ tphist) {
+    __shared__ __attribute__((aligned(16))) float xs[2 * kTpRow];
+    __shared__ float red[2 * (kTpT / 64)];
+    const int c = blockIdx.x, t = threadIdx.x;
+    if (active && active[c] == 0) return;                                    // (uniform over the workgroup)
+    const float* base = in + (size_t)c * (size_t)in_stride * 2;
+    float* hs = tphist + (size_t)c * 2 * kTpH;
+    const bool wide = (reinterpret_cast<uintptr_t>(base) & 15) == 0;         // 16-byte loads: every tile starts a multiple of 8 KB in
+
+    // the history this call leaves: frame n - 11 + k for slot k, taken from the input, or from the old history where the call is shorter.
+    // Every read of the old history happens before the first barrier, every write after the last.
+    float hnew = 0.0f;
+    if (t < 2 * kTpH) {
+        const int r = t / kTpH, kk = t - r * kTpH;
+        const long long i = n - kTpH + kk;
+        hnew = i >= 0 ? base[(size_t)i * 2 + r] : hs[r * kTpH + (int)(n + kk)];
+    }
+
+    float4 pre[2];                                                           // two frames each; wide: 2 loads of 16 bytes, else 4 of 8
+    float halo = 0.0f;
+    auto fetch = [&](long long f0) {
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const long long f = f0 + q * (2 * kTpT) + 2 * t;
+            pre[q] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (f + 1 < n) {
+                if (wide) pre[q] = *reinterpret_cast<const float4*>(base + (size_t)f * 2);
+                else {
+                    const float2 a = *reinterpret_cast<const float2*>(base + (size_t)f * 2);
+                    const float2 b = *reinterpret_cast<const float2*>(base + (size_t)f * 2 + 2);
+                    pre[q] = make_float4(a.x, a.y, b.x, b.y);
+                }
+            } else if (f < n) {
+                const float2 a = *reinterpret_cast<const float2*>(base + (size_t)f * 2);
+                pre[q] = make_float4(a.x, a.y, 0.0f, 0.0f);
+            }
+        }
+        if (L > 1 && t < 2 * kTpH && f0 < n) {                               // the 11 frames before the tile, per rail
+            const int r = t / kTpH, kk = t - r * kTpH;
+            halo = f0 == 0 ? hs[r * kTpH + kk] : base[(size_t)(f0 - kTpH + kk) * 2 + r];
+        }
+    };
+    auto stash = [&]() {
+#pragma unroll
+        for (int q = 0; q < 2; q++) {
+            const int o = kTpLead + q * (2 * kTpT) + 2 * t;
+            *reinterpret_cast<float2*>(&xs[o]) = make_float2(pre[q].x, pre[q].z);
+            *reinterpret_cast<float2*>(&xs[kTpRow + o]) = make_float2(pre[q].y, pre[q].w);
+        }
+        if (L > 1 && t < 2 * kTpH) {
+            const int r = t / kTpH, kk = t - r * kTpH;
+            xs[r * kTpRow + 1 + kk] = halo;
+        }
+    };
+
+    float tp[2] = {0.0f, 0.0f};
+    fetch(0);
+    for (long long f0 = 0; f0 < n; f0 += kTpTile) {
+        stash();
+        __syncthreads();
+        fetch(f0 + kTpTile);                                                 // in flight while this tile runs (nothing is loaded past n)
+        const int cnt = n - f0 < kTpTile ? (int)(n - f0) : kTpTile;
+        if (4 * t < cnt) {
+#pragma unroll
+            for (int r = 0; r < 2; r++) {
+                const float* row = &xs[r * kTpRow + 4 * t];
+                float w[16];                                                 // w[i] = x[4t - 12 + i]
+                if (L > 1) {
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const float4 v = *reinterpret_cast<const float4*>(row + 4 * q);
+                        w[4 * q] = v.x; w[4 * q + 1] = v.y; w[4 * q + 2] = v.z; w[4 * q + 3] = v.w;
+                    }
+                } else {
+                    const float4 v = *reinterpret_cast<const float4*>(row + kTpLead);
+                    w[12] = v.x; w[13] = v.y; w[14] = v.z; w[15] = v.w;
+                }
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    float m = fabsf(w[12 + j]);
+#pragma unroll
+                    for (int p = 0; p < L - 1; p++) {
+                        float y = 0.0f;
+#pragma unroll
+                        for (int kk = 0; kk < 12; kk++) y = fmaf(taps.g[p][kk], w[12 + j - kk], y);
+                        m = fmaxf(m, fabsf(y));                              // (a NaN is dropped: fmaxf returns its other operand)
+                    }
+                    if (4 * t + j < cnt) tp[r] = fmaxf(tp[r], m);
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+#pragma unroll
+    for (int r = 0; r < 2; r++) {
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) tp[r] = fmaxf(tp[r], __shfl_xor(tp[r], d));
+        if ((t & 63) == 0) red[r * (kTpT / 64) + (t >> 6)] = tp[r];
+    }
+    __syncthreads();
+    if (t < 2 * kTpH) hs[t] = hnew;
+    if (t == 0) {
+        fmd_meter_r128_status* st = r128 + c;
+#pragma unroll
+        for (int r = 0; r < 2; r++) {
+            float m = red[r * (kTpT / 64)];
+#pragma unroll
+            for (int wv = 1; wv < kTpT / 64; wv++) m = fmaxf(m, red[r * (kTpT / 64) + wv]);
+            st->tp_call[r] = m;
+            st->tp_hold[r] = fmaxf(st->tp_hold[r], m);
+        }
     }
 }
 
@@ -180,6 +346,12 @@ struct fmd_meter_s {
     double* d_carry = nullptr;              // [C][2][5]
     unsigned* d_hist = nullptr;             // [C][1000]
     double* d_edge = nullptr;               // [1001]
+    unsigned features = 0;                  // FMD_METER_*
+    fmd_meter_tp_design_t tp{};
+    TpTaps tp_taps{};
+    fmd_meter_r128_status* d_r128 = nullptr;   // [C], with either feature
+    float* d_tphist = nullptr;              // [C][2][11], with FMD_METER_TRUE_PEAK
+    unsigned* d_range = nullptr;            // [C][1000], with FMD_METER_RANGE
     hipEvent_t done = nullptr;              // end of the previous call's work
     bool have_done = false;
     std::string err;
@@ -198,18 +370,27 @@ static bool mt_quiesce(fmd_meter m) {
 
 extern "C" {
 
-int fmd_meter_create(const fmd_meter_config* cfg, fmd_meter* out) {
+int fmd_meter_create(const fmd_meter_config* cfg, fmd_meter* out) { return fmd_meter_create_ex(cfg, 0u, out); }
+
+int fmd_meter_create_ex(const fmd_meter_config* cfg, unsigned features, fmd_meter* out) {
     if (!cfg || !out) return mt_fail(nullptr, FMD_ERR_ARG, "null configuration or handle");
+    if (features & ~(FMD_METER_TRUE_PEAK | FMD_METER_RANGE)) return mt_fail(nullptr, FMD_ERR_ARG, "unknown feature bits 0x%x", features);
     if (cfg->n_channels <= 0 || cfg->max_input_frames <= 0 || cfg->max_input_frames > (1LL << 30))
         return mt_fail(nullptr, FMD_ERR_ARG, "n_channels %d is not positive or max_input_frames %lld outside (0, 2^30]", cfg->n_channels, cfg->max_input_frames);
     fmd_meter_design_t d;
     if (fmd::meter_design(cfg->fs, &d, &fmd::meter_global_error()) != FMD_OK) return FMD_ERR_ARG;
+    fmd_meter_tp_design_t tp;
+    if (fmd::meter_tp_design(cfg->fs, &tp, &fmd::meter_global_error()) != FMD_OK) return FMD_ERR_ARG;
     if (fmd_device_count() <= 0) return mt_fail(nullptr, FMD_ERR_NO_DEVICE, "no gfx950 device");
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return mt_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
     fmd_meter m = new fmd_meter_s();
     m->device = dev; m->C = cfg->n_channels; m->fs = cfg->fs; m->max_in = cfg->max_input_frames;
     m->design = d;
+    m->features = features;
+    m->tp = tp;
+    for (int p = 0; p < 3; p++)
+        for (int kk = 0; kk < fmd::kMeterTpTaps; kk++) m->tp_taps.g[p][kk] = tp.taps[p][kk];
     m->coef = MeterCoef{d.pre_b[0], d.pre_b[1], d.pre_b[2], -d.pre_a[1], -d.pre_a[2], d.rlb_b[0], d.rlb_b[1], d.rlb_b[2], -d.rlb_a[1], -d.rlb_a[2],
                         (double)d.frames_per_subblock, d.frames_per_subblock};
     const size_t C = (size_t)m->C;
@@ -218,6 +399,9 @@ int fmd_meter_create(const fmd_meter_config* cfg, fmd_meter* out) {
     ok = ok && hipMalloc(&m->d_carry, sizeof(double) * 2 * kCarry * C) == hipSuccess;
     ok = ok && hipMalloc(&m->d_hist, sizeof(unsigned) * kMeterBins * C) == hipSuccess;
     ok = ok && hipMalloc(&m->d_edge, sizeof(double) * (kMeterBins + 1)) == hipSuccess;
+    if (features) ok = ok && hipMalloc(&m->d_r128, sizeof(fmd_meter_r128_status) * C) == hipSuccess;
+    if (features & FMD_METER_TRUE_PEAK) ok = ok && hipMalloc(&m->d_tphist, sizeof(float) * 2 * kTpH * C) == hipSuccess;
+    if (features & FMD_METER_RANGE) ok = ok && hipMalloc(&m->d_range, sizeof(unsigned) * kMeterBins * C) == hipSuccess;
     ok = ok && hipEventCreateWithFlags(&m->done, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipMemcpy(m->d_edge, d.edge, sizeof(double) * (kMeterBins + 1), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok || fmd_meter_reset(m, -1) != FMD_OK) { fmd_meter_destroy(m); return mt_fail(nullptr, FMD_ERR_DEVICE, "device allocation failed"); }
@@ -228,7 +412,7 @@ int fmd_meter_create(const fmd_meter_config* cfg, fmd_meter* out) {
 int fmd_meter_destroy(fmd_meter m) {
     if (!m) return FMD_ERR_ARG;
     (void)mt_quiesce(m);
-    for (void* p : {(void*)m->d_status, (void*)m->d_carry, (void*)m->d_hist, (void*)m->d_edge})
+    for (void* p : {(void*)m->d_status, (void*)m->d_carry, (void*)m->d_hist, (void*)m->d_edge, (void*)m->d_r128, (void*)m->d_tphist, (void*)m->d_range})
         if (p) (void)hipFree(p);
     if (m->done) (void)hipEventDestroy(m->done);
     delete m;
@@ -242,7 +426,10 @@ int fmd_meter_reset(fmd_meter m, int channel) {
     const size_t c0 = channel < 0 ? 0 : (size_t)channel, cn = channel < 0 ? (size_t)m->C : 1;
     if (hipMemset(m->d_status + c0, 0, sizeof(fmd_meter_status) * cn) != hipSuccess ||
         hipMemset(m->d_carry + c0 * 2 * kCarry, 0, sizeof(double) * 2 * kCarry * cn) != hipSuccess ||
-        hipMemset(m->d_hist + c0 * kMeterBins, 0, sizeof(unsigned) * kMeterBins * cn) != hipSuccess)
+        hipMemset(m->d_hist + c0 * kMeterBins, 0, sizeof(unsigned) * kMeterBins * cn) != hipSuccess ||
+        (m->d_r128 && hipMemset(m->d_r128 + c0, 0, sizeof(fmd_meter_r128_status) * cn) != hipSuccess) ||
+        (m->d_tphist && hipMemset(m->d_tphist + c0 * 2 * kTpH, 0, sizeof(float) * 2 * kTpH * cn) != hipSuccess) ||
+        (m->d_range && hipMemset(m->d_range + c0 * kMeterBins, 0, sizeof(unsigned) * kMeterBins * cn) != hipSuccess))
         return mt_fail(m, FMD_ERR_DEVICE, "memset failed");
     if (hipStreamSynchronize(nullptr) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
     return FMD_OK;
@@ -255,6 +442,9 @@ int fmd_meter_reset_peaks(fmd_meter m, int channel) {
     const size_t c0 = channel < 0 ? 0 : (size_t)channel, cn = channel < 0 ? (size_t)m->C : 1;
     char* p = reinterpret_cast<char*>(m->d_status + c0) + offsetof(fmd_meter_status, peak_call);
     if (hipMemset2D(p, sizeof(fmd_meter_status), 0, 4 * sizeof(float), cn) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "memset failed");
+    // tp_call and tp_hold, the record's first 16 bytes (the interpolator's history stays)
+    if (m->d_r128 && hipMemset2D(m->d_r128 + c0, sizeof(fmd_meter_r128_status), 0, 4 * sizeof(float), cn) != hipSuccess)
+        return mt_fail(m, FMD_ERR_DEVICE, "memset failed");
     if (hipStreamSynchronize(nullptr) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
     return FMD_OK;
 }
@@ -268,9 +458,21 @@ int fmd_meter_process_f32_dev(fmd_meter m, const float* d_in, long long in_strid
     if (hipSetDevice(m->device) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "hipSetDevice failed");
     // every station's state carries over from call to call: a caller that switches streams is ordered behind the previous call
     if (m->have_done && hipStreamWaitEvent(s, m->done, 0) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "stream wait failed");
-    hipLaunchKernelGGL(k_meter, dim3((unsigned)((m->C + kCh - 1) / kCh)), dim3(kT), 0, s, d_in, in_stride, n, d_active, m->C, m->coef, m->d_edge,
-                       m->d_status, m->d_carry, m->d_hist);
+    const dim3 grid((unsigned)((m->C + kCh - 1) / kCh));
+    if (m->features & FMD_METER_RANGE)
+        hipLaunchKernelGGL(k_meter<true>, grid, dim3(kT), 0, s, d_in, in_stride, n, d_active, m->C, m->coef, m->d_edge, m->d_status, m->d_carry,
+                           m->d_hist, m->d_r128, m->d_range);
+    else
+        hipLaunchKernelGGL(k_meter<false>, grid, dim3(kT), 0, s, d_in, in_stride, n, d_active, m->C, m->coef, m->d_edge, m->d_status, m->d_carry,
+                           m->d_hist, static_cast<fmd_meter_r128_status*>(nullptr), static_cast<unsigned*>(nullptr));
     if (hipGetLastError() != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "k_meter launch failed");
+    if (m->features & FMD_METER_TRUE_PEAK) {                                 // one workgroup per station, behind k_meter
+        const dim3 tgrid((unsigned)m->C);
+        if (m->tp.L == 4) hipLaunchKernelGGL(k_meter_tp<4>, tgrid, dim3(kTpT), 0, s, d_in, in_stride, n, d_active, m->tp_taps, m->d_r128, m->d_tphist);
+        else if (m->tp.L == 2) hipLaunchKernelGGL(k_meter_tp<2>, tgrid, dim3(kTpT), 0, s, d_in, in_stride, n, d_active, m->tp_taps, m->d_r128, m->d_tphist);
+        else hipLaunchKernelGGL(k_meter_tp<1>, tgrid, dim3(kTpT), 0, s, d_in, in_stride, n, d_active, m->tp_taps, m->d_r128, m->d_tphist);
+        if (hipGetLastError() != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "k_meter_tp launch failed");
+    }
     if (hipEventRecord(m->done, s) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "event record failed");
     m->have_done = true;
     return FMD_OK;
@@ -293,6 +495,35 @@ int fmd_meter_get_histogram(fmd_meter m, unsigned* hist) {
 int fmd_meter_status_dev(fmd_meter m, const fmd_meter_status** d_status) {
     if (!m || !d_status) return mt_fail(m, FMD_ERR_ARG, "null meter or output");
     *d_status = m->d_status;
+    return FMD_OK;
+}
+
+int fmd_meter_features(fmd_meter m, unsigned* features) {
+    if (!m || !features) return mt_fail(m, FMD_ERR_ARG, "null meter or output");
+    *features = m->features;
+    return FMD_OK;
+}
+
+int fmd_meter_get_r128_status(fmd_meter m, fmd_meter_r128_status* out) {
+    if (!m || !out) return mt_fail(m, FMD_ERR_ARG, "null meter or output");
+    if (!m->features) return mt_fail(m, FMD_ERR_STATE, "the meter was created without FMD_METER_TRUE_PEAK or FMD_METER_RANGE");
+    if (!mt_quiesce(m)) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (hipMemcpy(out, m->d_r128, sizeof(fmd_meter_r128_status) * (size_t)m->C, hipMemcpyDeviceToHost) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "copy failed");
+    return FMD_OK;
+}
+
+int fmd_meter_r128_status_dev(fmd_meter m, const fmd_meter_r128_status** d_out) {
+    if (!m || !d_out) return mt_fail(m, FMD_ERR_ARG, "null meter or output");
+    if (!m->features) return mt_fail(m, FMD_ERR_STATE, "the meter was created without FMD_METER_TRUE_PEAK or FMD_METER_RANGE");
+    *d_out = m->d_r128;
+    return FMD_OK;
+}
+
+int fmd_meter_get_range_histogram(fmd_meter m, unsigned* hist) {
+    if (!m || !hist) return mt_fail(m, FMD_ERR_ARG, "null meter or output");
+    if (!(m->features & FMD_METER_RANGE)) return mt_fail(m, FMD_ERR_STATE, "the meter was created without FMD_METER_RANGE");
+    if (!mt_quiesce(m)) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (hipMemcpy(hist, m->d_range, sizeof(unsigned) * kMeterBins * (size_t)m->C, hipMemcpyDeviceToHost) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "copy failed");
     return FMD_OK;
 }
 

@@ -5,6 +5,8 @@
 #include <cmath>
 #include <limits>
 
+#include "fmd_bessel.h"
+
 namespace fmd {
 
 std::string& meter_global_error() {
@@ -47,11 +49,72 @@ int meter_design(int fs, fmd_meter_design_t* out, std::string* err) {
     return FMD_OK;
 }
 
+// The true-peak interpolator (include/fmdemod.h, "tp design"): a Kaiser-windowed sinc at L fs, cut into its L phases.
+int meter_tp_design(int fs, fmd_meter_tp_design_t* out, std::string* err) {
+    if (!out) { *err = "null design"; return FMD_ERR_ARG; }
+    if (fs < 8000 || fs > 192000 || fs % 10 != 0) { *err = "fs " + std::to_string(fs) + " is not a multiple of 10 in 8000 ... 192000"; return FMD_ERR_ARG; }
+    const double pi = 3.14159265358979323846, beta = 5.0;
+    const int L = fs < 88200 ? 4 : fs < 176400 ? 2 : 1, T = kMeterTpTaps, N = L * T;
+    const double c = (double)(N / 2), i0b = bessel_i0(beta);
+    out->L = L;
+    out->taps_per_phase = T;
+    for (int p = 0; p < 3; p++)
+        for (int k = 0; k < T; k++) out->taps[p][k] = 0.0f;
+    for (int p = 1; p < L; p++) {
+        double g[kMeterTpTaps], sum = 0.0;
+        for (int k = 0; k < T; k++) {
+            const double t = (double)(k * L + p) - c, x = t / (double)L, r = t / c;
+            const double s = x == 0.0 ? 1.0 : std::sin(pi * x) / (pi * x);
+            g[k] = s * bessel_i0(beta * std::sqrt(1.0 - r * r)) / i0b;
+            sum += g[k];
+        }
+        for (int k = 0; k < T; k++) out->taps[p - 1][k] = (float)(g[k] / sum);
+    }
+    return FMD_OK;
+}
+
 }  // namespace fmd
 
 extern "C" {
 
 int fmd_meter_design(int fs, fmd_meter_design_t* out) { return fmd::meter_design(fs, out, &fmd::meter_global_error()); }
+
+int fmd_meter_tp_design(int fs, fmd_meter_tp_design_t* out) { return fmd::meter_tp_design(fs, out, &fmd::meter_global_error()); }
+
+double fmd_meter_dbtp(float peak) {
+    if (peak == 0.0f) return -std::numeric_limits<double>::infinity();
+    return 20.0 * std::log10((double)peak);
+}
+
+int fmd_meter_range(const unsigned* hist, const fmd_meter_design_t* d, double* lra, double* low, double* high) {
+    if (!hist || !d || !lra || !low || !high) { fmd::meter_global_error() = "null histogram, design or output"; return FMD_ERR_ARG; }
+    unsigned long long n0 = 0;
+    double s = 0.0;
+    for (int j = 0; j < fmd::kMeterBins; j++) {
+        n0 += hist[j];
+        s += (double)hist[j] * d->centre[j];
+    }
+    if (n0 == 0) { fmd::meter_global_error() = "the range histogram is empty"; return FMD_ERR_STATE; }
+    const double gate = 0.01 * (s / (double)n0);
+    unsigned long long n = 0;
+    for (int j = 0; j < fmd::kMeterBins; j++)
+        if (d->centre[j] >= gate) n += hist[j];
+    if (n == 0) { fmd::meter_global_error() = "no short-term value passes the relative gate"; return FMD_ERR_STATE; }
+    const unsigned long long r10 = (unsigned long long)std::floor(0.10 * (double)(n - 1) + 0.5);
+    const unsigned long long r95 = (unsigned long long)std::floor(0.95 * (double)(n - 1) + 0.5);
+    int j10 = -1, j95 = -1;
+    unsigned long long cum = 0;
+    for (int j = 0; j < fmd::kMeterBins; j++) {
+        if (!(d->centre[j] >= gate)) continue;
+        cum += hist[j];
+        if (j10 < 0 && cum > r10) j10 = j;
+        if (j95 < 0 && cum > r95) j95 = j;
+    }
+    *low = -70.0 + 0.1 * (double)j10 + 0.05;
+    *high = -70.0 + 0.1 * (double)j95 + 0.05;
+    *lra = (double)(j95 - j10) / 10.0;
+    return FMD_OK;
+}
 
 double fmd_meter_lufs(double energy) {
     if (energy == 0.0) return -std::numeric_limits<double>::infinity();

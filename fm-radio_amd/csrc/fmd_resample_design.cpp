@@ -10,6 +10,8 @@
 // operations per value (DESIGN.md "Audio resampler").
 #include "fmd_resample_design.h"
 
+#include "fmd_bessel.h"
+
 #include <math.h>
 
 #include <algorithm>
@@ -35,12 +37,6 @@ bool resample_ref_table(int n_in, int n_out, std::vector<ResampleRefTap>* tab) {
     }
     tab->swap(t);
     return true;
-}
-
-static double bessel_i0(double x) {
-    double sum = 1.0, term = 1.0;
-    for (int k = 1; k < 64; k++) { term *= (x / (2.0 * k)) * (x / (2.0 * k)); sum += term; if (term < 1e-18 * sum) break; }
-    return sum;
 }
 
 // Kaiser-windowed sinc at the up-sampled rate L fs_in (Kaiser's estimates for the window: beta = 0.1102 (A - 8.7) and

@@ -655,8 +655,9 @@ const char* fmd_iqcorr_last_error(fmd_iqcorr h);
  * Batched loudness meter (NOT part of the reference): ITU-R BS.1770 / EBU R 128 programme loudness and sample peak of every station's
  * audio, measured where the audio already is.  It reads the same device array [C][in_stride][2] as the resampler and the mixer
  * (fmd_audio_dev's view, or a resampler's output), changes nothing in the stage that wrote it, and keeps one fmd_meter_status record and
- * a 1000-bin histogram per station.  It measures the audio, not the RF signal.  No true peak, no loudness range; channel weights are 1.0
- * for L and R.  Arithmetic, restated in C by tests/cpp/meter_ref.c:
+ * a 1000-bin histogram per station.  It measures the audio, not the RF signal.  Maximum true-peak level (BS.1770 Annex 2) and loudness
+ * range (EBU Tech 3342) are features chosen at create (fmd_meter_create_ex, "True peak and loudness range" below); channel weights are
+ * 1.0 for L and R.  Arithmetic, restated in C by tests/cpp/meter_ref.c:
  *   design      host, double, host libm (fmd_meter_design); pi = 3.14159265358979323846:
  *                 pre-filter (high shelf): f0 = 1681.974450955533, G = 3.999843853973347 dB, Q = 0.7071752369554196
  *                   K = tan(pi * f0 / fs);  Vh = pow(10, G / 20);  Vb = pow(Vh, 0.4996667741545416);  a0 = 1 + K / Q + K * K
@@ -725,10 +726,10 @@ int fmd_meter_short_term(const fmd_meter_status* s, double* lufs);
 
 int fmd_meter_create(const fmd_meter_config* cfg, fmd_meter* out);
 int fmd_meter_destroy(fmd_meter m);
-/* everything of station `channel` (-1 = every station) as after create: counters, ring, filter states, histogram, peaks.  Waits for the
- * meter's earlier work */
+/* everything of station `channel` (-1 = every station) as after create: counters, ring, filter states, histogram, peaks, and with the
+ * features the r128 record, the true-peak history and the range histogram.  Waits for the meter's earlier work */
 int fmd_meter_reset(fmd_meter m, int channel);
-/* peak_call and peak_hold of station `channel` (-1 = every station) to 0; nothing else */
+/* peak_call and peak_hold (and tp_call, tp_hold) of station `channel` (-1 = every station) to 0; nothing else: the true-peak history stays */
 int fmd_meter_reset_peaks(fmd_meter m, int channel);
 /* meters n frames of every station.  d_in [C][in_stride][2] f32 on the device, 8-byte aligned; d_active: [C] uint8 on the device,
  * NULL = all: a station whose byte is 0 is skipped whole (no state, counter or peak of it changes).  n < 0, n > in_stride or
@@ -743,6 +744,63 @@ int fmd_meter_get_histogram(fmd_meter m, unsigned* hist);
  * valid until the next process call */
 int fmd_meter_status_dev(fmd_meter m, const fmd_meter_status** d_status);
 const char* fmd_meter_last_error(fmd_meter m);
+
+/* True peak and loudness range: the two other figures of EBU R 128, opt-in per meter.  Nothing above changes with them: fmd_meter_status,
+ * the histogram and every entry point keep their layout, meaning and values.  Arithmetic, restated in C by tests/cpp/meter_r128_ref.c:
+ *   tp design   host, double, host libm (fmd_meter_tp_design); pi as above, beta = 5.0:
+ *                 L = 4 for fs < 88200, 2 for 88200 <= fs < 176400, 1 otherwise;  T = 12 taps per phase;  N = L * T;  c = N / 2
+ *                 h[i] = sinc((i - c) / L) * I0(beta * sqrt(1 - ((i - c) / c)^2)) / I0(beta),  i = 0 ... N - 1
+ *                   sinc(0) = 1, sinc(x) = sin(pi * x) / (pi * x);  I0(x) = 1 + sum over k >= 1 of prod_{m <= k} (x / (2 m))^2, summed
+ *                   in k order until a term falls under 1e-18 of the sum
+ *                 phase 0 of h is the identity: the raw sample stands for it.  For p = 1 ... L - 1:
+ *                   g_p[k] = h[k * L + p], k = 0 ... 11, divided by (sum over k ascending, from +0, of g_p[k]), rounded to float
+ *   true peak   per (station, rail), fp32 (denormals kept), every multiply-add an explicit fmaf:
+ *                 y_p[n] = fmaf(g_p[11], x[n-11], ... fmaf(g_p[1], x[n-1], fmaf(g_p[0], x[n], +0.0f)))     k ascending, from +0
+ *                 tp = fmaxf(tp, fabsf(x[n]));  for p = 1 ... L - 1: tp = fmaxf(tp, fabsf(y_p[n]))        (a NaN leaves tp as it is)
+ *               x[n] for n < 0 is the station's history: zeros after create and reset, otherwise the last 11 frames metered.  tp_call
+ *               starts at 0 in every process call that meters the station; tp_hold = fmaxf(tp_hold, tp_call), cleared at create, reset and
+ *               reset_peaks (which leaves the history alone).  A maximum that never keeps a NaN does not depend on order, so tp_hold is
+ *               bit-identical however the frames are split into calls, and tp_hold >= peak_hold.  At L = 1 tp_* equal peak_*.
+ *   range       when sub-block g >= 29 completes, after E_g is stored (one short-term value per 100 ms):
+ *                 s = +0;  s += energy_ring[i % 30] for i = g - 29 ... g;  S = s / 30.0
+ *                 S not finite -> st_nonfinite++;  else S < edge[0] -> st_below++;  else range_hist[j]++ for the j with
+ *                 edge[j] <= S < edge[j + 1] (S >= edge[1000] -> j = 999).  Comparisons only; ordinary stores.
+ *   read-out    host, double, pure:
+ *                 fmd_meter_dbtp(peak) = 20 * log10((double)peak);  0 -> -inf
+ *                 fmd_meter_range    : n0 = sum of hist; n0 == 0 -> FMD_ERR_STATE.  Gamma = (sum over j ascending, from +0, of
+ *                                      (double)hist[j] * centre[j]) / (double)n0.  Keep the bins with centre[j] >= 0.01 * Gamma (the -20 LU
+ *                                      relative gate); n = their count.  Zero-based ranks r10 = floor(0.10 * (n - 1) + 0.5) and
+ *                                      r95 = floor(0.95 * (n - 1) + 0.5) over the kept values in ascending order fall in bins j10 and j95
+ *                                      (by cumulative count):  low = -70 + 0.1 * j10 + 0.05, high likewise, lra = (j95 - j10) / 10.0.
+ *               The bins quantise the range to 0.1 LU, against the +-1 LU of EBU Tech 3342. */
+#define FMD_METER_TRUE_PEAK 1u
+#define FMD_METER_RANGE     2u
+/* fmd_meter_create(cfg, out) == fmd_meter_create_ex(cfg, 0, out).  Unknown feature bits: FMD_ERR_ARG */
+int fmd_meter_create_ex(const fmd_meter_config* cfg, unsigned features, fmd_meter* out);
+int fmd_meter_features(fmd_meter m, unsigned* features);
+
+typedef struct {
+    int   L, taps_per_phase;          /* 4, 2 or 1; 12 */
+    float taps[3][12];                /* taps[p - 1][k] = g_p[k], phases p = 1 ... L - 1; unused rows are 0 */
+} fmd_meter_tp_design_t;
+/* host only; the fs rule of fmd_meter_design */
+int fmd_meter_tp_design(int fs, fmd_meter_tp_design_t* out);
+double fmd_meter_dbtp(float peak);
+
+/* one per station, 24 bytes: tp_call at byte 0, tp_hold 8, st_below 16, st_nonfinite 20.  The fields of a feature that is off stay 0 */
+typedef struct {
+    float    tp_call[2], tp_hold[2];  /* L, R: true peak of the last call that metered the station / since reset or reset_peaks */
+    unsigned st_below, st_nonfinite;  /* short-term values under -70 LUFS / non-finite */
+} fmd_meter_r128_status;
+/* out [C]; synchronises with the meter's work.  FMD_ERR_STATE on a meter that has neither feature */
+int fmd_meter_get_r128_status(fmd_meter m, fmd_meter_r128_status* out);
+/* as fmd_meter_status_dev */
+int fmd_meter_r128_status_dev(fmd_meter m, const fmd_meter_r128_status** d_out);
+/* hist [C][1000]: the short-term values' counts per 0.1 LU bin; FMD_ERR_STATE on a meter without FMD_METER_RANGE */
+int fmd_meter_get_range_histogram(fmd_meter m, unsigned* hist);
+/* host only, pure: one station's [1000] range histogram -> lra in LU, low / high = the 10th / 95th percentile in LUFS.  FMD_ERR_STATE
+ * when no bin survives the gates */
+int fmd_meter_range(const unsigned* hist, const fmd_meter_design_t* d, double* lra, double* low, double* high);
 
 #ifdef __cplusplus
 }
