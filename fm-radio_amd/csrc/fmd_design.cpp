@@ -109,3 +109,15 @@ void design_all(fmd_coeffs* k, int fs_baseband, const fmd_controls* c) {
 }
 
 }  // namespace fmd
+
+// (include/fmdemod.h; here, beside the designs it feeds, so that the host-only units stand without the library)
+void fmd_default_controls(fmd_controls* c) {
+    // reference Broadcast_FM_Demod_Controls defaults (broadcast_fm_demod.h:82-88) and the SetValue() calls of the
+    // constructor (broadcast_fm_demod.cpp:189,248,260)
+    c->audio_out = FMD_AUDIO_STEREO;
+    c->audio_stereo_mix_factor = 1.0f;
+    c->use_deemphasis = 0;
+    c->deemphasis_tus = 1;
+    c->lpr_cutoff_hz = 15000;
+    c->lmr_cutoff_hz = 15000;
+}

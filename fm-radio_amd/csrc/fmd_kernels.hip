@@ -748,9 +748,9 @@ template <int M, int TPX>
 struct PredecimGeomM {
     static constexpr int TP = TPX;                    // outputs per workgroup
     static constexpr int NT = TP / 256;               // 16 x 16 output tiles
-    static constexpr int SH = 8 - M;                  // the staged window starts SH samples early, on a multiple of 8 samples: 16-byte loads of u8 captures
+    static constexpr int SH = predecim_shift(M);      // the staged window starts SH samples early, on a multiple of 8 samples: 16-byte loads of u8 captures
     static constexpr int NB = M * TP + 64;            // input samples staged: w[j] = s[M n0 + M - 64 - SH + j];  A[m][t] = b[t - SH - M m]
-    static constexpr int KS = (64 + SH + 15 * M + 31) / 32;
+    static constexpr int KS = predecim_ksteps(M);
     static constexpr int SEG = 16 * M;                // elements between two columns' windows
     static constexpr int NEP = NB + 8 * (NB / SEG + 1);   // padded elements per array
     static constexpr int HIST = 64;
@@ -892,10 +892,10 @@ struct FrontPreGeom {
     static constexpr int NPH = 2112, NCOLS = NPH / 16;            // phases / columns per tile
     static constexpr int NSUB = U8 ? (M == 4 ? 2 : 4) : (M == 4 ? 4 : 6);
     static constexpr int CS = NCOLS / NSUB;                       // columns per sub-step
-    static constexpr int SH = 8 - M;
+    static constexpr int SH = predecim_shift(M);
     static constexpr int SEG = 16 * M;                            // input samples between two columns' windows
     static constexpr int NBS = SEG * CS + 64;                     // input samples staged per sub-step
-    static constexpr int KS = (64 + SH + 15 * M + 31) / 32;
+    static constexpr int KS = predecim_ksteps(M);
     static constexpr int NEP = NBS + 8 * (NBS / SEG + 1);         // padded elements per array (see PredecimGeomM)
     static constexpr int NH = U8 ? 1 : 2;
     static constexpr int NWD = NEP / 2;                           // words per array

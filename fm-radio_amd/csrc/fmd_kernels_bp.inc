@@ -61,7 +61,7 @@ struct ExtractGeomB {
 // 8 sixteen-byte slots apart, and with the Toeplitz band (neighbouring rows read overlapping addresses: broadcast) the instruction's lane
 // groups hit 14 different slots — conflict-free (DESIGN.md section 3).  Buffers::bp_tab per cut-off slot: L+R, L-R re, L-R im blocks;
 // Buffers::rds_bp_tab: RDS S0 block, then S1 [re hi][im hi].
-static constexpr int kBpPadL = 96, kBpTL = 448, kBpTabU4 = kBpTL * 2 / 16, kBpTabSlotU4 = 12 * kBpTabU4;
+static constexpr int kBpTabU4 = kBpTL * 2 / 16, kBpTabSlotU4 = kBpSlotTabs * kBpTabU4;     // (kBpPadL, kBpTL, the table counts: fmd_tables.h)
 static_assert(kBpTL * 2 % 256 == 128 && kBpTL >= kBpPadL + 4 + 32 * ExtractGeomB::KS + 8 && kBpPadL >= 32 + 4 * 14 + 8 && kBpPadL % 8 == 0, "tap table geometry");
 
 // sum over groups of 8 adjacent lanes (every lane of a group gets it)
@@ -88,7 +88,7 @@ __global__ __launch_bounds__(256, 4) void k_extract_bp(Dims d, int nt, const flo
                                                         const float* __restrict__ lmr_est_prev, int field_cur, int field_prev, float* __restrict__ rds_pow) {
     using G = ExtractGeomB;
     constexpr int TA = G::TA;
-    __shared__ __attribute__((aligned(256))) uint16_t tabs[18 * kBpTL];               // the station's tap tables: [family 0 .. 3][4 tables], then S1's two
+    __shared__ __attribute__((aligned(256))) uint16_t tabs[(kBpSlotTabs + kBpRdsTabs) * kBpTL];               // the station's tap tables: [family 0 .. 3][4 tables], then S1's two
     __shared__ __attribute__((aligned(16))) uint32_t win[4][2 * G::NBW];              // per wavefront: its tile's window as bf16 halves, two per word, [hi | lo]
     __shared__ float2 s_old[SPW][SPW == 1 ? 32 : 31];
     __shared__ float off_s[SPW];
@@ -125,20 +125,20 @@ __global__ __launch_bounds__(256, 4) void k_extract_bp(Dims d, int nt, const flo
 #pragma unroll
         for (int k = 0; k < kLmrInlineMax / kWave; k++) ev[k] = (lane + kWave * k < d.n_est) ? lmr_est_prev[(size_t)(c + wv) * d.n_est + lane + kWave * k] : 0.0f;
     }
-    uint4 em[6];                         // the block's first tile: this thread's 24 columns x (re, im) of S_old's matrix (fp16), row tid / 8
+    uint4 em[kBpEdgeU4];                         // the block's first tile: this thread's 24 columns x (re, im) of S_old's matrix (fp16), row tid / 8
     float4 qe, qe1;
     {
         const int2 slot = aud_idx[c];
         if (edge) {
             if (tid < 48) qe = *reinterpret_cast<const float4*>(fo_c0 - 188 + 4 * tid);
             if (SPW == 2 && two && tid < 48) qe1 = *reinterpret_cast<const float4*>(fo_c0 + (kFoPad + n) - 188 + 4 * tid);
-            if (tid < 248) {
-                const uint4* ep = bp_edge + ((size_t)slot.y * 248 + tid) * 6;
+            if (tid < kBpEdgeRows) {
+                const uint4* ep = bp_edge + ((size_t)slot.y * kBpEdgeRows + tid) * kBpEdgeU4;
 #pragma unroll
-                for (int k = 0; k < 6; k++) em[k] = ep[k];
+                for (int k = 0; k < kBpEdgeU4; k++) em[k] = ep[k];
             }
         }
-        constexpr int NU4 = 18 * kBpTabU4;
+        constexpr int NU4 = (kBpSlotTabs + kBpRdsTabs) * kBpTabU4;
 #pragma unroll
         for (int r = 0; r < (NU4 + 255) / 256; r++) {
             const int j = tid + 256 * r;
@@ -169,12 +169,12 @@ __global__ __launch_bounds__(256, 4) void k_extract_bp(Dims d, int nt, const flo
         if (sx) __syncthreads();         // (the first station's reads of the scratch)
         if (tid < 48) *reinterpret_cast<float4*>(wf32 + 4 * tid) = sx ? qe1 : qe;
         __syncthreads();
-        if (tid < 248) {
+        if (tid < kBpEdgeRows) {
             const float* wp = wf32 + 24 * (tid & 7);
             float ar = 0.0f, ai = 0.0f;
             typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
 #pragma unroll
-            for (int k = 0; k < 6; k++) {
+            for (int k = 0; k < kBpEdgeU4; k++) {
                 const float4 w4 = *reinterpret_cast<const float4*>(wp + 4 * k);
                 const uint32_t ew[4] = {em[k].x, em[k].y, em[k].z, em[k].w};
                 const float ws[4] = {w4.x, w4.y, w4.z, w4.w};

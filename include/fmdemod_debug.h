@@ -38,7 +38,7 @@ int fmd_selftest_atan2_small(const float* y, const float* x, float* out, uint8_t
  * kind 3: out = atan2(a, b) / 2 pi, the six-coefficient form of the discriminator and the pilot loop's phase detector. */
 int fmd_selftest_fast_math(int kind, const float* a, const float* b, float* out, size_t n);
 
-/* Host-only (no GPU needed): the tables of the tolerance mode's span-wise pilot PLL (fm-radio_amd/csrc/fmd_kernels.h PllSpanTab) as
+/* Host-only (no GPU needed): the tables of the tolerance mode's span-wise pilot PLL (fm-radio_amd/csrc/fmd_tables.h PllSpanTab) as
  * the library designs them for fs_baseband — w [5][128] weights of the held-frequency error sequence (rows: loop filter, integrator,
  * phase deviation at samples 41, 84, 127), s [5][8] weights of the state (lpf, I, e1, e2, r0), minv [3][4] cubic fit, misc[0] = the
  * quadrature factor, misc[1] = kappa.  tests/test_span_design.py checks them against an independent float64 restatement. */

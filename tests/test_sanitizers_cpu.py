@@ -1,11 +1,14 @@
 """CPU sanitizer run (SURVEY §4 "sanitizers on the CPU build"; never on the GPU box's device code): the oracle (oracle/fm_oracle.c),
-the library's host-side filter designer (fm-radio_amd/csrc/fmd_design.cpp) and the host-side drivers (group synchroniser, scraper
-writers) built with -fsanitize=address,undefined (`make -C oracle asan`) and fed the golden fixtures.  Any out-of-bounds access, use after
+the library's host-side filter designer (fm-radio_amd/csrc/fmd_design.cpp), the designers of the tolerance mode's tables
+(fmd_tables.cpp), the kernel-selection plan (fmd_plan.cpp) and the host-side drivers (group synchroniser, scraper writers) built with
+-fsanitize=address,undefined (`make -C oracle asan`) as stand-alone programs and fed the golden fixtures.  Any out-of-bounds access, use after
 free, leak, signed overflow or misaligned access aborts the run (-fno-sanitize-recover); the outputs must still be the fixtures'.
 
 The reference's own trouble spots on this path: a static lambda capture in its designer (src/dsp/filter_designer.cpp:235,288,345) and
 the re-blocking buffer's span arithmetic (src/utility/reconstruction_buffer.h:16-26) — the driver re-blocks ragged pieces the same way."""
 import ctypes as C
+import hashlib
+import json
 import os
 import subprocess
 from pathlib import Path
@@ -106,3 +109,19 @@ def test_kernel_selection_plan_under_sanitizers_equals_the_model(asan_build, tmp
     assert len(out) == len(cases) > 20_000
     for line, (c, m, nf, ne, fl, th, u) in zip(out, cases):
         assert tuple(map(int, line.split())) == M.plan(c, m, nf, ne, fl, th, bool(u)), (c, m, nf, ne, fl, th, u)
+
+
+def test_table_designers_under_sanitizers_reproduce_the_pinned_tables(asan_build, tmp_path):
+    """fm-radio_amd/csrc/fmd_tables.cpp with fmd_design.cpp, plain g++ (no HIP, no library), under the sanitizers: every table the tolerance mode
+    uploads — PilotFastTab, PllSpanTab, PllSparseTab with its wrap ties, the Toeplitz operand images, the 12 + 6 band-pass tap tables and the
+    block-edge matrix — at the three rates, with both audio cut-offs at 15, 12 and 9 kHz, byte for byte what the designers gave while they were
+    part of fmd_api.cpp (tests/golden/design_tables.json: SHA-256 per table, made from that code before it moved)."""
+    want = json.loads((ROOT / "tests" / "golden" / "design_tables.json").read_text())
+    out = tmp_path / "tables.bin"
+    records = [l.split() for l in _run([asan_build / "tables_main", out]).stdout.splitlines()]
+    blob = out.read_bytes()
+    got = [{"fs": int(fs), "table": name, "bytes": int(n), "sha256": hashlib.sha256(blob[int(off):int(off) + int(n)]).hexdigest()} for fs, name, off, n in records]
+    assert len(want["tables"]) == 21 and [(t["fs"], t["table"], t["bytes"]) for t in got] == [(t["fs"], t["table"], t["bytes"]) for t in want["tables"]]
+    differing = [(g["fs"], g["table"]) for g, w in zip(got, want["tables"]) if g["sha256"] != w["sha256"]]
+    assert not differing, f"first differing table: {differing[0]}; all: {differing}"
+    assert len(blob) == want["bytes"] == sum(t["bytes"] for t in got) and hashlib.sha256(blob).hexdigest() == want["sha256"]

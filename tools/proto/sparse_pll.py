@@ -36,7 +36,7 @@ KAPPA = -19000.0 * TS32 + 19.0 / 128.0
 
 
 def design_rows(b0, b1, a0):
-    """fmd_api.cpp design_pll_span in float64: rows (lpf_end, I_end, dev[N1], dev[N2], dev[L-1]) over v = (lpf, I, e1, e2, r0, eh[0..L-1])."""
+    """fmd_tables.cpp design_pll_span in float64: rows (lpf_end, I_end, dev[N1], dev[N2], dev[L-1]) over v = (lpf, I, e1, e2, r0, eh[0..L-1])."""
     NV = 5 + L
     def unit(i):
         v = np.zeros(NV); v[i] = 1.0; return v
