@@ -1,6 +1,7 @@
 // C ABI of libfmdemod.so (include/fmdemod.h): handle management, per-channel controls, device buffers and
-// the per-block kernel launch sequence.  Host side only; the kernels are in fmd_kernels.hip, the coefficient
-// design in fmd_design.cpp and the design of the tolerance mode's tables in fmd_tables.cpp (both without HIP).
+// the HIP side of the per-block kernel launch sequence.  Host side only; the kernels are in fmd_kernels.hip, the coefficient
+// design in fmd_design.cpp, the design of the tolerance mode's tables in fmd_tables.cpp and the block schedule — which stage goes on
+// which queue behind which events — in fmd_schedule.cpp (all three without HIP).
 // There is no CPU fallback: without a gfx950 device every call fails loudly.
 #include <hip/hip_runtime.h>
 
@@ -17,19 +18,12 @@
 #include "fmd_design.h"
 #include "fmd_kernels.h"
 #include "fmd_plan.h"
+#include "fmd_schedule.h"
 #include "fmd_tables.h"
 #include "fmdemod.h"
 #include "fmdemod_debug.h"
 
 using namespace fmd;
-
-// Stage placement: k_front on sF, k_pilot_power on sA, k_pilot_pll on sB, k_extract (+ k_lmr_phase) on sX, k_rds_sync on sR.
-// Blocks rotate through kSlots buffer slots and every stage waits only for its producer (HIP events), so in steady state
-// all stages run concurrently on different blocks.
-enum Stage { ST_FRONT = 0, ST_DEEMPH, ST_POWER, ST_PLL, ST_EXTRACT, ST_RDS, ST_PREDECIM, ST_COUNT };
-static const char* const kStageName[ST_COUNT] = {"k_front", "k_deemphasis+k_hilbert", "k_pilot_power", "k_pilot_pll", "k_extract", "k_rds_sync", "k_predecim"};
-// ... and of the tolerance mode's kernels, as they appear in rocprofv3 kernel traces
-static const char* const kStageNameFast[ST_COUNT] = {"k_front_mfma", "k_deemphasis", "k_pilot_power", "k_pll_sparse", "k_extract_bp", "k_rds_sync", "k_predecim_mfma"};
 
 struct ProfiledBlock { hipEvent_t t0[ST_COUNT], t1[ST_COUNT]; bool used[ST_COUNT]; };
 
@@ -46,9 +40,9 @@ struct fmd_handle_s {
     void* d_in = nullptr;                    // staging for the host-pointer entry points
     size_t d_in_bytes = 0;
     hipStream_t own_stream = nullptr;        // host-pointer entry points, uploads, resets
-    hipStream_t last_stream = nullptr;
-    hipStream_t sF = nullptr, sA = nullptr, sB = nullptr, sB2 = nullptr, sX = nullptr, sR = nullptr, sD = nullptr;   // sD: the optional de-emphasis stage
-    unsigned pll_seq = 0;                    // k_pilot_pll launches handed over per wavefront so far (0: hand-over by stream order)
+    hipStream_t last_stream = nullptr;       // the caller's stream of the newest block (unpipelined: where its stages ran)
+    hipStream_t sF = nullptr, sA = nullptr, sB = nullptr, sX = nullptr, sR = nullptr, sD = nullptr;   // the schedule's queues F A B X R D (Q_OWN is own_stream); sD: the optional de-emphasis stage
+    Schedule sched;                          // which stage goes on which queue behind which events (fmd_schedule.h); HipBackend below makes the calls
     // exact mode, Plan::pll_k_adaptive (above kPllK16MaxEff, up to kPllK16UnlockedMaxEff effective stations): the pilot-PLL kernel's lane count follows what is out of lock — 8 lanes a station while every
     // loop holds lock (fewest instructions beside the FIR kernels), 16 while some do not (a loop out of lock costs its wavefront ~1.8x, and
     // the kernel lasts as long as its slowest wavefront: 1.55 -> 1.12 ms a block with 16).  The kernel counts the wavefronts that ran out
@@ -59,42 +53,15 @@ struct fmd_handle_s {
     hipEvent_t ev_in = nullptr, ev_P[kSlots] = {}, ev_F[kSlots] = {}, ev_A[kSlots] = {}, ev_B[kSlots] = {}, ev_E[kSlots] = {}, ev_X[kSlots] = {};
     hipEvent_t ev_D[kSlots] = {};            // k_front done, de-emphasis stage may start
     hipEvent_t ev_C[kSlots] = {};            // fmd_release_outputs: the consumer of a slot's outputs has finished with them
-    bool consumer_pending[kSlots] = {};
-    bool slot_used[kSlots] = {};
-    bool last_block_deemph = false;          // the previous block went through the de-emphasis stage (stream sD)
     bool poisoned = false;                   // a block failed part-way: state is not the state after a whole number of blocks
     bool pipelined = true;
-    // Tolerance mode, fmd_submit_*: k_extract_bp shares k_front_mfma's stream and a block's extract + RDS stages are queued when the
-    // NEXT block is submitted (behind that block's front end) or when somebody asks for the outputs — see process_dev
-    bool lazy_extract = false;
-    // pll_pending: the block's pilot stage has not been queued either — it rides in the next block's front-end launch (k_front_mfma<FUSED>) or,
-    // where that is not possible (a start-up block, the getters' per-sample streams, a flush), goes in front of the extract stage on its own;
-    // front_dep: the event behind the stage that made the block's fm_out; pll_dep / pll_stream: where the pilot stage was queued (NULL event: same
-    // queue as the front end, nothing to wait for)
-    struct Deferred { bool active = false, pll_pending = false, front_cross = false, deemph = false; SlotRef ref{}; hipEvent_t pll_dep = nullptr, front_dep = nullptr; hipStream_t pll_stream = nullptr, front_stream = nullptr;
-                      int slot = 0; long block = 0; ProfiledBlock* pm = nullptr; bool prof_p = false, prof_x = false, prof_r = false; } deferred;
-    hipStream_t last_x_stream = nullptr;     // where the newest extract stage was queued, and the event behind it: consecutive blocks'
-    hipEvent_t last_x_event = nullptr;       // extract stages are ordered (L-R phase estimate), whichever of the two streams they take
-    hipStream_t last_p_stream = nullptr;     // where the newest pilot stage was queued and the event behind it: consecutive blocks' pilot stages run in
-    hipEvent_t last_p_event = nullptr;       // order (loop state), whichever queue each takes (its own, or the front end's); NULL: drained
-    hipEvent_t x_done[kSlots] = {};          // fires when the extract stage of the block in that slot has run (its timing event while it is being timed); NULL: drained
-    int warm_left = 0;                       // tolerance mode: blocks still inside some station's start-up transient (k_pll_span runs beside k_pll_sparse)
-    long n_blocks = 0;                       // blocks submitted since create/reset; slot = n_blocks % kSlots
-    int out_slot = 0;                        // slot holding the newest outputs (the newest block's; under fmd_set_output_lag: the newest QUEUED outputs)
-    int sub_slot = 0;                        // slot of the newest submitted block
-    bool have_out = false;                   // some block's output stages have been queued since create / reset
-    long out_block = -1;                     // ... and which block's (0 = the first since create / reset) the output views are
     long epoch = 0;                          // how often the block numbering restarted (fmd_reset, fmd_set_config ...): fmd_outputs_epoch
-    bool lag_outputs = false;                // fmd_set_output_lag
-    hipEvent_t ev_consumed = nullptr;        // fires when the newest block's input buffer has been read (fmd_wait_input)
     int device = 0;
     int bytes_cap = 0;
     std::string err;
     std::map<int, std::vector<float>> lpf_cache;  // cut-off Hz -> 128 taps
     std::map<int, int> img_slot;                  // FMD_FLAG_FAST_MATH: cut-off Hz -> slot of its operand image in aud_img (k_extract_bp)
     size_t img_capacity = 0;                      // slots allocated in aud_img
-    unsigned debug_skip = 0;                 // development knob FMD_DEBUG_SKIP_STAGES: bit (1 << Stage) = do not launch that stage (timing experiments only: outputs are garbage)
-    int profiling = 0;                       // 0 off, 1 every kernel of every block, 2 k_pilot_pll every block + the rest every 4th
     std::vector<ProfiledBlock*> marks;       // one per profiled block, drained by fmd_profile_read
 };
 
@@ -330,108 +297,95 @@ int zero_history(fmd_handle h, hipStream_t s) {
     if (b.pll_chain) HIP_TRY(h, hipMemsetAsync(b.pll_chain, 0, sizeof(unsigned) * ((size_t)h->ctx.plan.pll_waves + 1 + (size_t)d.C + 2), s));      // (and the body hints behind it)
     if (h->pll_unl_host) h->pll_unl_host[0] = h->pll_unl_host[1] = 0u;
     h->ctx.pll_unlocked_now = false; h->ctx.pll_launch_no = 0;
-    h->pll_seq = 0;
-    h->n_blocks = 0;
-    h->warm_left = h->ctx.fast ? (int)((8192 + d.n_fm_out - 1) / d.n_fm_out) : 0;     // kPllWarmSamples of every station's life
-    if (h->ctx.fast && dev_env("FMD_DEBUG_PLL_DENSE")) h->warm_left = 1 << 30;   // development knob: k_pll_span for every block (A/B against round 3's pilot stage)
-    h->deferred.active = false; h->last_x_event = nullptr; h->last_p_event = nullptr;
-    for (hipEvent_t& e : h->x_done) e = nullptr;
-    h->ev_consumed = nullptr;
-    h->out_slot = 0; h->sub_slot = 0; h->have_out = false; h->out_block = -1;
+    h->sched.reset();
     h->epoch++;
-    for (bool& u : h->slot_used) u = false;
-    for (bool& u : h->consumer_pending) u = false;
     h->poisoned = false;
     return FMD_OK;
 }
 
-// The extract + RDS stages of the block whose launch fmd_submit_* put off (tolerance mode).
-// behind_front (the next block has just been submitted): k_extract_bp goes on the FRONT END's stream.  The two throughput kernels
-// gain nothing from running side by side — together they took longer than one after the other (tools/r3_timeline.sh: 0.37 ms a block for
-// the pair against 0.14 + 0.17 ms alone; they share a CU's LDS and wave slots, and every hop between queues costs ~50 us) — so they take
-// turns on one queue, in the order front(k + 1), extract(k), front(k + 2), ...; by the time extract(k) is reached, the pilot loop of
-// block k has run on its own queue, as the RDS stages do.  Otherwise (somebody asks for the block's outputs before the next block is
-// there: fmd_wait_outputs, a getter, fmd_synchronize) it goes on the extract stream as in the exact mode, beside the next front end.
-// The pilot stage of the put-off block as a launch of its own on `sP`: the front end's queue, or the pilot queue as in the undeferred
-// arrangement (consecutive blocks' pilot stages must run in order: a block whose stage is queued at submission sends the put-off one ahead).
-int launch_deferred_pll(fmd_handle h, hipStream_t sP) {
-    auto& q = h->deferred;
-    if (!q.active || !q.pll_pending) return FMD_OK;
-    q.pll_pending = false;
-    if (h->last_p_event && h->last_p_stream != sP) HIP_TRY(h, hipStreamWaitEvent(sP, h->last_p_event, 0));
-    if (sP != h->sF || q.front_cross) HIP_TRY(h, hipStreamWaitEvent(sP, q.front_dep, 0));
-    if (sP != h->sF) {          // (see process_dev: the stage also writes the history in front of the next slot's rows)
-        const int nx = (q.slot + 1) % kSlots;
-        if (h->slot_used[nx] && h->x_done[nx]) HIP_TRY(h, hipStreamWaitEvent(sP, h->x_done[nx], 0));
+// The schedule's names as this handle's streams and events, and its four calls as the HIP runtime's.  caller: the stream the entry point was given
+// (Q_CALLER); d_iq / u8: the block the front end or the first decimator reads.
+struct HipBackend final : ScheduleBackend {
+    fmd_handle h;
+    hipStream_t caller;
+    const void* d_iq;
+    bool u8;
+    explicit HipBackend(fmd_handle h_, hipStream_t caller_ = nullptr, const void* d_iq_ = nullptr, bool u8_ = false) : h(h_), caller(caller_), d_iq(d_iq_), u8(u8_) {}
+    hipStream_t stream(Queue q) const {
+        switch (q) {
+            case Q_OWN: return h->own_stream;
+            case Q_F: return h->sF;
+            case Q_D: return h->sD;
+            case Q_A: return h->sA;
+            case Q_B: return h->sB;
+            case Q_X: return h->sX;
+            case Q_R: return h->sR;
+            default: return caller;
+        }
     }
-    SlotRef r = q.ref;
-    if (q.pm && q.prof_p) { r.t0 = q.pm->t0[ST_PLL]; r.t1 = q.pm->t1[ST_PLL]; q.pm->used[ST_PLL] = true; }
-    if (!r.t1) r.done = h->ev_B[q.slot];
-    q.pll_dep = r.t1 ? r.t1 : h->ev_B[q.slot];
-    q.pll_stream = sP;
-    hipError_t e = (h->debug_skip & (1u << ST_PLL)) ? hipEventRecord(q.pll_dep, sP) : launch_stage_pll(h->ctx, r, sP);
-    if (e != hipSuccess) { h->poisoned = true; return fail(h, FMD_ERR_DEVICE, "k_pll_sparse launch: %s", hipGetErrorString(e)); }
-    h->last_p_stream = sP; h->last_p_event = q.pll_dep;
-    return FMD_OK;
+    hipEvent_t event(Event e) const {
+        switch (e.kind) {
+            case EV_IN: return h->ev_in;
+            case EV_P: return h->ev_P[e.slot];
+            case EV_F: return h->ev_F[e.slot];
+            case EV_D: return h->ev_D[e.slot];
+            case EV_A: return h->ev_A[e.slot];
+            case EV_B: return h->ev_B[e.slot];
+            case EV_E: return h->ev_E[e.slot];
+            case EV_X: return h->ev_X[e.slot];
+            case EV_C: return h->ev_C[e.slot];
+            case EV_T0: return h->marks[(size_t)e.slot]->t0[e.stage];
+            case EV_T1: h->marks[(size_t)e.slot]->used[e.stage] = true; return h->marks[(size_t)e.slot]->t1[e.stage];   // (a stop event is only ever looked up for a stage that is being timed)
+            default: return nullptr;
+        }
+    }
+    SlotRef ref(const Launch& l) const { return SlotRef{l.buf, l.par, event(l.t0), event(l.t1), event(l.done), l.seq, l.warm}; }
+    int wait(Queue q, Event e) override { return (int)hipStreamWaitEvent(stream(q), event(e), 0); }
+    int record(Event e, Queue q) override { return (int)hipEventRecord(event(e), stream(q)); }
+    int launch(Stage st, Queue q, const Launch& l, const Launch* ride) override {
+        const SlotRef r = ref(l);
+        hipStream_t s = stream(q);
+        switch (st) {
+            case ST_PREDECIM: return (int)launch_stage_predecim(h->ctx, r, d_iq, u8, s);
+            case ST_FRONT: {
+                const SlotRef rider = ride ? ref(*ride) : SlotRef{};
+                return (int)launch_stage_front(h->ctx, r, d_iq, u8, s, ride ? &rider : nullptr);
+            }
+            case ST_DEEMPH: return (int)launch_stage_deemph(h->ctx, r, s);
+            case ST_POWER: return (int)launch_stage_power(h->ctx, r, s);
+            case ST_PLL: return (int)launch_stage_pll(h->ctx, r, s);
+            case ST_EXTRACT: return (int)launch_stage_extract(h->ctx, r, s);
+            case ST_RDS: return (int)launch_stage_rds(h->ctx, r, s);
+            default: return (int)hipErrorInvalidValue;
+        }
+    }
+    int copy_pll_hint(Queue q) override {
+        return (int)hipMemcpyAsync(h->pll_unl_host, h->ctx.b.pll_hint + h->ctx.d.C, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream(q));
+    }
+};
+
+// what a call into the schedule returned: a runtime error leaves stages half queued
+int sched_rc(fmd_handle h, int e) {
+    if (!e) return FMD_OK;
+    h->poisoned = true;
+    return fail(h, FMD_ERR_DEVICE, "%s: %s", h->sched.failed_what(), hipGetErrorString((hipError_t)e));
 }
 
-int launch_deferred(fmd_handle h, bool behind_front) {
-    auto& q = h->deferred;
-    if (!q.active) return FMD_OK;
-    hipStream_t sXq = behind_front ? h->sF : h->sX, sR = h->sR;
-    if (h->consumer_pending[q.slot]) {       // fmd_release_outputs: a consumer still reads this slot's old outputs
-        HIP_TRY(h, hipStreamWaitEvent(sXq, h->ev_C[q.slot], 0));
-        HIP_TRY(h, hipStreamWaitEvent(sR, h->ev_C[q.slot], 0));
-        h->consumer_pending[q.slot] = false;
-    }
-    if (h->last_x_event && h->last_x_stream != sXq) HIP_TRY(h, hipStreamWaitEvent(sXq, h->last_x_event, 0));
-    { int rc = launch_deferred_pll(h, behind_front ? h->sF : h->sB); if (rc) return rc; }
-    q.active = false;
-    if (q.pll_dep && q.pll_stream != sXq) HIP_TRY(h, hipStreamWaitEvent(sXq, q.pll_dep, 0));
-    hipEvent_t dep;
-    {
-        SlotRef r = q.ref;
-        if (q.pm && q.prof_x) { r.t0 = q.pm->t0[ST_EXTRACT]; r.t1 = q.pm->t1[ST_EXTRACT]; q.pm->used[ST_EXTRACT] = true; }
-        if (!r.t1) r.done = h->ev_E[q.slot];
-        dep = r.t1 ? r.t1 : h->ev_E[q.slot];
-        hipError_t e = (h->debug_skip & (1u << ST_EXTRACT)) ? hipEventRecord(dep, sXq) : launch_stage_extract(h->ctx, r, sXq);
-        if (e != hipSuccess) { h->poisoned = true; return fail(h, FMD_ERR_DEVICE, "k_extract launch: %s", hipGetErrorString(e)); }
-        h->last_x_stream = sXq; h->last_x_event = dep; h->x_done[q.slot] = dep;
-    }
-    HIP_TRY(h, hipStreamWaitEvent(sR, dep, 0));
-    {
-        SlotRef r = q.ref;
-        if (q.pm && q.prof_r) { r.t0 = q.pm->t0[ST_RDS]; r.t1 = q.pm->t1[ST_RDS]; q.pm->used[ST_RDS] = true; }
-        if (!r.t1) r.done = h->ev_X[q.slot];
-        dep = r.t1 ? r.t1 : h->ev_X[q.slot];
-        hipError_t e = (h->debug_skip & (1u << ST_RDS)) ? hipEventRecord(dep, sR) : launch_stage_rds(h->ctx, r, sR);
-        if (e != hipSuccess) { h->poisoned = true; return fail(h, FMD_ERR_DEVICE, "k_rds_sync launch: %s", hipGetErrorString(e)); }
-    }
-    if (dep != h->ev_X[q.slot]) HIP_TRY(h, hipEventRecord(h->ev_X[q.slot], sR));
-    h->out_slot = q.slot; h->have_out = true; h->out_block = q.block;
-    return FMD_OK;
-}
-
-// A caller is about to use the device views of the newest outputs (fmd_wait_outputs, fmd_release_outputs, the *_dev getters).
-// Default: they are the newest BLOCK's — if its extract stage is still put off it is queued now, on the extract stream, and from here on
-// the handle queues every block's stages at once (such a caller asks after every block: taking turns on the front end's queue would
-// stall that queue for the length of the pilot loop each time).  fmd_set_output_lag: nothing is forced, the views are the newest queued ones.
+// A caller is about to use the device views of the newest outputs (fmd_wait_outputs, fmd_release_outputs, the *_dev getters): Schedule::outputs_wanted
 int outputs_wanted(fmd_handle h) {
-    if (h->lag_outputs || !h->deferred.active) return FMD_OK;
+    if (!h->sched.outputs_put_off()) return FMD_OK;
     HIP_TRY(h, hipSetDevice(h->device));        // (the *_dev getters reach this without one: launches follow)
-    h->lazy_extract = false;
-    return launch_deferred(h, false);
+    HipBackend be(h);
+    return sched_rc(h, h->sched.outputs_wanted(be));
 }
 
 int sync_all(fmd_handle h) {
     HIP_TRY(h, hipSetDevice(h->device));
-    { int rc = launch_deferred(h, true); if (rc) return rc; }    // (everything drains: the front end's queue is as good as any)
-    for (hipStream_t st : {h->sF, h->sD, h->sA, h->sB, h->sB2, h->sX, h->sR, h->own_stream}) if (st) HIP_TRY(h, hipStreamSynchronize(st));
-    h->last_x_event = nullptr;        // (everything has run: no order left to keep; a timed block's events are about to be freed)
-    h->last_p_event = nullptr;
-    for (hipEvent_t& e : h->x_done) e = nullptr;
-    if (!h->pipelined && h->n_blocks > 0) HIP_TRY(h, hipStreamSynchronize(h->last_stream));
-    if (h->ctx.plan.pll_chained && h->pll_seq) {   // the hand-over watchdog of k_pilot_pll
+    { HipBackend be(h); int rc = sched_rc(h, h->sched.flush(true, be)); if (rc) return rc; }    // (everything drains: the front end's queue is as good as any)
+    for (hipStream_t st : {h->sF, h->sD, h->sA, h->sB, h->sX, h->sR, h->own_stream}) if (st) HIP_TRY(h, hipStreamSynchronize(st));
+    h->sched.drained();
+    if (!h->pipelined && h->sched.n_blocks() > 0) HIP_TRY(h, hipStreamSynchronize(h->last_stream));
+    if (h->ctx.plan.pll_chained && h->sched.pll_seq()) {   // the hand-over watchdog of k_pilot_pll
         unsigned timed_out = 0;
         HIP_TRY(h, hipMemcpy(&timed_out, h->ctx.b.pll_chain + h->ctx.plan.pll_waves, sizeof(unsigned), hipMemcpyDeviceToHost));
         if (timed_out) {
@@ -460,174 +414,24 @@ int process_dev(fmd_handle h, const InT* d_iq, int n_channels, int n_samples, vo
         if (!rc) rc = upload_controls(h, h->own_stream);
         if (rc) return rc;
     }
-    const int slot = (int)(h->n_blocks % kSlots);
-    SlotRef ref{slot, (int)(h->n_blocks & 1), nullptr, nullptr};
-    ref.warm = (h->ctx.fast && h->warm_left > 0) ? (h->warm_left >= (1 << 29) ? 2 : 1) : 0;
-    const bool u8 = sizeof(InT) == 2;
-    const bool pipe = h->pipelined;
-    if (!pipe) ordered = true;                     // every stage runs on `s` itself
-    hipStream_t sF = pipe ? h->sF : s, sA = pipe ? h->sA : s, sX = pipe ? h->sX : s, sR = pipe ? h->sR : s;
-    const bool lazy = pipe && h->lazy_extract && !ordered;
-    // consecutive blocks' PLL launches alternate between two streams when they hand over per wavefront (fmd_kernels.hip)
-    const bool chained = pipe && h->ctx.plan.pll_chained;
-    hipStream_t sB = pipe ? ((chained && (h->n_blocks & 1)) ? h->sB2 : h->sB) : s;
-    ProfiledBlock* pm = nullptr;
-    if (h->profiling) {
-        pm = new ProfiledBlock();
+    BlockFacts f;
+    f.ordered = ordered; f.have_stream = s != nullptr;
+    f.any_deemph = h->ctx.any_deemph != 0; f.deemph_in_tile = h->ctx.deemph_in_tile != 0; f.split_front = h->ctx.split_front != 0;
+    if (h->sched.profiling()) {
+        ProfiledBlock* pm = new ProfiledBlock();
         for (int i = 0; i < ST_COUNT; i++) { pm->used[i] = false; HIP_TRY(h, hipEventCreate(&pm->t0[i])); HIP_TRY(h, hipEventCreate(&pm->t1[i])); }
         h->marks.push_back(pm);
+        f.prof_block = (int)h->marks.size() - 1;
     }
-    // event bracketing perturbs the pipeline it measures (extra queue packets between dependent kernels): mode 2 keeps it
-    // on the dominant kernel and samples the others
-    // mode 3 samples: every stage of every 4th block, plus the PLL stage of the block behind it (for the hand-over gap)
-    auto prof_stage = [&](int st) {
-        if (h->profiling == 3) return (h->n_blocks & 3) == 0 || (st == ST_PLL && (h->n_blocks & 3) == 1);
-        return h->profiling == 1 || st == ST_PLL || (h->n_blocks & 3) == 0;
-    };
-    // The event that orders the next stage behind this one rides on the stage's last dispatch packet (SlotRef::done).  A
-    // stage that is being timed already carries its stop event there: the next stage then waits on that one (dep).
-    hipEvent_t dep = nullptr;
-    auto run = [&](Stage st, hipStream_t on, hipError_t (*fn)(const LaunchCtx&, SlotRef, hipStream_t), hipEvent_t done) -> hipError_t {
-        SlotRef r = ref;
-        if (pm && prof_stage(st)) { r.t0 = pm->t0[st]; r.t1 = pm->t1[st]; pm->used[st] = true; }
-        if (pipe && !r.t1) r.done = done;
-        if (st == ST_PLL && chained) r.seq = ++h->pll_seq;
-        dep = r.t1 ? r.t1 : done;
-        if (h->debug_skip & (1u << st)) return pipe ? hipEventRecord(dep, on) : hipSuccess;
-        return fn(h->ctx, r, on);
-    };
-    hipError_t e = hipSuccess;
     // from here on kernels are queued and host-side counters advance: a failure leaves the state between two blocks
     struct Poison { fmd_handle h; bool armed = true; ~Poison() { if (armed) h->poisoned = true; } } poison{h};
-    // fmd_release_outputs: the writers of this slot's output views wait for the consumer that still reads the old contents
-    if (h->consumer_pending[slot] && !lazy) {
-        HIP_TRY(h, hipStreamWaitEvent(sX, h->ev_C[slot], 0));
-        if (sR != sX) HIP_TRY(h, hipStreamWaitEvent(sR, h->ev_C[slot], 0));
-        h->consumer_pending[slot] = false;
-    }
-    // The first decimator (1.024 / 2.048 MSa/s) gets a stream of its own when the PLL launches do not need own_stream: it then
-    // works on block b+1 while k_front works on block b (back to back on one stream the two were the longest stage)
-    const bool fused_pre = front_takes_capture(h->ctx);      // (tolerance mode: one kernel, k_front_pre_mfma)
-    const bool predecim = h->ctx.d.m > 1 && !fused_pre;
-    hipStream_t sP = (pipe && h->ctx.d.m > 1 && !chained) ? h->own_stream : sF;
-    // Deferred schedule at 1.024 / 2.048 MSa/s: the front end (with the previous block's pilot stage riding it) follows the first
-    // decimator on that queue, and the extract stages have the front end's queue to themselves: two queues that each run ahead,
-    // instead of one on which k_extract_bp and the front end take turns while the decimator works beside both.
-    hipStream_t sFq = (lazy && h->ctx.d.m > 1 && sP != sF && h->ctx.fast) ? sP : sF;
-    hipStream_t s_first = predecim ? sP : sFq;     // the stream of the stage that reads the caller's input
-    if (pipe) {
-        // input is ready once everything queued so far on the caller's stream has run
-        if (ordered || s) {
-            HIP_TRY(h, hipEventRecord(h->ev_in, s));
-            HIP_TRY(h, hipStreamWaitEvent(s_first, h->ev_in, 0));
-        }
-        // WAR: this slot's fm_in / fm_out_iq / pilot / pll_dt were last read by the stages of the block kSlots blocks ago
-        if (h->slot_used[slot]) {
-            HIP_TRY(h, hipStreamWaitEvent(sF, h->ev_X[slot], 0));
-            if (sP != sF) HIP_TRY(h, hipStreamWaitEvent(sP, h->ev_X[slot], 0));
-        }
-    }
-    // the block after the last de-emphasised one: k_front maintains the Hilbert history (fo_tail) again and must not overwrite
-    // what the previous block's k_hilbert, on its own stream, is still reading
-    if (pipe && !h->ctx.any_deemph && h->last_block_deemph) HIP_TRY(h, hipStreamWaitEvent(sFq, h->ev_F[h->sub_slot], 0));
-    hipEvent_t input_done = nullptr;               // fires when the caller's buffer has been consumed
-    if (predecim) {
-        SlotRef r = ref;
-        if (pm && prof_stage(ST_PREDECIM)) { r.t0 = pm->t0[ST_PREDECIM]; r.t1 = pm->t1[ST_PREDECIM]; pm->used[ST_PREDECIM] = true; }
-        if (pipe && !r.t1) r.done = h->ev_P[slot];
-        input_done = r.t1 ? r.t1 : h->ev_P[slot];
-        e = launch_stage_predecim(h->ctx, r, d_iq, u8, sP);
-        if (e != hipSuccess) return fail(h, FMD_ERR_DEVICE, "k_predecim launch: %s", hipGetErrorString(e));
-        if (pipe && sP != sFq) HIP_TRY(h, hipStreamWaitEvent(sFq, input_done, 0));
-    }
-    {
-        SlotRef r = ref;
-        if (pm && prof_stage(ST_FRONT)) { r.t0 = pm->t0[ST_FRONT]; r.t1 = pm->t1[ST_FRONT]; pm->used[ST_FRONT] = true; }
-        hipEvent_t front_done = h->ctx.any_deemph ? h->ev_D[slot] : h->ev_F[slot];
-        if (pipe && !r.t1) r.done = front_done;
-        dep = r.t1 ? r.t1 : front_done;
-        // the previous block's pilot stage, put off with its extract stage: as the first workgroups of this launch
-        const SlotRef* ride = nullptr;
-        auto& q = h->deferred;
-        if (lazy && q.active && q.pll_pending && !q.ref.warm && !q.deemph && q.front_stream == sFq && !h->ctx.any_deemph && !h->ctx.b.fm_out_iq[q.slot] &&
-            !(h->debug_skip & ((1u << ST_PLL) | (1u << ST_FRONT)))) {
-            ride = &q.ref;
-            q.pll_pending = false; q.pll_dep = (sFq != sF) ? dep : nullptr; q.pll_stream = sFq;
-            if (h->last_p_event && h->last_p_stream != sFq) HIP_TRY(h, hipStreamWaitEvent(sFq, h->last_p_event, 0));
-            h->last_p_stream = sFq; h->last_p_event = dep;          // (the launch's own event)
-        }
-        if (h->debug_skip & (1u << ST_FRONT)) e = pipe ? hipEventRecord(dep, sFq) : hipSuccess;
-        else e = launch_stage_front(h->ctx, r, d_iq, u8, sFq, ride);
-    }
-    if (e != hipSuccess) return fail(h, FMD_ERR_DEVICE, "k_front launch: %s", hipGetErrorString(e));
-    hipEvent_t front_dep = dep;                    // k_front itself: the caller's buffer (256 kSa/s captures) has been consumed
-    if (h->ctx.any_deemph) {
-        // the optional de-emphasis IIR + Hilbert FIR: a pipeline stage of its own (stream sD), so that k_front of the next block
-        // runs beside it — in k_front's stream the two made the front end the longest stage (+25 % on the step)
-        hipStream_t sDe = pipe ? h->sD : s;
-        if (pipe) HIP_TRY(h, hipStreamWaitEvent(sDe, dep, 0));
-        if ((e = run(ST_DEEMPH, sDe, launch_stage_deemph, h->ev_F[slot])) != hipSuccess)
-            return fail(h, FMD_ERR_DEVICE, "de-emphasis launch: %s", hipGetErrorString(e));
-    }
-    if (pipe && ordered) HIP_TRY(h, hipStreamWaitEvent(s, input_done ? input_done : front_dep, 0));   // the caller may reuse `iq` in stream order after this call
-    if (pipe) {
-        // fmd_wait_input: an event that outlives this call (a timed stage's stop event belongs to the profiling marks)
-        hipEvent_t persistent = predecim ? h->ev_P[slot] : (h->ctx.any_deemph ? h->ev_D[slot] : h->ev_F[slot]);
-        if ((input_done ? input_done : front_dep) != persistent) HIP_TRY(h, hipEventRecord(persistent, predecim ? sP : sFq));
-        h->ev_consumed = persistent;
-    }
-    if (h->ctx.plan.pll_k_adaptive) {
+    if (h->ctx.plan.pll_k_adaptive) {      // (the copy that brings the two words back: Schedule::submit, every other block)
         const unsigned done = reinterpret_cast<volatile unsigned*>(h->pll_unl_host)[1], heavy = reinterpret_cast<volatile unsigned*>(h->pll_unl_host)[0];
         h->ctx.pll_unlocked_now = heavy != 0u && (heavy > done || done - heavy < 8u);      // (heavy > done: the launch that is still running has such wavefronts)
         h->ctx.pll_launch_no++;
-        // (no ordering against the PLL launches: both words only grow, whichever values the copy finds will do)
-        if ((h->n_blocks & 1) == 0) HIP_TRY(h, hipMemcpyAsync(h->pll_unl_host, h->ctx.b.pll_hint + h->ctx.d.C, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, sA));
     }
-    if (!h->ctx.fast) {   // (FMD_FLAG_FAST_MATH: the pilot peak filter runs inside the PLL kernel, there is no power pass)
-        if (pipe) HIP_TRY(h, hipStreamWaitEvent(sA, dep, 0));
-        if ((e = run(ST_POWER, sA, launch_stage_power, h->ev_A[slot])) != hipSuccess) return fail(h, FMD_ERR_DEVICE, "k_pilot_power launch: %s", hipGetErrorString(e));
-    }
-    const hipEvent_t fm_out_dep = dep;              // behind this event the block's fm_out is complete
-    const bool fm_out_cross = h->ctx.any_deemph != 0 || sFq != sF;
-    const bool pll_now = !lazy;
-    if (pll_now) {
-    { int rc = launch_deferred_pll(h, sB); if (rc) return rc; }        // (the put-off block's pilot stage first)
-    if (pipe) HIP_TRY(h, hipStreamWaitEvent(sB, dep, 0));
-    // Tolerance mode: the pilot stage of block k also writes the history in front of the NEXT slot's rows (fm_out tail, last span's cubic),
-    // which the extract stage of the block that last used that slot (k - 5) reads.  On the deferred schedule that stage sits ahead on
-    // the front end's queue; otherwise (fmd_process_*, small batches, a consumer holding outputs back) nothing else orders the two.
-    if (pipe && h->ctx.fast) {
-        const int nx = (slot + 1) % kSlots;
-        if (h->slot_used[nx] && h->x_done[nx]) HIP_TRY(h, hipStreamWaitEvent(sB, h->x_done[nx], 0));
-    }
-    if (pipe && h->ctx.fast && h->last_p_event && h->last_p_stream != sB) HIP_TRY(h, hipStreamWaitEvent(sB, h->last_p_event, 0));
-    if ((e = run(ST_PLL, sB, launch_stage_pll, h->ev_B[slot])) != hipSuccess) return fail(h, FMD_ERR_DEVICE, "k_pilot_pll launch: %s", hipGetErrorString(e));
-    if (pipe && h->ctx.fast) { h->last_p_stream = sB; h->last_p_event = dep; }
-    }
-    // the previous block's extract + RDS stages, if fmd_submit_* put them off: behind this block's front end (launch_deferred)
-    { int rc = launch_deferred(h, true); if (rc) return rc; }
-    if (lazy) {
-        auto& q = h->deferred;
-        q.active = true; q.pll_pending = !pll_now; q.front_cross = fm_out_cross; q.deemph = h->ctx.any_deemph != 0; q.front_stream = sFq; q.ref = ref; q.pll_dep = pll_now ? dep : nullptr; q.pll_stream = pll_now ? sB : nullptr; q.front_dep = fm_out_dep;
-        q.slot = slot; q.block = h->n_blocks; q.pm = pm;
-        q.prof_p = pm && prof_stage(ST_PLL); q.prof_x = pm && prof_stage(ST_EXTRACT); q.prof_r = pm && prof_stage(ST_RDS);
-    } else {
-        if (pipe) HIP_TRY(h, hipStreamWaitEvent(sX, dep, 0));
-        if (pipe && h->last_x_event && h->last_x_stream != sX) HIP_TRY(h, hipStreamWaitEvent(sX, h->last_x_event, 0));
-        // the extract stage's event fires behind k_extract itself: k_rds_sync does not need k_lmr_phase (same stream, behind it)
-        if ((e = run(ST_EXTRACT, sX, launch_stage_extract, h->ev_E[slot])) != hipSuccess) return fail(h, FMD_ERR_DEVICE, "k_extract launch: %s", hipGetErrorString(e));
-        if (pipe) { h->last_x_stream = sX; h->last_x_event = dep; h->x_done[slot] = dep; }
-        if (pipe) HIP_TRY(h, hipStreamWaitEvent(sR, dep, 0));
-        if ((e = run(ST_RDS, sR, launch_stage_rds, h->ev_X[slot])) != hipSuccess) return fail(h, FMD_ERR_DEVICE, "k_rds_sync launch: %s", hipGetErrorString(e));
-        // ev_X outlives this call (slot reuse, fmd_wait_outputs): when the dispatch carried a timing event instead, record it
-        if (pipe && dep != h->ev_X[slot]) HIP_TRY(h, hipEventRecord(h->ev_X[slot], sR));
-    }
-    h->last_block_deemph = h->ctx.any_deemph != 0;
-    h->slot_used[slot] = true;
-    h->sub_slot = slot;
-    if (!lazy) { h->out_slot = slot; h->have_out = true; h->out_block = h->n_blocks; }
-    h->n_blocks++;
-    if (h->warm_left > 0) h->warm_left--;
+    HipBackend be(h, s, d_iq, sizeof(InT) == 2);
+    { int rc = sched_rc(h, h->sched.submit(f, be)); if (rc) return rc; }
     if (h->deemph_linger) { h->deemph_linger = false; h->ctx.any_deemph = 0; }
     h->last_stream = s;
     poison.armed = false;
@@ -734,7 +538,6 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
         hipError_t e = hipStreamCreateWithFlags(st, hipStreamNonBlocking);
         if (e != hipSuccess) return bail(fail(h, FMD_ERR_DEVICE, "stream: %s", hipGetErrorString(e)));
     }
-    h->sB2 = h->own_stream;
 
     h->pipelined = (cfg->flags & FMD_FLAG_NO_PIPELINE) == 0;
     if (h->pipelined) warn_hw_queues_once();
@@ -755,8 +558,6 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
     h->ctx.keep_taps = (cfg->flags & FMD_FLAG_KEEP_TAPS) ? 1 : 0;
     h->ctx.rds_decode = (cfg->flags & FMD_FLAG_RDS_DECODE) ? 1 : 0;
     h->ctx.fast = (cfg->flags & FMD_FLAG_FAST_MATH) ? 1 : 0;
-    if (const char* e = dev_env("FMD_DEBUG_SKIP_STAGES")) h->debug_skip = (unsigned)strtoul(e, nullptr, 0);   // development knob
-    h->lazy_extract = h->ctx.plan.lazy_capable;
 
     fmd_controls def;
     fmd_default_controls(&def);
@@ -861,6 +662,13 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
         else h->pll_unl_host[0] = h->pll_unl_host[1] = 0u;
     }
     if (rc) return bail(rc);
+    {
+        ScheduleConfig sc;
+        sc.fast = fast; sc.pipelined = h->pipelined; sc.iq_streams = streams; sc.m = d.m; sc.n_fm_out = d.n_fm_out;
+        sc.warm_forever = dev_env("FMD_DEBUG_PLL_DENSE") != nullptr;   // development knob: k_pll_span for every block (A/B against round 3's pilot stage)
+        if (const char* e = dev_env("FMD_DEBUG_SKIP_STAGES")) sc.debug_skip = (unsigned)strtoul(e, nullptr, 0);   // development knob
+        h->sched.init(sc, &h->ctx.plan);
+    }
     rc = zero_history(h, h->own_stream);
     if (!rc) rc = upload_controls(h, h->own_stream);
     if (rc) return bail(rc);
@@ -954,10 +762,9 @@ int fmd_submit_u8_dev(fmd_handle h, const uint8_t* d_iq, int n_channels, int n_s
 }
 int fmd_wait_input(fmd_handle h, void* stream) {
     if (!h) return FMD_ERR_ARG;
-    if (!h->pipelined || h->n_blocks == 0 || !h->ev_consumed) return FMD_OK;   // unpipelined: the read is already ordered on the submitting stream
     HIP_TRY(h, hipSetDevice(h->device));
-    HIP_TRY(h, hipStreamWaitEvent(static_cast<hipStream_t>(stream), h->ev_consumed, 0));
-    return FMD_OK;
+    HipBackend be(h, static_cast<hipStream_t>(stream));
+    return sched_rc(h, h->sched.wait_input(be));
 }
 int fmd_process_cf32_host(fmd_handle h, const float* iq, int n_channels, int n_samples) {
     return process_host<float2>(h, reinterpret_cast<const float2*>(iq), n_channels, n_samples);
@@ -970,8 +777,7 @@ int fmd_set_output_lag(fmd_handle h, int on) {
     if (!h) return FMD_ERR_ARG;
     int rc = sync_all(h);
     if (rc) return rc;
-    h->lag_outputs = on != 0;
-    h->lazy_extract = h->ctx.plan.lazy_capable;        // (a caller that asked for every block's outputs at once had switched it off)
+    h->sched.set_output_lag(on != 0);
     return FMD_OK;
 }
 
@@ -979,7 +785,7 @@ int fmd_outputs_block(fmd_handle h, long* block) {
     if (!h || !block) return FMD_ERR_ARG;
     int rc = outputs_wanted(h);
     if (rc) return rc;
-    *block = h->have_out ? h->out_block : -1;
+    *block = h->sched.have_out() ? h->sched.out_block() : -1;
     return FMD_OK;
 }
 
@@ -996,40 +802,33 @@ int fmd_synchronize(fmd_handle h) {
 
 int fmd_wait_outputs(fmd_handle h, void* stream) {
     if (!h) return FMD_ERR_ARG;
-    if (!h->pipelined || h->n_blocks == 0) return FMD_OK;   // unpipelined: the outputs are already ordered on the caller's stream
     HIP_TRY(h, hipSetDevice(h->device));
-    { int rc = outputs_wanted(h); if (rc) return rc; }
-    if (!h->have_out) return FMD_OK;                        // (fmd_set_output_lag before the second block: nothing queued yet)
-    HIP_TRY(h, hipStreamWaitEvent(static_cast<hipStream_t>(stream), h->ev_X[h->out_slot], 0));
-    return FMD_OK;
+    HipBackend be(h, static_cast<hipStream_t>(stream));
+    return sched_rc(h, h->sched.wait_outputs(be));
 }
 
 int fmd_release_outputs(fmd_handle h, void* stream) {
     if (!h) return FMD_ERR_ARG;
-    if (h->n_blocks == 0) return FMD_OK;
     HIP_TRY(h, hipSetDevice(h->device));
-    { int rc = outputs_wanted(h); if (rc) return rc; }
-    if (!h->have_out) return FMD_OK;
-    HIP_TRY(h, hipEventRecord(h->ev_C[h->out_slot], static_cast<hipStream_t>(stream)));
-    h->consumer_pending[h->out_slot] = true;
-    return FMD_OK;
+    HipBackend be(h, static_cast<hipStream_t>(stream));
+    return sched_rc(h, h->sched.release_outputs(be));
 }
 
 int fmd_audio_dev(fmd_handle h, const float** d_audio) {
     if (!h || !d_audio) return FMD_ERR_ARG;
     { int rc = outputs_wanted(h); if (rc) return rc; }
-    *d_audio = h->ctx.b.audio[h->out_slot];
+    *d_audio = h->ctx.b.audio[h->sched.out_slot()];
     return FMD_OK;
 }
 
 int fmd_audio_pcm16_dev(fmd_handle h, int16_t* d_pcm, void* stream) {
     if (!h || !d_pcm) return FMD_ERR_ARG;
-    if (h->n_blocks == 0) return fail(h, FMD_ERR_ARG, "no block has been processed");
+    if (h->sched.n_blocks() == 0) return fail(h, FMD_ERR_ARG, "no block has been processed");
     int rc = fmd_wait_outputs(h, stream);
-    if (!rc && !h->have_out) return fail(h, FMD_ERR_ARG, "no block's outputs are queued yet (fmd_set_output_lag: from the second fmd_submit_* on)");
+    if (!rc && !h->sched.have_out()) return fail(h, FMD_ERR_ARG, "no block's outputs are queued yet (fmd_set_output_lag: from the second fmd_submit_* on)");
     if (rc) return rc;
     const Dims& d = h->ctx.d;
-    hipError_t e = launch_audio_pcm16(h->ctx.b.audio[h->out_slot], d_pcm, (size_t)d.C * d.n_audio * 2, static_cast<hipStream_t>(stream));
+    hipError_t e = launch_audio_pcm16(h->ctx.b.audio[h->sched.out_slot()], d_pcm, (size_t)d.C * d.n_audio * 2, static_cast<hipStream_t>(stream));
     if (e != hipSuccess) return fail(h, FMD_ERR_DEVICE, "k_audio_pcm16 launch: %s", hipGetErrorString(e));
     return FMD_OK;
 }
@@ -1037,8 +836,8 @@ int fmd_audio_pcm16_dev(fmd_handle h, int16_t* d_pcm, void* stream) {
 int fmd_rds_dev(fmd_handle h, const float** d_syms, const int** d_counts) {
     if (!h || !d_syms || !d_counts) return FMD_ERR_ARG;
     { int rc = outputs_wanted(h); if (rc) return rc; }
-    *d_syms = h->ctx.b.rds_sym[h->out_slot];
-    *d_counts = h->ctx.b.rds_count[h->out_slot];
+    *d_syms = h->ctx.b.rds_sym[h->sched.out_slot()];
+    *d_counts = h->ctx.b.rds_count[h->sched.out_slot()];
     return FMD_OK;
 }
 
@@ -1047,7 +846,7 @@ int fmd_get_audio(fmd_handle h, float* audio) {
     int rc = fmd_synchronize(h);
     if (rc) return rc;
     const Dims& d = h->ctx.d;
-    HIP_TRY(h, hipMemcpy(audio, h->ctx.b.audio[h->out_slot], sizeof(float) * 2 * (size_t)d.C * d.n_audio, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(audio, h->ctx.b.audio[h->sched.out_slot()], sizeof(float) * 2 * (size_t)d.C * d.n_audio, hipMemcpyDeviceToHost));
     return FMD_OK;
 }
 
@@ -1056,8 +855,8 @@ int fmd_get_rds_symbols(fmd_handle h, float* syms, int* counts) {
     int rc = fmd_synchronize(h);
     if (rc) return rc;
     const Dims& d = h->ctx.d;
-    HIP_TRY(h, hipMemcpy(syms, h->ctx.b.rds_sym[h->out_slot], sizeof(float) * (size_t)d.C * d.n_rds, hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(counts, h->ctx.b.rds_count[h->out_slot], sizeof(int) * (size_t)d.C, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(syms, h->ctx.b.rds_sym[h->sched.out_slot()], sizeof(float) * (size_t)d.C * d.n_rds, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(counts, h->ctx.b.rds_count[h->sched.out_slot()], sizeof(int) * (size_t)d.C, hipMemcpyDeviceToHost));
     return FMD_OK;
 }
 
@@ -1067,8 +866,8 @@ int fmd_get_rds_bytes(fmd_handle h, uint8_t* bytes, int cap_bytes_per_channel, i
     if (rc) return rc;
     const Dims& d = h->ctx.d;
     std::vector<uint8_t> tmp((size_t)d.C * h->bytes_cap);
-    HIP_TRY(h, hipMemcpy(tmp.data(), h->ctx.b.rds_bytes[h->out_slot], tmp.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(counts, h->ctx.b.rds_bytes_count[h->out_slot], sizeof(int) * (size_t)d.C, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(tmp.data(), h->ctx.b.rds_bytes[h->sched.out_slot()], tmp.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(counts, h->ctx.b.rds_bytes_count[h->sched.out_slot()], sizeof(int) * (size_t)d.C, hipMemcpyDeviceToHost));
     for (int c = 0; c < d.C; c++) {
         counts[c] = std::min(counts[c], std::min(cap_bytes_per_channel, h->bytes_cap));
         std::memcpy(bytes + (size_t)c * cap_bytes_per_channel, tmp.data() + (size_t)c * h->bytes_cap, (size_t)counts[c]);
@@ -1079,8 +878,8 @@ int fmd_get_rds_bytes(fmd_handle h, uint8_t* bytes, int cap_bytes_per_channel, i
 int fmd_rds_bytes_dev(fmd_handle h, const uint8_t** d_bytes, const int** d_counts, int* cap_bytes_per_channel) {
     if (!h || !d_bytes || !d_counts || !cap_bytes_per_channel) return FMD_ERR_ARG;
     { int rc = outputs_wanted(h); if (rc) return rc; }
-    *d_bytes = h->ctx.b.rds_bytes[h->out_slot];
-    *d_counts = h->ctx.b.rds_bytes_count[h->out_slot];
+    *d_bytes = h->ctx.b.rds_bytes[h->sched.out_slot()];
+    *d_counts = h->ctx.b.rds_bytes_count[h->sched.out_slot()];
     *cap_bytes_per_channel = h->bytes_cap;
     return FMD_OK;
 }
@@ -1089,14 +888,14 @@ int fmd_get_rds_db(fmd_handle h, fmd_rds_db* db) {
     if (!h || !db || !h->ctx.rds_decode) return FMD_ERR_ARG;
     int rc = fmd_synchronize(h);
     if (rc) return rc;
-    HIP_TRY(h, hipMemcpy(db, h->ctx.b.rds_db[h->out_slot], sizeof(fmd_rds_db) * (size_t)h->ctx.d.C, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(db, h->ctx.b.rds_db[h->sched.out_slot()], sizeof(fmd_rds_db) * (size_t)h->ctx.d.C, hipMemcpyDeviceToHost));
     return FMD_OK;
 }
 
 int fmd_rds_db_dev(fmd_handle h, const fmd_rds_db** d_db) {
     if (!h || !d_db || !h->ctx.rds_decode) return FMD_ERR_ARG;
     { int rc = outputs_wanted(h); if (rc) return rc; }
-    *d_db = h->ctx.b.rds_db[h->out_slot];
+    *d_db = h->ctx.b.rds_db[h->sched.out_slot()];
     return FMD_OK;
 }
 
@@ -1106,8 +905,8 @@ int fmd_get_rds_groups(fmd_handle h, fmd_rds_group* groups, int cap_groups_per_c
     if (rc) return rc;
     const int C = h->ctx.d.C, gcap = rds_groups_cap(h->bytes_cap);
     std::vector<fmd_rds_group> tmp((size_t)C * gcap);
-    HIP_TRY(h, hipMemcpy(tmp.data(), h->ctx.b.rds_groups[h->out_slot], sizeof(fmd_rds_group) * tmp.size(), hipMemcpyDeviceToHost));
-    HIP_TRY(h, hipMemcpy(counts, h->ctx.b.rds_groups_count[h->out_slot], sizeof(int) * (size_t)C, hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(tmp.data(), h->ctx.b.rds_groups[h->sched.out_slot()], sizeof(fmd_rds_group) * tmp.size(), hipMemcpyDeviceToHost));
+    HIP_TRY(h, hipMemcpy(counts, h->ctx.b.rds_groups_count[h->sched.out_slot()], sizeof(int) * (size_t)C, hipMemcpyDeviceToHost));
     for (int c = 0; c < C; c++) {
         const int n = std::min(counts[c], std::min(cap_groups_per_channel, gcap));
         std::memcpy(groups + (size_t)c * cap_groups_per_channel, tmp.data() + (size_t)c * gcap, sizeof(fmd_rds_group) * (size_t)n);
@@ -1118,8 +917,8 @@ int fmd_get_rds_groups(fmd_handle h, fmd_rds_group* groups, int cap_groups_per_c
 int fmd_rds_groups_dev(fmd_handle h, const fmd_rds_group** d_groups, const int** d_counts, int* cap_groups_per_channel) {
     if (!h || !d_groups || !d_counts || !cap_groups_per_channel || !h->ctx.rds_decode) return FMD_ERR_ARG;
     { int rc = outputs_wanted(h); if (rc) return rc; }
-    *d_groups = h->ctx.b.rds_groups[h->out_slot];
-    *d_counts = h->ctx.b.rds_groups_count[h->out_slot];
+    *d_groups = h->ctx.b.rds_groups[h->sched.out_slot()];
+    *d_counts = h->ctx.b.rds_groups_count[h->sched.out_slot()];
     *cap_groups_per_channel = rds_groups_cap(h->bytes_cap);
     return FMD_OK;
 }
@@ -1139,7 +938,7 @@ int fmd_get_stream(fmd_handle h, const char* name, float* out, size_t cap_floats
     const Buffers& b = h->ctx.b;
     const size_t C = (size_t)d.C;
     const bool keep = h->ctx.keep_taps != 0;
-    const int o = h->out_slot;
+    const int o = h->sched.out_slot();
     const void* p = nullptr;
     size_t n = 0;
     bool from_state = false, lmr_peek = false;
@@ -1151,7 +950,7 @@ int fmd_get_stream(fmd_handle h, const char* name, float* out, size_t cap_floats
     else if (s == "pll_poly" && b.pll_poly[o]) { p = b.pll_poly[o]; n = 4 * C * ((size_t)1 + d.n_fm_out / kSpan); }   // tolerance mode: [C][1 + spans][4], entry 0 = the previous block's last span
     else if (s == "audio") { p = b.audio[o]; n = 2 * C * d.n_audio; }
     else if (s == "rds_sym") { p = b.rds_sym[o]; n = C * d.n_rds; }
-    else if (s == "lmr_est") { p = b.lmr_est[(h->n_blocks + 1) & 1]; n = C * d.n_est; }
+    else if (s == "lmr_est") { p = b.lmr_est[(h->sched.n_blocks() + 1) & 1]; n = C * d.n_est; }
     else if (s == "rds" ) { p = b.rds[o]; n = 2 * C * d.n_rds; }
     else if (s == "lpr" && keep) { p = b.lpr[o]; n = C * d.n_audio; }
     else if (s == "lmr" && keep) { p = b.lmr[o]; n = C * d.n_audio; }
@@ -1188,7 +987,7 @@ int fmd_get_stream(fmd_handle h, const char* name, float* out, size_t cap_floats
     int rc = fmd_synchronize(h);
     if (rc) return rc;
     if (lmr_peek) {   // reference GetAudioLMRPhaseError(): the offset after the newest block's update (the next block's k_extract computes it for itself)
-        HIP_TRY(h, launch_lmr_phase_peek(h->ctx, (int)((h->n_blocks + 1) & 1), b.lmr_peek, h->own_stream));
+        HIP_TRY(h, launch_lmr_phase_peek(h->ctx, (int)((h->sched.n_blocks() + 1) & 1), b.lmr_peek, h->own_stream));
         HIP_TRY(h, hipStreamSynchronize(h->own_stream));
     }
     HIP_TRY(h, hipMemcpy(out, p, sizeof(float) * n, hipMemcpyDeviceToHost));
@@ -1206,7 +1005,7 @@ struct StatePart { float* base; size_t floats; size_t stride; };   // the channe
 std::vector<StatePart> state_parts(fmd_handle h) {
     const Dims& d = h->ctx.d;
     Buffers& b = h->ctx.b;
-    const int par = (int)(h->n_blocks & 1), slot = (int)(h->n_blocks % kSlots);
+    const int par = (int)(h->sched.n_blocks() & 1), slot = (int)(h->sched.n_blocks() % kSlots);
     std::vector<StatePart> v;
     auto by_par = [&](void* const* base, size_t floats, int flip) { v.push_back({static_cast<float*>(base[par ^ flip]), floats, floats}); };
     { void* p[2] = {b.base_tail[0], b.base_tail[1]}; by_par(p, (size_t)d.tail_base * 2, 0); }
@@ -1250,14 +1049,14 @@ int fmd_get_state(fmd_handle h, int channel, void* blob, size_t cap_bytes) {
     float* out = reinterpret_cast<float*>(static_cast<char*>(blob) + sizeof(hd));
     // SoA fields [field][C] -> one float per field
     HIP_TRY(h, hipMemcpy2D(out, sizeof(float), h->ctx.b.state + channel, sizeof(float) * (size_t)d.C, sizeof(float), S_NUM_FIELDS, hipMemcpyDeviceToHost));
-    const int par = (int)(h->n_blocks & 1);   // the histories the NEXT block reads
+    const int par = (int)(h->sched.n_blocks() & 1);   // the histories the NEXT block reads
     // the two L-R phase fields hold P_k by k & 1 (fmd_kernels.hip: lmr_field); in the blob: PREV = the newest block's offset
     if (par == 1) std::swap(out[S_LMR_PHASE_CUR], out[S_LMR_PHASE_PREV]);
     // CUR = P_b, the offset the NEXT block is mixed with.  Where the next block's k_extract derives it itself (tolerance mode, small
     // batches) nothing has written it behind the newest block: materialise it here, so that a blob means the same whichever path
     // produced it and can be restored into a handle on the other side of that switch
-    if (h->n_blocks > 0) {
-        HIP_TRY(h, launch_lmr_phase_peek(h->ctx, (int)((h->n_blocks + 1) & 1), h->ctx.b.lmr_peek, h->own_stream));
+    if (h->sched.n_blocks() > 0) {
+        HIP_TRY(h, launch_lmr_phase_peek(h->ctx, (int)((h->sched.n_blocks() + 1) & 1), h->ctx.b.lmr_peek, h->own_stream));
         HIP_TRY(h, hipStreamSynchronize(h->own_stream));
         HIP_TRY(h, hipMemcpy(&out[S_LMR_PHASE_CUR], h->ctx.b.lmr_peek + channel, sizeof(float), hipMemcpyDeviceToHost));
     }
@@ -1296,13 +1095,13 @@ int fmd_set_state(fmd_handle h, int channel, const void* blob, size_t n_bytes) {
     int rc = sync_all(h);
     if (rc) return rc;
     const float* in = reinterpret_cast<const float*>(static_cast<const char*>(blob) + sizeof(hd));
-    const int par = (int)(h->n_blocks & 1);
+    const int par = (int)(h->sched.n_blocks() & 1);
     std::vector<float> fields(in, in + S_NUM_FIELDS);
     if (par == 1) std::swap(fields[S_LMR_PHASE_CUR], fields[S_LMR_PHASE_PREV]);   // see fmd_get_state
     HIP_TRY(h, hipMemcpy2D(h->ctx.b.state + channel, sizeof(float) * (size_t)d.C, fields.data(), sizeof(float), sizeof(float), S_NUM_FIELDS, hipMemcpyHostToDevice));
     // a station restored inside its start-up transient (tolerance mode: SA_X1I counts its samples since the reset) keeps k_pll_span for the rest of it
     if (h->ctx.fast && fields[SA_X1I] < kPllWarmSamples)
-        h->warm_left = std::max(h->warm_left, (int)((kPllWarmSamples - fields[SA_X1I] + (float)d.n_fm_out - 1.0f) / (float)d.n_fm_out));
+        h->sched.keep_warm((int)((kPllWarmSamples - fields[SA_X1I] + (float)d.n_fm_out - 1.0f) / (float)d.n_fm_out));
     in += S_NUM_FIELDS;
     for (const StatePart& p : state_parts(h)) {
         HIP_TRY(h, hipMemcpy(p.base + (size_t)channel * p.stride, in, sizeof(float) * p.floats, hipMemcpyHostToDevice));
@@ -1406,7 +1205,7 @@ int fmd_debug_extract_pairing(fmd_handle h, int mode) {
 
 int fmd_profile_enable(fmd_handle h, int on) {
     if (!h) return FMD_ERR_ARG;
-    h->profiling = on < 0 ? 0 : (on > 3 ? 3 : on);
+    h->sched.set_profiling(on < 0 ? 0 : (on > 3 ? 3 : on));
     return FMD_OK;
 }
 

@@ -9,6 +9,7 @@
 #include <cstdlib>
 
 #include "fmd_plan.h"
+#include "fmd_schedule.h"
 #include "fmd_tables.h"
 #include "fmdemod.h"
 
@@ -68,12 +69,7 @@ struct Dims {
     int tail_base;  // fm_in samples of history k_front keeps per channel
 };
 
-// Stream buffers are indexed by pipeline slot (= block index % kSlots): the stages of consecutive blocks run concurrently
-// on different streams, so a producer of block b+1 must not overwrite what a consumer of block b (or b-1) still reads.
-// Six slots: the front end and the power pass of a block must be able to run far enough ahead of the PLL that the next PLL
-// launch's inputs are ready before the running one ends (with four, the front end of block b+4 waited for the RDS stage of
-// block b and the power pass came in ~90 us before the PLL needed it: no room for the per-wavefront hand-over to overlap).
-static constexpr int kSlots = 6;
+// Stream buffers are indexed by pipeline slot (= block index % kSlots, fmd_schedule.h)
 static_assert(kSlots <= 8, "one S_PILOT_POWER state field per slot");
 // buf = block % kSlots (stream buffers), par = block & 1 (history tails); t0/t1: optional events that receive the stage's
 // first kernel's start and last kernel's end timestamps (attached to the dispatch packets themselves: no extra queue packets)
@@ -236,7 +232,8 @@ inline size_t tap_floats(const Dims& d) { return (size_t)d.C * (6 * (size_t)d.n_
 hipError_t launch_stage_predecim(const LaunchCtx& ctx, SlotRef r, const void* d_iq, bool u8, hipStream_t s);   // k_predecim (m > 1)
 // pll != NULL (tolerance mode only): the pilot stage of the block in slot pll->buf rides in the same launch (k_front_mfma<..., FUSED>)
 hipError_t launch_stage_front(const LaunchCtx& ctx, SlotRef r, const void* d_iq, bool u8, hipStream_t s, const SlotRef* pll = nullptr);   // k_front
-bool front_takes_capture(const LaunchCtx& ctx);    // m > 1: the first decimator runs inside launch_stage_front's kernel (no predecim stage for this block)
+// m > 1: the first decimator runs inside launch_stage_front's kernel (no predecim stage for this block)
+inline bool front_takes_capture(const LaunchCtx& ctx) { return front_takes_capture(ctx.d.m, ctx.fast != 0, ctx.any_deemph != 0, ctx.deemph_in_tile != 0, ctx.d.n_fm_out, ctx.split_front != 0); }
 hipError_t launch_stage_deemph(const LaunchCtx& ctx, SlotRef r, hipStream_t s);                            // k_deemphasis + k_hilbert
 hipError_t launch_stage_power(const LaunchCtx& ctx, SlotRef r, hipStream_t s);                             // k_pilot_power
 hipError_t launch_stage_pll(const LaunchCtx& ctx, SlotRef r, hipStream_t s);                               // k_pilot_pll

@@ -3089,10 +3089,6 @@ hipError_t launch_stage_predecim(const LaunchCtx& ctx, SlotRef r, const void* d_
 
 // 1.024 / 2.048 MSa/s, tolerance mode: the first decimator inside the front end's kernel (k_front_pre_mfma) — the block then has no
 // predecim stage and launch_stage_front takes the capture.  Not with a de-emphasised station (k_front_mfma's WU form stays on fm_in).
-bool front_takes_capture(const LaunchCtx& ctx) {
-    return ctx.d.m > 1 && ctx.fast && !ctx.any_deemph && !ctx.deemph_in_tile && ctx.d.n_fm_out % 1024 == 0 && !ctx.split_front;
-}
-
 template <int M, typename InT>
 static hipError_t launch_front_pre(const LaunchCtx& ctx, SlotRef r, const InT* d_iq, hipStream_t s, const SlotRef* pll) {
     using G = FrontPreGeom<M, sizeof(InT) == 2>;

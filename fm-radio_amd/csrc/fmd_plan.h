@@ -65,6 +65,13 @@ inline PllThresholds default_pll_thresholds(unsigned flags) {
             (flags & FMD_FLAG_PLL_LOW_WORK) ? 0 : ((flags & FMD_FLAG_PLL_TIME_PARALLEL) ? INT_MAX : kPllTimeParallelMaxStations)};
 }
 
+// Tolerance mode at 1.024 / 2.048 MSa/s (m > 1): the first decimator runs inside the front end's kernel (k_front_pre_mfma) and the block has no
+// decimator stage of its own, unless a de-emphasis filter is on (as a stage or in k_front's tile), the block length does not fit the tiles, or
+// fmd_debug_split_front asks for the two kernels.  The launchers (fmd_kernels.hip) and the schedule (fmd_schedule.cpp) both ask.
+inline bool front_takes_capture(int m, bool fast, bool any_deemph, bool deemph_in_tile, int n_fm_out, bool split_front) {
+    return m > 1 && fast && !any_deemph && !deemph_in_tile && n_fm_out % 1024 == 0 && !split_front;
+}
+
 struct Plan {
     int channels, effective;     // the station count and effective_channels() of it
     PllThresholds pll;           // in force: default_pll_thresholds(), or what fmd_debug_pll_adaptive moved them to

@@ -1,6 +1,6 @@
 """CPU sanitizer run (SURVEY §4 "sanitizers on the CPU build"; never on the GPU box's device code): the oracle (oracle/fm_oracle.c),
 the library's host-side filter designer (fm-radio_amd/csrc/fmd_design.cpp), the designers of the tolerance mode's tables
-(fmd_tables.cpp), the kernel-selection plan (fmd_plan.cpp) and the host-side drivers (group synchroniser, scraper writers) built with
+(fmd_tables.cpp), the kernel-selection plan (fmd_plan.cpp), the block schedule (fmd_schedule.cpp) and the host-side drivers (group synchroniser, scraper writers) built with
 -fsanitize=address,undefined (`make -C oracle asan`) as stand-alone programs and fed the golden fixtures.  Any out-of-bounds access, use after
 free, leak, signed overflow or misaligned access aborts the run (-fno-sanitize-recover); the outputs must still be the fixtures'.
 
@@ -125,3 +125,15 @@ def test_table_designers_under_sanitizers_reproduce_the_pinned_tables(asan_build
     differing = [(g["fs"], g["table"]) for g, w in zip(got, want["tables"]) if g["sha256"] != w["sha256"]]
     assert not differing, f"first differing table: {differing[0]}; all: {differing}"
     assert len(blob) == want["bytes"] == sum(t["bytes"] for t in got) and hashlib.sha256(blob).hexdigest() == want["sha256"]
+
+
+def test_block_schedule_under_sanitizers_gives_the_recorded_graphs(asan_build, tmp_path):
+    """fm-radio_amd/csrc/fmd_schedule.cpp with fmd_plan.cpp, plain g++ (no HIP, no library), under the sanitizers: tests/cpp/schedule_main.cpp on every scenario of
+    tests/golden/schedule_traces.json gives the dependency graphs recorded from the code the unit replaced (tests/test_schedule_cpu.py states the comparison)."""
+    import schedule_graph as G
+    golden = json.loads((ROOT / "tests" / "golden" / "schedule_traces.json").read_text())
+    (tmp_path / "scenarios.txt").write_text(G.scenario_text(golden["scenarios"]))
+    got = G.split_log(_run([asan_build / "schedule_main", tmp_path / "scenarios.txt"]).stdout)
+    assert sorted(got) == sorted(golden["traces"]) and len(got) >= 25
+    for name, want in golden["traces"].items():
+        assert G.normalise(got[name]).queues == G.normalise(want).queues, name
