@@ -160,6 +160,26 @@ class MeterTpDesign(C.Structure):
     _fields_ = [("L", C.c_int), ("taps_per_phase", C.c_int), ("taps", (C.c_float * 12) * 3)]
 
 
+class ModmonConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_samples", C.c_longlong), ("device", C.c_int)]
+
+
+class ModmonDesign(C.Structure):
+    """include/fmdemod.h fmd_modmon_design_t"""
+    _fields_ = [("fs", C.c_int), ("M", C.c_int), ("P", C.c_int), ("reserved", C.c_int), ("hz_per_rad", C.c_double), ("pilot_gain", C.c_double),
+                ("h", C.c_float * 33), ("reserved_f", C.c_float), ("pilot_cos", C.c_double * 384), ("pilot_sin", C.c_double * 384),
+                ("edge", C.c_double * 301)]
+
+
+# include/fmdemod.h fmd_modmon_status (1792 bytes)
+MODMON_STATUS_DTYPE = np.dtype([("samples", "<u8"), ("intervals", "<u8"), ("seconds", "<u8"), ("last_hi", "<f4"), ("last_lo", "<f4"),
+                                ("hold_hi", "<f4"), ("hold_lo", "<f4"), ("last_s1", "<f8"), ("last_s2", "<f8"), ("last_sc", "<f8"),
+                                ("last_ss", "<f8"), ("sec_e", "<f8", (60,)), ("sec_f", "<f8", (60,)), ("sec_q", "<f8", (60,)),
+                                ("sec_n", "<u4", (60,)), ("open_e", "<f8"), ("open_f", "<f8"), ("open_q", "<f8"), ("open_n", "<u4"),
+                                ("over", "<u4"), ("nonfinite", "<u4"), ("reserved", "<u4")])
+MODMON_BINS = 300
+
+
 class PlanInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("effective_channels", "pilot_power_rows", "pll_k_adaptive", "pll_chained", "pll_waves", "lmr_inline", "lazy_capable",
                                        "front_lds_pad", "front_big_tile", "extract_auto_pair", "pll_kernel")]
@@ -343,6 +363,23 @@ def load_library():
     L.fmd_meter_range.argtypes = [C.c_void_p, C.POINTER(MeterDesign), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.fmd_meter_last_error.restype = C.c_char_p
     L.fmd_meter_last_error.argtypes = [C.c_void_p]
+    L.fmd_modmon_design.argtypes = [C.c_int, C.POINTER(ModmonDesign)]
+    for fn in ("fmd_modmon_deviation_hz", "fmd_modmon_offset_hz", "fmd_modmon_pilot_hz"):
+        getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(ModmonDesign), C.POINTER(C.c_double)]
+    L.fmd_modmon_mpx_power_dbr.argtypes = [C.c_void_p, C.POINTER(ModmonDesign), C.c_int, C.POINTER(C.c_double)]
+    L.fmd_modmon_exceedance.argtypes = [C.c_void_p, C.c_uint, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]
+    L.fmd_modmon_percentile.argtypes = [C.c_void_p, C.c_uint, C.c_double, C.POINTER(C.c_double)]
+    L.fmd_modmon_create.argtypes = [C.POINTER(ModmonConfig), C.POINTER(C.c_void_p)]
+    L.fmd_modmon_destroy.argtypes = [C.c_void_p]
+    L.fmd_modmon_reset.argtypes = [C.c_void_p, C.c_int]
+    L.fmd_modmon_reset_peaks.argtypes = [C.c_void_p, C.c_int]
+    L.fmd_modmon_process_cf32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_modmon_process_u8_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_modmon_get_status.argtypes = [C.c_void_p, C.c_void_p]
+    L.fmd_modmon_get_histogram.argtypes = [C.c_void_p, C.c_void_p]
+    L.fmd_modmon_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.fmd_modmon_last_error.restype = C.c_char_p
+    L.fmd_modmon_last_error.argtypes = [C.c_void_p]
     L.fmd_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.argtypes = [C.c_void_p]
@@ -1480,3 +1517,163 @@ class LoudnessMeter:
         if not self.features & METER_TRUE_PEAK:
             raise FmdError(FMD_ERR_STATE, "the meter was created without METER_TRUE_PEAK")
         return meter_dbtp(self.r128_status()["tp_hold"])
+
+
+def _modmon_raise(L, rc):
+    raise FmdError(rc, L.fmd_modmon_last_error(None).decode() or L.fmd_status_string(rc).decode())
+
+
+def modmon_design(fs: int) -> ModmonDesign:
+    """fmd_modmon_design (host only, no GPU needed): the interval length M, the MPX low-pass's 33 taps, the pilot table and its gain,
+    and the histogram's edges"""
+    L = load_library()
+    d = ModmonDesign()
+    rc = L.fmd_modmon_design(int(fs), C.byref(d))
+    if rc != FMD_OK:
+        _modmon_raise(L, rc)
+    return d
+
+
+def _modmon_record(fn, record, design: ModmonDesign, *args) -> float:
+    L = load_library()
+    r = np.ascontiguousarray(record, MODMON_STATUS_DTYPE).reshape(-1)
+    if r.size != 1:
+        raise ValueError("one status record at a time")
+    out = C.c_double(0.0)
+    rc = getattr(L, fn)(r.ctypes.data_as(C.c_void_p), C.byref(design), *args, C.byref(out))
+    if rc != FMD_OK:
+        _modmon_raise(L, rc)
+    return out.value
+
+
+def modmon_deviation_hz(record, design: ModmonDesign) -> float:
+    """fmd_modmon_deviation_hz of one MODMON_STATUS_DTYPE record: half the peak-to-peak swing of the newest 50 ms interval, in Hz
+    (FMD_ERR_STATE before the first interval)"""
+    return _modmon_record("fmd_modmon_deviation_hz", record, design)
+
+
+def modmon_offset_hz(record, design: ModmonDesign) -> float:
+    """fmd_modmon_offset_hz: the carrier's frequency offset over the newest interval, in Hz"""
+    return _modmon_record("fmd_modmon_offset_hz", record, design)
+
+
+def modmon_pilot_hz(record, design: ModmonDesign) -> float:
+    """fmd_modmon_pilot_hz: the 19 kHz pilot's deviation over the newest interval, in Hz"""
+    return _modmon_record("fmd_modmon_pilot_hz", record, design)
+
+
+def modmon_mpx_power_dbr(record, design: ModmonDesign, window_s: int = 60) -> float:
+    """fmd_modmon_mpx_power_dbr: ITU-R BS.412 multiplex power over the newest window_s completed seconds, in dBr (FMD_ERR_STATE while
+    fewer are complete)"""
+    return _modmon_record("fmd_modmon_mpx_power_dbr", record, design, C.c_int(int(window_s)))
+
+
+def _modmon_hist(hist):
+    h = np.ascontiguousarray(hist, np.uint32)
+    if h.shape != (MODMON_BINS,):
+        raise ValueError("hist must hold 300 bins")
+    return h
+
+
+def modmon_exceedance(hist, over: int, limit_hz: int = 75000):
+    """fmd_modmon_exceedance (host only): (fraction, count) of one station's 50 ms intervals whose peak deviation is at least limit_hz
+    (a multiple of 500 up to 150000)"""
+    L = load_library()
+    h = _modmon_hist(hist)
+    frac, cnt = C.c_double(0.0), C.c_ulonglong(0)
+    rc = L.fmd_modmon_exceedance(h.ctypes.data_as(C.c_void_p), int(over), int(limit_hz), C.byref(frac), C.byref(cnt))
+    if rc != FMD_OK:
+        _modmon_raise(L, rc)
+    return frac.value, cnt.value
+
+
+def modmon_percentile(hist, over: int, q: float) -> float:
+    """fmd_modmon_percentile (host only): the q-quantile (0 ... 1) of one station's interval peaks, as its 500 Hz bin's centre in Hz"""
+    L = load_library()
+    h = _modmon_hist(hist)
+    out = C.c_double(0.0)
+    rc = L.fmd_modmon_percentile(h.ctypes.data_as(C.c_void_p), int(over), float(q), C.byref(out))
+    if rc != FMD_OK:
+        _modmon_raise(L, rc)
+    return out.value
+
+
+class ModulationMonitor:
+    """Peak deviation (ITU-R SM.1268), multiplex power (ITU-R BS.412), carrier offset and pilot deviation of C stations' baseband on the
+    GPU (fmd_modmon_*).  Feed it the [C, n, 2] float32 or uint8 CUDA tensors the demodulator takes (a channeliser's output); it changes
+    nothing in them.  status() returns MODMON_STATUS_DTYPE records, histogram() the interval peaks' [C, 300] counts; the modmon_*
+    functions turn them into Hz and dBr on the host."""
+
+    def __init__(self, n_channels: int, fs: int, max_input_samples: int = 1 << 20, device: int = -1):
+        self.L = load_library()
+        cfg = ModmonConfig(int(n_channels), int(fs), int(max_input_samples), device)
+        self.m = C.c_void_p()
+        rc = self.L.fmd_modmon_create(C.byref(cfg), C.byref(self.m))
+        if rc != FMD_OK:
+            self.m = None
+            _modmon_raise(self.L, rc)
+        self.n_channels, self.fs = int(n_channels), int(fs)
+        self.design = modmon_design(fs)
+
+    def close(self):
+        if getattr(self, "m", None):
+            self.L.fmd_modmon_destroy(self.m)
+            self.m = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc < 0:
+            raise FmdError(rc, (self.L.fmd_modmon_last_error(self.m) or b"").decode() or self.L.fmd_status_string(rc).decode())
+        return rc
+
+    def process(self, x, n: int | None = None, active=None, stream=None):
+        """monitors the first n samples (default all) of x: [C, >= n, 2] float32 or uint8 on the device, contiguous samples; active: None
+        or a [C] uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole).  Asynchronous on `stream` (default: torch's
+        current)."""
+        import torch
+        if not (x.is_cuda and x.dtype in (torch.float32, torch.uint8) and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
+                and x.stride(2) == 1 and x.stride(1) == 2):
+            raise ValueError("x must be a CUDA float32 or uint8 tensor [C, n, 2] with contiguous samples")
+        n = int(x.shape[1]) if n is None else int(n)
+        if active is not None:
+            if active.dtype == torch.bool:
+                active = active.view(torch.uint8)
+            if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (self.n_channels,) and active.is_contiguous()):
+                raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
+        fn = self.L.fmd_modmon_process_cf32_dev if x.dtype == torch.float32 else self.L.fmd_modmon_process_u8_dev
+        self._check(fn(self.m, C.c_void_p(x.data_ptr()), in_stride, n, None if active is None else C.c_void_p(active.data_ptr()),
+                       C.c_void_p(stream)))
+
+    def reset(self, channel: int = -1):
+        self._check(self.L.fmd_modmon_reset(self.m, int(channel)))
+
+    def reset_peaks(self, channel: int = -1):
+        self._check(self.L.fmd_modmon_reset_peaks(self.m, int(channel)))
+
+    def status(self) -> np.ndarray:
+        """[C] MODMON_STATUS_DTYPE records; waits for the monitor's work"""
+        out = np.zeros(self.n_channels, MODMON_STATUS_DTYPE)
+        self._check(self.L.fmd_modmon_get_status(self.m, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def histogram(self) -> np.ndarray:
+        """[C, 300] uint32 counts of 50 ms intervals per 500 Hz bin of peak deviation; waits for the monitor's work"""
+        out = np.zeros((self.n_channels, MODMON_BINS), np.uint32)
+        self._check(self.L.fmd_modmon_get_histogram(self.m, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def status_dev_ptr(self) -> int:
+        """fmd_modmon_status_dev: the address of the device's own [C] records, valid until the next process call"""
+        p = C.c_void_p()
+        self._check(self.L.fmd_modmon_status_dev(self.m, C.byref(p)))
+        return p.value

@@ -802,6 +802,121 @@ int fmd_meter_get_range_histogram(fmd_meter m, unsigned* hist);
  * when no bin survives the gates */
 int fmd_meter_range(const unsigned* hist, const fmd_meter_design_t* d, double* lra, double* low, double* high);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * FM modulation monitor (NOT part of the reference): peak deviation (ITU-R SM.1268: peak hold over 50 ms intervals and the distribution
+ * of those peaks), multiplex power (ITU-R BS.412), carrier frequency offset and pilot deviation of every station, measured where the
+ * station's baseband already is.  It reads the device array [C][in_stride][2] (cf32 or u8) that the demodulator takes and the channeliser
+ * writes, changes nothing in it, and keeps one fmd_modmon_status record and a 300-bin histogram per station.  It measures the RF signal,
+ * not the audio.  Arithmetic, restated in C by tests/cpp/modmon_ref.c; T = 33 taps, NP = 64 partials, NB = 300 bins, RING = 60:
+ *   input       u8 converts as (float)v - 127 (fmd_process_u8_*); everything below sees floats i, q.
+ *   design      host, double, host libm (fmd_modmon_design); pi = 3.14159265358979323846; fs a multiple of 1000 in 192000 ... 384000:
+ *                 M = fs / 20 (samples of a 50 ms interval);  P = fs / gcd(fs, 19000) (the pilot table's period, at most 384)
+ *                 hz_per_rad = (double)fs / (2 * pi)
+ *                 MPX low-pass, fc = 76000: w = 2 * fc / fs;  x = w * (i - 16);  r = (i - 16) / 16.0
+ *                   g[i] = ((w * sinc(x)) * I0(5.0 * sqrt(1 - r * r))) / I0(5.0), i = 0 ... 32, sinc and I0 as in the true-peak design above
+ *                   h[i] = (float)(g[i] / (sum over i ascending, from +0, of g[i]))
+ *                 pilot_cos[k] = cos((2 * pi * (double)m) / (double)fs), pilot_sin[k] = sin(the same), m = (19000 * k) mod fs, k = 0 ... P - 1
+ *                 pilot_gain = sqrt(re * re + im * im) * sinc(19000.0 / fs), with a_i = (2 * pi * (double)(19000 * i)) / (double)fs,
+ *                   re = sum over i ascending, from +0, of (double)h[i] * cos(a_i), im likewise with sin
+ *                   (the second factor is the difference discriminator's own response to a 19 kHz line)
+ *                 edge[j] = 500.0 * j, j = 0 ... 300
+ *   discriminator  fp32 (denormals kept), per station, n counted absolutely since the station's reset:
+ *                 theta[n] = atan2f(q, i)                                          (the host libm's, fmd_math.h's fmd_atan2f on the device)
+ *                 d[n] = wrap(theta[n] - theta[n-1]);  wrap(x) = x >= (float)pi ? x - 2 (float)pi : x <= -(float)pi ? x + 2 (float)pi : x
+ *                 d[n] = +0.0f for n <= 0 (the first sample after a reset has no predecessor)
+ *                 y[n] = fmaf(h[32], d[n-32], ... fmaf(h[1], d[n-1], fmaf(h[0], d[n], +0.0f)))      t ascending, from +0
+ *               The 33 samples before a call's first are the station's history; a masked call and reset_peaks keep it.
+ *   per sample  hi = fmaxf(hi, y), lo = fminf(lo, y) from -inf and +inf at each interval's start (a NaN leaves both as they are); the same
+ *               two updates go into hold_hi and hold_lo (-inf and +inf at create, reset and reset_peaks).
+ *                 fd = (double)y * hz_per_rad
+ *               Interval g is the samples [g M, (g + 1) M), r = n - g M.  Partial j = r mod 64 takes its terms in ascending r, from +0:
+ *                 s1_j = s1_j + fd;  s2_j = fma(fd, fd, s2_j);  sc_j = fma(fd, pilot_cos[n mod P], sc_j);  ss_j = fma(fd, pilot_sin[n mod P], ss_j)
+ *               An open interval carries hi, lo and its 4 x 64 partials to the next call (2 KB per station).
+ *   interval end  per sum the halving tree p_j += p_{j+w} for j < w, w = 32, 16, ... 1;  S = p_0.
+ *                 D = 0.5 * ((double)hi - (double)lo) * hz_per_rad    (half the peak-to-peak swing: a mistuned carrier is not deviation)
+ *                 last_hi, last_lo, last_s1, last_s2, last_sc, last_ss = hi, lo, S1, S2, Sc, Ss;  intervals++
+ *                 D or S2 not finite -> nonfinite++ (the interval enters neither the histogram nor the second's sums)
+ *                 else: D >= edge[300] -> over++, else hist[j]++ for the j with edge[j] <= D < edge[j + 1] (comparisons only); and
+ *                       open_e += S2;  open_f += S1;  open_q += fma(Sc, Sc, Ss * Ss);  open_n += 1
+ *                 every 20th interval completes a second: open_e, open_f, open_q, open_n go to sec_e, sec_f, sec_q, sec_n at index
+ *                 [seconds % 60], seconds++, and the open sums return to +0.
+ *               No floating-point atomics; ordinary stores.  Nothing depends, bit for bit, on how the samples are split into calls, on
+ *               streams, on the format, on the batch or on the station's row.
+ *   read-out    host, double, pure functions; FMD_ERR_STATE where there is nothing to read yet:
+ *                 deviation_hz = D of the newest interval, from last_hi and last_lo          (intervals == 0 -> FMD_ERR_STATE)
+ *                 offset_hz    = last_s1 / (double)M;   pilot_hz = 2 * sqrt(fma(sc, sc, ss * ss)) / (double)M / pilot_gain
+ *                 mpx_power_dbr(window_s), 1 <= window_s <= 60: over the newest window_s completed seconds, oldest first, from +0:
+ *                   e += sec_e, f += sec_f, k += sec_n;  N = (double)M * (double)k;  v = e / N - (f / N) * (f / N)
+ *                   10 * log10(2 * v / (19000.0 * 19000.0)), -inf for v <= 0;  FMD_ERR_STATE while seconds < window_s or k == 0
+ *                 exceedance(limit_hz), a multiple of 500 in 0 ... 150000: count = over + the bins from limit_hz / 500 up;
+ *                   fraction = (double)count / (double)(over + all bins)
+ *                 percentile(q), 0 <= q <= 1: n = over + all bins; the zero-based rank floor(q * (n - 1) + 0.5) by cumulative count falls
+ *                   in bin j: 500.0 * j + 250.0 (the bin's centre), or 150000.0 where it falls among the `over` intervals
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_modmon_s* fmd_modmon;
+typedef struct {
+    int       n_channels;         /* C: station rows of the input */
+    int       fs;                 /* the baseband's rate: a multiple of 1000 in 192000 ... 384000 */
+    long long max_input_samples;  /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_modmon_config;
+typedef struct {
+    int    fs, M, P, reserved;
+    double hz_per_rad, pilot_gain;
+    float  h[33], reserved_f;
+    double pilot_cos[384], pilot_sin[384];           /* [0, P) used, the rest 0 */
+    double edge[301];
+} fmd_modmon_design_t;
+/* one per station, 1792 bytes: samples at byte 0, intervals 8, seconds 16, last_hi 24, last_lo 28, hold_hi 32, hold_lo 36, last_s1 40,
+ * last_s2 48, last_sc 56, last_ss 64, sec_e 72, sec_f 552, sec_q 1032, sec_n 1512, open_e 1752, open_f 1760, open_q 1768, open_n 1776,
+ * over 1780, nonfinite 1784, reserved 1788 */
+typedef struct {
+    unsigned long long samples;       /* samples monitored since reset */
+    unsigned long long intervals;     /* completed 50 ms intervals */
+    unsigned long long seconds;       /* completed groups of 20 intervals */
+    float    last_hi, last_lo;        /* extremes of y over the newest interval, in rad per sample */
+    float    hold_hi, hold_lo;        /* extremes of y since reset or reset_peaks (-inf, +inf before the first sample) */
+    double   last_s1, last_s2, last_sc, last_ss;   /* the newest interval's sums, in Hz and Hz^2 */
+    double   sec_e[60], sec_f[60], sec_q[60];      /* second s at [s % 60]: sums of S2, S1 and Sc^2 + Ss^2 over its classified intervals */
+    unsigned sec_n[60];               /* ... and their count */
+    double   open_e, open_f, open_q;  /* the open second's sums */
+    unsigned open_n;
+    unsigned over, nonfinite;         /* intervals with D >= 150 kHz / with a non-finite D or S2 */
+    unsigned reserved;
+} fmd_modmon_status;
+
+/* host-only (no GPU needed).  FMD_ERR_ARG unless fs is a multiple of 1000 in 192000 ... 384000 */
+int fmd_modmon_design(int fs, fmd_modmon_design_t* out);
+int fmd_modmon_deviation_hz(const fmd_modmon_status* s, const fmd_modmon_design_t* d, double* hz);
+int fmd_modmon_offset_hz(const fmd_modmon_status* s, const fmd_modmon_design_t* d, double* hz);
+int fmd_modmon_pilot_hz(const fmd_modmon_status* s, const fmd_modmon_design_t* d, double* hz);
+int fmd_modmon_mpx_power_dbr(const fmd_modmon_status* s, const fmd_modmon_design_t* d, int window_s, double* dbr);
+/* hist [300]: one station's histogram; over: its status record's counter */
+int fmd_modmon_exceedance(const unsigned* hist, unsigned over, int limit_hz, double* fraction, unsigned long long* count);
+int fmd_modmon_percentile(const unsigned* hist, unsigned over, double q, double* hz);
+
+int fmd_modmon_create(const fmd_modmon_config* cfg, fmd_modmon* out);
+int fmd_modmon_destroy(fmd_modmon m);
+/* everything of station `channel` (-1 = every station) as after create: counters, sums, histogram, extremes and the 33-sample history.
+ * Waits for the monitor's earlier work */
+int fmd_modmon_reset(fmd_modmon m, int channel);
+/* hold_hi and hold_lo of station `channel` (-1 = every station) to -inf and +inf; nothing else */
+int fmd_modmon_reset_peaks(fmd_modmon m, int channel);
+/* monitors n samples of every station.  d_in [C][in_stride][2] on the device, cf32 (8-byte aligned) or u8 (2-byte aligned); d_active:
+ * [C] uint8 on the device, NULL = all: a station whose byte is 0 is skipped whole.  n < 0, n > in_stride, n > max_input_samples or a
+ * misaligned d_in return FMD_ERR_ARG and change nothing; n == 0 is valid.  Asynchronous on `stream`; consecutive calls may use different
+ * streams (the library orders them). */
+int fmd_modmon_process_cf32_dev(fmd_modmon m, const float* d_in, long long in_stride, long long n, const uint8_t* d_active, void* stream);
+int fmd_modmon_process_u8_dev(fmd_modmon m, const uint8_t* d_in, long long in_stride, long long n, const uint8_t* d_active, void* stream);
+/* out [C]; synchronises with the monitor's work */
+int fmd_modmon_get_status(fmd_modmon m, fmd_modmon_status* out);
+/* hist [C][300]: intervals per 500 Hz bin of D; synchronises with the monitor's work */
+int fmd_modmon_get_histogram(fmd_modmon m, unsigned* hist);
+/* the device's own [C] records, for a consumer on the device: ordered behind the monitor's work on the stream of its last process call,
+ * valid until the next process call */
+int fmd_modmon_status_dev(fmd_modmon m, const fmd_modmon_status** d_status);
+const char* fmd_modmon_last_error(fmd_modmon m);
+
 #ifdef __cplusplus
 }
 #endif
