@@ -361,6 +361,12 @@ const char* fmd_rdsdec_last_error(fmd_rdsdec d);
  * (Airspy, SDRplay, USRP sc16) — into n_stations channels at fs_out, laid out [C][n_out] cf32 — the input layout of fmd_process_cf32_dev.  Per station: mix the centre frequency to 0, then a rational polyphase
  * decimator L/M = fs_out/fs_in (256 k / 10 M = 16 / 625) built from one Kaiser-windowed prototype (cut-off fs_out / 2,
  * 60 dB).  Streaming: histories and the mixers' phases carry over from call to call.
+ * The input and output sample indices are counted since create / reset in unsigned 64-bit integers and the mixer's phase n inc is
+ * taken modulo 2^64, which is its definition; the first product to overflow is o M (o the output index, in the window start
+ * floor(o M / L) and the branch (o M) mod L) at o M = 2^64, i.e. after 2^64 / L >= 2^58 input samples (L <= 64): 101 806 days at
+ * 32.768 MSa/s, the highest rate accepted at fs_out = 256 kSa/s.  (A station's mixer runs at inc 2^-64 fs_in with inc the double
+ * frac(f / fs_in) rounded to 2^-63: within 2^-54 fs_in, 1.8e-9 Hz at that rate, of f.  Against the exact f that is a phase difference
+ * of up to 3.5e-16 rad per sample, 1.5e-6 rad at sample 2^32.)
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct fmd_channelizer_s* fmd_channelizer;
 typedef struct {
@@ -416,6 +422,10 @@ const char* fmd_chan_last_error(fmd_channelizer h);
  *     into calls.  Reported: PSD[i] = S[k] / (F fs_in sum w^2), i = (k + N / 2) mod N: bin i is at (i - N / 2) fs_in / N Hz, low to
  *     high (F frames; sum w^2 over the fp32 window values, in double; before the first frame the PSD is all zero).
  *     A non-finite sample makes the frames that hold it non-finite, and the PSD stays non-finite until fmd_scan_reset.
+ *     No kernel computes with the absolute index: a call's frames are indexed within its window [history][block] (below 2^32 + N), and
+ *     the host counts samples in an unsigned and frames in a signed 64-bit integer, so the limit is 2^64 input samples (F = 2^57 at
+ *     N = 256): 6.5 million days at 32.768 MSa/s, the highest rate the channeliser accepts at 256 kSa/s (the scanner takes any rate);
+ *     F enters the PSD's scale as a double, exact up to 2^53 frames.
  *  2. detection on the host, a pure function of the PSD in double (fmd_scan_detect): channel power over a raster, SNR against a noise
  *     quantile of the usable band, one detection per station (rules: fmd_scan_params below).
  * ------------------------------------------------------------------------------------------------------------------ */
@@ -497,7 +507,10 @@ const char* fmd_scan_last_error(fmd_scanner h);
  *                           sinc (>= 60 dB from min(fs_in, fs_out) / 2 up, every phase's DC gain 1).  Each channel keeps its
  *                           last T - 1 input frames (zero after a reset); the frame counters are 64-bit, on the host and shared by
  *                           all channels, so fmd_resampler_output_frames is exact.  Fixed fp32 FMA order: a station's outputs do
- *                           not depend on how its input was split into calls, on the batch size or on its row.
+ *                           not depend on how its input was split into calls, on the batch size or on its row.  The counters and
+ *                           every product of them are signed 64-bit; the first to overflow is (frames in) L + M - 1 of the output
+ *                           count (with it n M of the window start and branch) at 2^63, i.e. after 2^63 / L >= 2^51 input frames
+ *                           (L <= 4096): 26 062 days at fs_in = 1 MHz, the highest rate accepted.
  * fs_in == fs_out: either method passes the input through unchanged (ConsumeBuffer, resampled_pcm_player.cpp:17-20).
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct fmd_resampler_s* fmd_resampler;
@@ -603,7 +616,11 @@ const char* fmd_mixer_last_error(fmd_mixer m);
  *                   total + tree(open chunk) and leaves the chunk open.
  *               No floating-point atomics.  For the integer formats every sum is an exact integer while it stays below 2^53: for s16
  *               that is at least 2^23 samples (|v|^2 <= 2^30), for u8 and s8 at least 2^39.  A non-finite sample makes its moments
- *               non-finite until fmd_iqcorr_reset / _reset_moments.
+ *               non-finite until fmd_iqcorr_reset / _reset_moments.  The sample index is an unsigned 64-bit count on the host and a
+ *               signed one in the kernel, whose largest expression is the end of a chunk, (floor(a / 4096) + 1) 4096 <= a + 4096
+ *               (a: the index of a call's first sample): it overflows at 2^63 samples, 3.26 million days at 32.768 MSa/s (the
+ *               corrector takes any rate; this is the highest the channeliser accepts at 256 kSa/s); n is reported as a double,
+ *               exact up to 2^53 samples (3181 days at that rate).
  *   solve       host, double, a pure function of the moments (fmd_iqcorr_solve):
  *                 m = (sum i, sum q) / n;  vii = sum i^2 / n - m_i^2;  vqq = sum q^2 / n - m_q^2;  viq = sum i q / n - m_i m_q
  *                 p = vii + vqq;  c = (vii - vqq) + 2j viq;  s = sqrt(max(0, p^2 - |c|^2));  w = -c / (p + s), w = 0 where p + s <= 0
