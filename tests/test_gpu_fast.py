@@ -176,7 +176,11 @@ def _compare(pkg, caps, bs, fs, from_block=0, sym_skip_s=0.4, **kw):
                 dlt -= np.round(dlt)
                 worst[k] = max(worst[k], rms(dlt))
             else:
-                worst[k] = max(worst[k], rms(a - b))
+                dlt = a - b
+                worst[k] = max(worst[k], rms(dlt))
+            # the largest single-sample error beside the RMS (recorded, not asserted here: tests/test_gpu_fast_seams.py holds the peak bars; of the
+            # flat arrays as the RMS is: per real component of fm_out_iq and per channel of audio, where seam_stats takes |e| of the sample / frame)
+            worst["peak_" + k] = max(worst.get("peak_" + k, 0.0), float(np.max(np.abs(dlt))) if dlt.size else 0.0)
         if np.array_equal(g["rds_count"][c], o["rds_count"]):
             counts_equal += 1
             # ... then the decoder saw the same number of symbols at every block edge: no shift is possible, and whatever differs is a soft symbol
