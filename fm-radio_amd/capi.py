@@ -185,6 +185,17 @@ class PlanInfo(C.Structure):
                                        "front_lds_pad", "front_big_tile", "extract_auto_pair", "pll_kernel")]
 
 
+class PlanFacts(C.Structure):
+    """fmd_plan_facts: what the controls and the debug hooks leave behind."""
+    _fields_ = [(n, C.c_int) for n in ("any_deemph", "deemph_in_tile", "split_front", "uniform_cutoffs", "extract_pairing")]
+
+
+class BlockPlanInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("iq_streams", "front_kernel", "front_input", "front_tile", "front_warmup", "front_workgroups", "front_lds_pad", "predecim_kernel",
+                                       "predecim_tile", "predecim_workgroups", "deemph_pilot_sums", "deemph_workgroups", "pilot_power_rows", "lmr_phase", "extract_tile",
+                                       "extract_bp", "extract_nt", "extract_pair", "extract_grid_x", "rds_kernel", "rds_partials")]
+
+
 PLL_KERNELS = ("low-work", 16, 8)      # fmd_plan_info.pll_kernel (FMD_PLL_KERNEL_*): the low-work kernel, the time-parallel one's lanes a station
 
 
@@ -280,6 +291,7 @@ def load_library():
     L.fmd_debug_pll_adaptive.argtypes = [H, C.c_int, C.c_int]
     L.fmd_debug_extract_pairing.argtypes = [H, C.c_int]
     L.fmd_debug_plan.argtypes = [C.POINTER(Config), C.c_int, C.c_int, C.c_int, C.POINTER(PlanInfo)]
+    L.fmd_debug_block_plan.argtypes = [C.POINTER(Config), C.POINTER(PlanFacts), C.c_int, C.POINTER(BlockPlanInfo)]
     L.fmd_profile_read.argtypes = [H, C.POINTER(KernelTime), C.c_int, C.POINTER(C.c_int)]
     L.fmd_chan_design.argtypes = [C.c_double, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.fmd_chan_default_taps_per_phase.restype = C.c_int
@@ -446,6 +458,16 @@ def plan(cfg: "Config", pll_thresholds=None, unlocked_now: bool = False) -> Plan
     out = PlanInfo()
     k16, tp = (-1, -1) if pll_thresholds is None else pll_thresholds
     rc = load_library().fmd_debug_plan(C.byref(cfg), int(k16), int(tp), 1 if unlocked_now else 0, C.byref(out))
+    if rc != FMD_OK:
+        raise FmdError(rc, "unsupported configuration")
+    return out
+
+
+def block_plan(cfg: "Config", facts: "PlanFacts" = None, u8: bool = False) -> BlockPlanInfo:
+    """fmd_debug_block_plan (host only, no GPU): each stage's kernel form and launch geometry for cfg, for u8 or cf32 captures, given the run-time facts
+    (None: a fresh handle's, no fact set)."""
+    out = BlockPlanInfo()
+    rc = load_library().fmd_debug_block_plan(C.byref(cfg), C.byref(facts if facts is not None else PlanFacts()), 1 if u8 else 0, C.byref(out))
     if rc != FMD_OK:
         raise FmdError(rc, "unsupported configuration")
     return out

@@ -205,8 +205,8 @@ int upload_controls(fmd_handle h, hipStream_t s) {
         }
         HIP_TRY(h, hipMemcpyAsync(b.aud_idx, idx.data(), idx.size() * 4, hipMemcpyHostToDevice, s));
         HIP_TRY(h, hipStreamSynchronize(s));
-        h->ctx.uniform_cutoffs = 1;
-        for (int c = 1; c < C; c++) if (idx[(size_t)c * 2] != idx[0] || idx[(size_t)c * 2 + 1] != idx[1]) { h->ctx.uniform_cutoffs = 0; break; }
+        h->ctx.facts.uniform_cutoffs = true;
+        for (int c = 1; c < C; c++) if (idx[(size_t)c * 2] != idx[0] || idx[(size_t)c * 2 + 1] != idx[1]) { h->ctx.facts.uniform_cutoffs = false; break; }
     }
     HIP_TRY(h, hipMemcpyAsync(b.b_lpr, lpr.data(), lpr.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipMemcpyAsync(b.b_lmr, lmr.data(), lmr.size() * 4, hipMemcpyHostToDevice, s));
@@ -216,15 +216,17 @@ int upload_controls(fmd_handle h, hipStream_t s) {
     // FMD_FLAG_FAST_MATH: the IIR runs inside k_front's tile (no state, no extra stage) unless a channel's time constant is too long
     // for its warm-up; a switch between the two forms (controls changed across ~79 us) restarts the filter from the state the other
     // form last left: a transient of a millisecond on those channels
-    h->ctx.deemph_in_tile = (h->ctx.fast && any && !slow_pole) ? 1 : 0;
-    if (h->ctx.deemph_in_tile) { h->ctx.any_deemph = 0; h->deemph_linger = false; h->deemph_on = false; }
+    PlanFacts& f = h->ctx.facts;
+    f.deemph_in_tile = h->ctx.fast && any && !slow_pole;
+    if (f.deemph_in_tile) { f.any_deemph = false; h->deemph_linger = false; h->deemph_on = false; }
     else {
-        if (any) { h->ctx.any_deemph = 1; h->deemph_linger = false; }
-        else if (h->deemph_on) { h->ctx.any_deemph = 1; h->deemph_linger = true; }
-        else if (!h->deemph_linger) h->ctx.any_deemph = 0;
+        if (any) { f.any_deemph = true; h->deemph_linger = false; }
+        else if (h->deemph_on) { f.any_deemph = true; h->deemph_linger = true; }
+        else if (!h->deemph_linger) f.any_deemph = false;
         h->deemph_on = any != 0;
     }
     h->controls_dirty = false;
+    refresh_block_plan(h->ctx);
     return FMD_OK;
 }
 
@@ -416,7 +418,7 @@ int process_dev(fmd_handle h, const InT* d_iq, int n_channels, int n_samples, vo
     }
     BlockFacts f;
     f.ordered = ordered; f.have_stream = s != nullptr;
-    f.any_deemph = h->ctx.any_deemph != 0; f.deemph_in_tile = h->ctx.deemph_in_tile != 0; f.split_front = h->ctx.split_front != 0;
+    f.any_deemph = h->ctx.facts.any_deemph; f.deemph_in_tile = h->ctx.facts.deemph_in_tile; f.split_front = h->ctx.facts.split_front;
     if (h->sched.profiling()) {
         ProfiledBlock* pm = new ProfiledBlock();
         for (int i = 0; i < ST_COUNT; i++) { pm->used[i] = false; HIP_TRY(h, hipEventCreate(&pm->t0[i])); HIP_TRY(h, hipEventCreate(&pm->t1[i])); }
@@ -432,7 +434,7 @@ int process_dev(fmd_handle h, const InT* d_iq, int n_channels, int n_samples, vo
     }
     HipBackend be(h, s, d_iq, sizeof(InT) == 2);
     { int rc = sched_rc(h, h->sched.submit(f, be)); if (rc) return rc; }
-    if (h->deemph_linger) { h->deemph_linger = false; h->ctx.any_deemph = 0; }
+    if (h->deemph_linger) { h->deemph_linger = false; h->ctx.facts.any_deemph = false; refresh_block_plan(h->ctx); }      // (launches only read the plan while they are queued)
     h->last_stream = s;
     poison.armed = false;
     return FMD_OK;
@@ -552,6 +554,7 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
     h->ctx.d = dims_of(*cfg, m);
     const Dims& d = h->ctx.d;
     h->ctx.plan = make_plan(d.C, d.m, d.n_fm_out, d.n_est, cfg->flags);
+    refresh_block_plan(h->ctx);
     h->ctx.pll_unlocked_now = false; h->ctx.pll_launch_no = 0;
     h->bytes_cap = 16 * (d.n_rds / 256 + 1);
     h->ctx.bytes_cap = h->bytes_cap;
@@ -576,9 +579,9 @@ int fmd_create(const fmd_config* cfg, fmd_handle* out) {
         if (!rc) rc = dev_alloc(h, &b.fo_tail[p], C * 64);
     }
     // Tolerance mode: fm_out as a plane (rows with the previous block's tail in front) and the NCO phase as span polynomials; the interleaved / per-sample streams
-    // only for FMD_FLAG_KEEP_TAPS (the getters) and for block lengths that run k_extract<128> (audio blocks not multiples of 256)
+    // only for FMD_FLAG_KEEP_TAPS (the getters) and for block lengths that run k_extract<128> (BlockPlan::iq_streams: no fact changes it)
     const bool fast = h->ctx.fast != 0;
-    const bool streams = !fast || h->ctx.keep_taps || (d.n_audio % 256) != 0;
+    const bool streams = h->ctx.block.iq_streams;
     for (int p = 0; p < kSlots && !rc; p++) {
         if (streams) rc = dev_alloc(h, &b.fm_out_iq[p], C * d.n_fm_out);
         if (!rc && m > 1) rc = dev_alloc(h, &b.fm_in[p], C * d.n_fm_in);
@@ -703,7 +706,7 @@ int fmd_reset(fmd_handle h) {
     int rc = zero_history(h, h->own_stream);
     if (rc) return rc;
     HIP_TRY(h, hipStreamSynchronize(h->own_stream));
-    h->deemph_on = false; h->deemph_linger = false; h->ctx.any_deemph = 0;
+    h->deemph_on = false; h->deemph_linger = false; h->ctx.facts.any_deemph = false;
     h->controls_dirty = true;
     return FMD_OK;
 }
@@ -1166,7 +1169,8 @@ int fmd_debug_split_front(fmd_handle h, int on) {
     if (!h) return FMD_ERR_ARG;
     int rc = fmd_synchronize(h);
     if (rc) return rc;
-    h->ctx.split_front = on != 0;
+    h->ctx.facts.split_front = on != 0;
+    refresh_block_plan(h->ctx);
     return FMD_OK;
 }
 
@@ -1178,6 +1182,7 @@ int fmd_debug_pll_adaptive(fmd_handle h, int k16_max_channels, int time_parallel
     const Dims& d = h->ctx.d;
     const PllThresholds moved{k16_max_channels, time_parallel_max_channels};
     h->ctx.plan = make_plan(d.C, d.m, d.n_fm_out, d.n_est, h->cfg.flags, &moved);
+    refresh_block_plan(h->ctx);
     h->ctx.pll_unlocked_now = false;
     return FMD_OK;
 }
@@ -1195,11 +1200,28 @@ int fmd_debug_plan(const fmd_config* cfg, int k16_max_channels, int time_paralle
     return FMD_OK;
 }
 
+int fmd_debug_block_plan(const fmd_config* cfg, const fmd_plan_facts* facts, int u8, fmd_block_plan_info* out) {
+    int m = 0;
+    if (!out || !facts || !config_ok(cfg, &m) || facts->extract_pairing < 0 || facts->extract_pairing > 2) return FMD_ERR_ARG;
+    const Dims d = dims_of(*cfg, m);
+    const Plan p = make_plan(d.C, d.m, d.n_fm_out, d.n_est, cfg->flags);
+    PlanFacts f;
+    f.any_deemph = facts->any_deemph != 0; f.deemph_in_tile = facts->deemph_in_tile != 0; f.split_front = facts->split_front != 0;
+    f.uniform_cutoffs = facts->uniform_cutoffs != 0; f.extract_pairing = facts->extract_pairing;
+    const BlockPlan b = make_block_plan(p, f);
+    const BlockPlan::Input& in = b.in[u8 != 0];
+    *out = fmd_block_plan_info{b.iq_streams, (int)b.front, (int)in.front_input, in.front_tile, b.front_warmup, in.front_workgroups, b.front_lds_pad,
+                               (int)in.predecim, in.predecim_tile, in.predecim_workgroups, b.deemph_pilot_sums, b.deemph_workgroups, p.power_rows,
+                               (int)b.lmr_phase, b.extract_tile, b.extract_bp, b.extract_nt, b.extract_pair, b.extract_grid_x, (int)b.rds, b.rds_partials};
+    return FMD_OK;
+}
+
 int fmd_debug_extract_pairing(fmd_handle h, int mode) {
     if (!h || mode < 0 || mode > 2) return FMD_ERR_ARG;
     int rc = fmd_synchronize(h);
     if (rc) return rc;
-    h->ctx.extract_pairing = mode;
+    h->ctx.facts.extract_pairing = mode;
+    refresh_block_plan(h->ctx);
     return FMD_OK;
 }
 
@@ -1220,9 +1242,7 @@ int fmd_profile_read(fmd_handle h, fmd_kernel_time* out, int cap, int* n_out) {
             float ms = 0.0f;
             HIP_TRY(h, hipEventElapsedTime(&ms, pm->t0[i], pm->t1[i]));
             int slot = -1;
-            const char* nm = h->ctx.fast ? kStageNameFast[i] : kStageName[i];
-            if (h->ctx.fast && i == ST_EXTRACT && h->ctx.d.n_audio % 256 == 0) nm = "k_extract_bp";      // (round 5: fmd_kernels_bp.inc)
-            if (i == ST_FRONT && front_takes_capture(h->ctx)) nm = "k_front_pre_mfma";
+            const char* nm = h->ctx.block.stage_name[i];
             for (int j = 0; j < n; j++) if (std::strncmp(out[j].name, nm, sizeof(out[j].name)) == 0) { slot = j; break; }
             if (slot < 0) {
                 if (n >= cap) continue;

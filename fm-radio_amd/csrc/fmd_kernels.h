@@ -192,18 +192,23 @@ struct LaunchCtx {
     LoopCoeffs loops;
     int keep_taps;
     int fast;                             // FMD_FLAG_FAST_MATH: the tolerance-mode kernels
-    int any_deemph;
-    int deemph_in_tile;     // FMD_FLAG_FAST_MATH: the de-emphasis IIR runs inside k_front's tile (every filtering channel's pole <= 0.905, i.e. up to ~79 us)
-    int split_front;        // fmd_debug_split_front: 1.024 / 2.048 MSa/s tolerance mode with k_predecim_mfma and k_front_mfma as two kernels (the parity check of k_front_pre_mfma)
     int bytes_cap;
     int rds_decode;                       // FMD_FLAG_RDS_DECODE: k_rds_decode behind k_rds_sync (state in rds_dec)
     RdsDecBufs rds_dec;
-    int uniform_cutoffs;                  // every station has the same L+R / L-R cut-offs: one set of k_extract_bp's tap tables serves any of them
-    int extract_pairing;                  // k_extract_bp with two stations per workgroup: 0 = where it pays (launch_extract_ta), 1 = wherever possible (tests), 2 = never
     Plan plan;                            // which kernels this batch gets (fmd_plan.h): made once, by fmd_create
+    PlanFacts facts;                      // what the controls and the debug hooks have set; whoever changes one calls refresh_block_plan
+    BlockPlan block;                      // each stage's kernel form and launch geometry, from plan and facts: the launchers read it and decide nothing
+    Dims d_front;                         // the block as k_front / k_front_mfma see it: a 256 kSa/s batch (behind the first decimator: N = n_fm_in, m = 1)
     unsigned pll_launch_no;               // 1-based number of the pilot-PLL launch being queued (exact mode)
     bool pll_unlocked_now;                // wavefronts ran out of lock in the last blocks the host has seen (fmd_api.cpp): pll_kernel()'s second argument
 };
+
+// After fmd_create, a control upload or a debug hook (everything idle): ctx.plan or ctx.facts may have changed
+inline void refresh_block_plan(LaunchCtx& ctx) {
+    ctx.block = make_block_plan(ctx.plan, ctx.facts);
+    ctx.d_front = ctx.d;
+    if (ctx.d.m > 1) { ctx.d_front.N = ctx.d.n_fm_in; ctx.d_front.m = 1; }
+}
 
 // where a slot's traces lie inside Buffers::taps[buf] (null pointers when the handle keeps none)
 inline TapPtrs tap_ptrs(const LaunchCtx& ctx, int buf) {
@@ -232,8 +237,7 @@ inline size_t tap_floats(const Dims& d) { return (size_t)d.C * (6 * (size_t)d.n_
 hipError_t launch_stage_predecim(const LaunchCtx& ctx, SlotRef r, const void* d_iq, bool u8, hipStream_t s);   // k_predecim (m > 1)
 // pll != NULL (tolerance mode only): the pilot stage of the block in slot pll->buf rides in the same launch (k_front_mfma<..., FUSED>)
 hipError_t launch_stage_front(const LaunchCtx& ctx, SlotRef r, const void* d_iq, bool u8, hipStream_t s, const SlotRef* pll = nullptr);   // k_front
-// m > 1: the first decimator runs inside launch_stage_front's kernel (no predecim stage for this block)
-inline bool front_takes_capture(const LaunchCtx& ctx) { return front_takes_capture(ctx.d.m, ctx.fast != 0, ctx.any_deemph != 0, ctx.deemph_in_tile != 0, ctx.d.n_fm_out, ctx.split_front != 0); }
+// (m > 1, BlockPlan::front == FrontPreMfma: the first decimator runs inside launch_stage_front's kernel and the block has no predecim stage)
 hipError_t launch_stage_deemph(const LaunchCtx& ctx, SlotRef r, hipStream_t s);                            // k_deemphasis + k_hilbert
 hipError_t launch_stage_power(const LaunchCtx& ctx, SlotRef r, hipStream_t s);                             // k_pilot_power
 hipError_t launch_stage_pll(const LaunchCtx& ctx, SlotRef r, hipStream_t s);                               // k_pilot_pll

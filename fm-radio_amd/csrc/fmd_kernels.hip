@@ -3005,130 +3005,115 @@ __global__ void k_reset(Dims d, float* __restrict__ state) {
 
 // ---------------------------------------------------------------------------------------------
 // host-side stage launchers
+// They decide nothing: which kernel form a stage gets, its tile and its workgroup count are LaunchCtx::block (fmd_plan.h BlockPlan, made by
+// refresh_block_plan whenever something it depends on can have changed); the one choice made per block is pll_kernel().  A launcher turns those
+// fields into template parameters (with_constant) and spells each kernel's argument list once.
 // ---------------------------------------------------------------------------------------------
-template <typename InT, int TT = 512, bool FAST = false>
-static hipError_t launch_front(const LaunchCtx& ctx, SlotRef r, const InT* d_iq, hipStream_t s, const SlotRef* pll = nullptr) {
-    using G = FrontGeom<TT>;
-    const Dims& d = ctx.d;
-    if constexpr (!FAST) {
-        if (ctx.fast) return launch_front<InT, TT, true>(ctx, r, d_iq, s, pll);
-    }
-    if constexpr (TT == 512) {
-        if constexpr (FAST && sizeof(InT) == 8) {
-            // cf32 captures: 2048-output tiles for the batches of kFrontBigTileMinWorkgroups
-            if (ctx.plan.front_big_tile && d.n_fm_out % 2048 == 0 && !ctx.deemph_in_tile) return launch_front<InT, 2048, FAST>(ctx, r, d_iq, s, pll);
-        }
-        if constexpr (FAST && sizeof(InT) == 2) {   // u8 captures: 2048-output tiles (4 KB of input per 1024-output workgroup leaves too few bytes in flight per CU)
-            if (d.n_fm_out % 2048 == 0 && !ctx.deemph_in_tile) return launch_front<InT, 2048, FAST>(ctx, r, d_iq, s, pll);
-        }
-        if (d.n_fm_out % 1024 == 0) return launch_front<InT, 1024, FAST>(ctx, r, d_iq, s, pll);
-    }
-    const int tiles = d.n_fm_out / G::T;
-    if constexpr (FAST) {   // tolerance mode: k_front_mfma; with the de-emphasis IIR inside the tile when a channel asks for it
-        PllFusedArgs pf{};
-        if (pll) {          // the pilot stage of the block in slot pll->buf as this launch's first workgroups
-            const int nxt = (pll->buf + 1) % kSlots;
-            pf = PllFusedArgs{(d.C + 31) / 32, ctx.b.pv_pl[pll->buf], ctx.b.pv_hist[pll->par], ctx.b.pv_hist[pll->par ^ 1], ctx.b.fo_pl[pll->buf], ctx.b.fo_pl[nxt],
-                              ctx.b.pll_poly[pll->buf], ctx.b.pll_poly[nxt], ctx.b.state, ctx.loops, ctx.b.sparse_tab, ctx.b.spec_stats};
-        }
-        const unsigned grid = (unsigned)(tiles * d.C + pf.n_wg);
-        if (ctx.deemph_in_tile) {
-            using GM = FrontGeomM<TT, kDeemphWarmup>;
-            if (pll) FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, kDeemphWarmup, true>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + ctx.plan.front_lds_pad, s, d, d_iq,
-                                ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1], ctx.b.fo_pl[r.buf], ctx.front.fm_gain, ctx.b.deemph, ctx.b.front_mfma, ctx.b.pv_pl[r.buf], ctx.b.sparse_tab, pf);
-            else FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, kDeemphWarmup, false>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + ctx.plan.front_lds_pad, s, d, d_iq,
-                            ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1], ctx.b.fo_pl[r.buf], ctx.front.fm_gain, ctx.b.deemph, ctx.b.front_mfma, ctx.b.pv_pl[r.buf], ctx.b.sparse_tab, pf);
-        } else {
-            using GM = FrontGeomM<TT, 0>;
-            if (pll) FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, 0, true>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + ctx.plan.front_lds_pad, s, d, d_iq,
-                                ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1], ctx.b.fo_pl[r.buf], ctx.front.fm_gain, ctx.b.deemph, ctx.b.front_mfma, ctx.b.pv_pl[r.buf], ctx.b.sparse_tab, pf);
-            else FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, 0, false>), dim3(grid), dim3(256), sizeof(float) * GM::LDS_FLOATS + ctx.plan.front_lds_pad, s, d, d_iq,
-                            ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1], ctx.b.fo_pl[r.buf], ctx.front.fm_gain, ctx.b.deemph, ctx.b.front_mfma, ctx.b.pv_pl[r.buf], ctx.b.sparse_tab, pf);
-        }
-        return hipGetLastError();
-    }
-    const size_t lds = sizeof(float) * G::LDS_FLOATS;
-    auto kern = k_front<InT, TT>;
-    FMD_LAUNCH(r, true, true, kern, dim3((unsigned)(tiles * d.C)), dim3(256), lds, s, d, d_iq, ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1],
-                       ctx.b.fm_out_iq[r.buf], ctx.b.fm_out[r.buf], ctx.b.fo_tail[r.par ^ 1], ctx.front, ctx.any_deemph);
-    return hipGetLastError();
+// A run-time value as a template parameter: f(std::integral_constant<int, V>{}) for the V of the list that v equals; false if it equals none
+template <int... Vs, typename F>
+static bool with_constant(int v, F&& f) { return ((v == Vs ? (f(std::integral_constant<int, Vs>{}), true) : false) || ...); }
+// a launch, or the error for a form no kernel was built for (a plan the launchers do not know: never a silent fall-back)
+static hipError_t launched(bool found) { return found ? hipGetLastError() : hipErrorInvalidConfiguration; }
+
+static_assert(kDeemphWarmup == kFrontDeemphWarmup && PredecimGeom<4>::TP == 512 && PredecimGeom<8>::TP == 512, "fmd_plan.cpp's geometry");
+
+// the pilot stage of the block in slot pll->buf as the first workgroups of a front-end launch (none: n_wg = 0)
+static PllFusedArgs fused_pilot_args(const LaunchCtx& ctx, const SlotRef* pll) {
+    if (!pll) return PllFusedArgs{};
+    const Buffers& b = ctx.b;
+    const int nxt = (pll->buf + 1) % kSlots;
+    return PllFusedArgs{(ctx.d.C + 31) / 32, b.pv_pl[pll->buf], b.pv_hist[pll->par], b.pv_hist[pll->par ^ 1], b.fo_pl[pll->buf], b.fo_pl[nxt],
+                        b.pll_poly[pll->buf], b.pll_poly[nxt], b.state, ctx.loops, b.sparse_tab, b.spec_stats};
 }
 
-template <int M, typename InT>
-static hipError_t launch_predecim(const LaunchCtx& ctx, SlotRef r, const InT* d_iq, hipStream_t s) {
-    const Dims& d = ctx.d;
-    using G = PredecimGeom<M>;
-    // tile: 2048 input samples of cf32 (16 KB; the kernel then sits on its HBM floor whatever the tile), 8192 of u8 (16 KB as well:
-    // with 4 KB per workgroup too few bytes are in flight per CU); blocks that are no multiple of it: 256 outputs per workgroup
-    constexpr int TPM = (sizeof(InT) == 2 ? 8192 : 2048) / M;
-    if (ctx.fast && d.n_fm_in % TPM != 0 && d.n_fm_in % 256 == 0) {
-        FMD_LAUNCH(r, true, true, (k_predecim_mfma<M, InT, 256>), dim3((unsigned)(d.n_fm_in / 256 * d.C)), dim3(256), 0, s, d, d_iq, ctx.b.pre_tail[r.par], ctx.b.pre_tail[r.par ^ 1],
-                   reinterpret_cast<float*>(ctx.b.fm_in[r.buf]), ctx.b.front_mfma + kFrontImgU4);
-    } else if (ctx.fast && d.n_fm_in % TPM == 0) {
-        FMD_LAUNCH(r, true, true, (k_predecim_mfma<M, InT, TPM>), dim3((unsigned)(d.n_fm_in / TPM * d.C)), dim3(256), 0, s, d, d_iq, ctx.b.pre_tail[r.par], ctx.b.pre_tail[r.par ^ 1],
-                   reinterpret_cast<float*>(ctx.b.fm_in[r.buf]), ctx.b.front_mfma + kFrontImgU4);
-    } else if (ctx.fast)
-        FMD_LAUNCH(r, true, true, (k_predecim<M, InT, true>), dim3((unsigned)(d.n_fm_in / G::TP * d.C)), dim3(256), 0, s, d, d_iq, ctx.b.pre_tail[r.par], ctx.b.pre_tail[r.par ^ 1],
-                   ctx.b.fm_in[r.buf], ctx.front);
-    else
-        FMD_LAUNCH(r, true, true, (k_predecim<M, InT, false>), dim3((unsigned)(d.n_fm_in / G::TP * d.C)), dim3(256), 0, s, d, d_iq, ctx.b.pre_tail[r.par], ctx.b.pre_tail[r.par ^ 1],
-                   ctx.b.fm_in[r.buf], ctx.front);
-    return hipGetLastError();
+// the tiles a front-end kernel is built with for input InT: no 2048 behind the first decimator
+template <typename InT, typename F>
+static bool with_front_tile(int tile, F&& f) {
+    if constexpr (sizeof(InT) == 4) return with_constant<512, 1024>(tile, f);
+    else return with_constant<512, 1024, 2048>(tile, f);
 }
 
-// the first decimator (m > 1 only): baseband -> fm_in[slot]
-hipError_t launch_stage_predecim(const LaunchCtx& ctx, SlotRef r, const void* d_iq, bool u8, hipStream_t s) {
-    const int m = ctx.d.m;
-    if (u8) {
-        const uchar2* p = static_cast<const uchar2*>(d_iq);
-        return m == 4 ? launch_predecim<4, uchar2>(ctx, r, p, s) : launch_predecim<8, uchar2>(ctx, r, p, s);
+// k_front / k_front_mfma on a 256 kSa/s stream: the capture itself or fm_in[slot] (InT = float: as phases)
+template <typename InT>
+static hipError_t launch_front(const LaunchCtx& ctx, const BlockPlan::Input& in, SlotRef r, const InT* d_iq, hipStream_t s, const SlotRef* pll) {
+    const BlockPlan& bp = ctx.block;
+    const Buffers& b = ctx.b;
+    const Dims& d = ctx.d_front;
+    if (bp.front == FrontKernel::FrontMfma) {   // tolerance mode; with the de-emphasis IIR inside the tile when a channel asks for it
+        const PllFusedArgs pf = fused_pilot_args(ctx, pll);
+        return launched(with_front_tile<InT>(in.front_tile, [&](auto tt) { with_constant<0, kDeemphWarmup>(bp.front_warmup, [&](auto wu) { with_constant<0, 1>(pll != nullptr, [&](auto fused) {
+            constexpr int TT = decltype(tt)::value, WU = decltype(wu)::value;
+            using G = FrontGeomM<TT, WU>;
+            FMD_LAUNCH(r, true, true, (k_front_mfma<InT, TT, WU, decltype(fused)::value != 0>), dim3((unsigned)(in.front_workgroups + pf.n_wg)), dim3(256),
+                       sizeof(float) * G::LDS_FLOATS + bp.front_lds_pad, s, d, d_iq, b.base_tail[r.par], b.base_tail[r.par ^ 1], b.fo_pl[r.buf], ctx.front.fm_gain,
+                       b.deemph, b.front_mfma, b.pv_pl[r.buf], b.sparse_tab, pf);
+        }); }); }));
     }
-    const float2* p = static_cast<const float2*>(d_iq);
-    return m == 4 ? launch_predecim<4, float2>(ctx, r, p, s) : launch_predecim<8, float2>(ctx, r, p, s);
+    // (k_front<InT, 2048> is built, so that the code object stays what it is, but no plan asks for it)
+    return launched(with_front_tile<InT>(in.front_tile, [&](auto tt) {
+        constexpr int TT = decltype(tt)::value;
+        FMD_LAUNCH(r, true, true, (k_front<InT, TT>), dim3((unsigned)in.front_workgroups), dim3(256), sizeof(float) * FrontGeom<TT>::LDS_FLOATS, s, d, d_iq, b.base_tail[r.par],
+                   b.base_tail[r.par ^ 1], b.fm_out_iq[r.buf], b.fm_out[r.buf], b.fo_tail[r.par ^ 1], ctx.front, ctx.facts.any_deemph ? 1 : 0);
+    }));
 }
 
 // 1.024 / 2.048 MSa/s, tolerance mode: the first decimator inside the front end's kernel (k_front_pre_mfma) — the block then has no
 // predecim stage and launch_stage_front takes the capture.  Not with a de-emphasised station (k_front_mfma's WU form stays on fm_in).
 template <int M, typename InT>
-static hipError_t launch_front_pre(const LaunchCtx& ctx, SlotRef r, const InT* d_iq, hipStream_t s, const SlotRef* pll) {
+static void launch_front_pre(const LaunchCtx& ctx, const BlockPlan::Input& in, SlotRef r, const InT* d_iq, hipStream_t s, const SlotRef* pll) {
     using G = FrontPreGeom<M, sizeof(InT) == 2>;
-    const Dims& d = ctx.d;
-    PllFusedArgs pf{};
-    if (pll) {
-        const int nxt = (pll->buf + 1) % kSlots;
-        pf = PllFusedArgs{(d.C + 31) / 32, ctx.b.pv_pl[pll->buf], ctx.b.pv_hist[pll->par], ctx.b.pv_hist[pll->par ^ 1], ctx.b.fo_pl[pll->buf], ctx.b.fo_pl[nxt],
-                          ctx.b.pll_poly[pll->buf], ctx.b.pll_poly[nxt], ctx.b.state, ctx.loops, ctx.b.sparse_tab, ctx.b.spec_stats};
-    }
-    const unsigned grid = (unsigned)(d.n_fm_out / 1024 * d.C + pf.n_wg);
-    if (pll) FMD_LAUNCH(r, true, true, (k_front_pre_mfma<M, InT, true>), dim3(grid), dim3(256), sizeof(float) * G::LDS_WORDS, s, d, d_iq, ctx.b.pre_tail[r.par], ctx.b.pre_tail[r.par ^ 1],
-                        ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1], ctx.b.fo_pl[r.buf], ctx.front.fm_gain, ctx.b.front_mfma + kFrontImgU4, ctx.b.front_mfma,
-                        ctx.b.pv_pl[r.buf], ctx.b.sparse_tab, pf);
-    else FMD_LAUNCH(r, true, true, (k_front_pre_mfma<M, InT, false>), dim3(grid), dim3(256), sizeof(float) * G::LDS_WORDS, s, d, d_iq, ctx.b.pre_tail[r.par], ctx.b.pre_tail[r.par ^ 1],
-                    ctx.b.base_tail[r.par], ctx.b.base_tail[r.par ^ 1], ctx.b.fo_pl[r.buf], ctx.front.fm_gain, ctx.b.front_mfma + kFrontImgU4, ctx.b.front_mfma,
-                    ctx.b.pv_pl[r.buf], ctx.b.sparse_tab, pf);
-    return hipGetLastError();
+    const Buffers& b = ctx.b;
+    const PllFusedArgs pf = fused_pilot_args(ctx, pll);
+    with_constant<0, 1>(pll != nullptr, [&](auto fused) {
+        FMD_LAUNCH(r, true, true, (k_front_pre_mfma<M, InT, decltype(fused)::value != 0>), dim3((unsigned)(in.front_workgroups + pf.n_wg)), dim3(256), sizeof(float) * G::LDS_WORDS, s, ctx.d, d_iq,
+                   b.pre_tail[r.par], b.pre_tail[r.par ^ 1], b.base_tail[r.par], b.base_tail[r.par ^ 1], b.fo_pl[r.buf], ctx.front.fm_gain, b.front_mfma + kFrontImgU4, b.front_mfma,
+                   b.pv_pl[r.buf], b.sparse_tab, pf);
+    });
 }
 
-// k_front on the 256 kSa/s stream: the capture itself (m == 1) or fm_in[slot]
+template <int M, typename InT>
+static void launch_predecim(const LaunchCtx& ctx, const BlockPlan::Input& in, SlotRef r, const InT* d_iq, hipStream_t s) {
+    const Buffers& b = ctx.b;
+    const dim3 grid((unsigned)in.predecim_workgroups);
+    if (in.predecim == PredecimKernel::Mfma) {
+        with_constant<256, (sizeof(InT) == 2 ? 8192 : 2048) / M>(in.predecim_tile, [&](auto tp) {
+            FMD_LAUNCH(r, true, true, (k_predecim_mfma<M, InT, decltype(tp)::value>), grid, dim3(256), 0, s, ctx.d, d_iq, b.pre_tail[r.par], b.pre_tail[r.par ^ 1],
+                       reinterpret_cast<float*>(b.fm_in[r.buf]), b.front_mfma + kFrontImgU4);
+        });
+    } else {
+        with_constant<0, 1>(in.predecim == PredecimKernel::Phases, [&](auto phases) {
+            FMD_LAUNCH(r, true, true, (k_predecim<M, InT, decltype(phases)::value != 0>), grid, dim3(256), 0, s, ctx.d, d_iq, b.pre_tail[r.par], b.pre_tail[r.par ^ 1], b.fm_in[r.buf], ctx.front);
+        });
+    }
+}
+
+// the capture as the kernels that read it are built: M = 4, 8 x cf32, u8
+template <typename F>
+static bool with_capture(const LaunchCtx& ctx, const void* d_iq, bool u8, F&& f) {
+    return with_constant<4, 8>(ctx.d.m, [&](auto mm) {
+        if (u8) f(mm, static_cast<const uchar2*>(d_iq));
+        else f(mm, static_cast<const float2*>(d_iq));
+    });
+}
+
+// the first decimator (m > 1 only): baseband -> fm_in[slot]
+hipError_t launch_stage_predecim(const LaunchCtx& ctx, SlotRef r, const void* d_iq, bool u8, hipStream_t s) {
+    const BlockPlan::Input& in = ctx.block.in[u8];
+    return launched(in.predecim != PredecimKernel::None && with_capture(ctx, d_iq, u8, [&](auto mm, auto* p) { launch_predecim<decltype(mm)::value>(ctx, in, r, p, s); }));
+}
+
+// the front end: on the capture itself, or behind launch_stage_predecim on fm_in[slot]
 hipError_t launch_stage_front(const LaunchCtx& ctx, SlotRef r, const void* d_iq, bool u8, hipStream_t s, const SlotRef* pll) {
-    if (front_takes_capture(ctx)) {
-        const int m = ctx.d.m;
-        if (u8) {
-            const uchar2* p = static_cast<const uchar2*>(d_iq);
-            return m == 4 ? launch_front_pre<4, uchar2>(ctx, r, p, s, pll) : launch_front_pre<8, uchar2>(ctx, r, p, s, pll);
-        }
-        const float2* p = static_cast<const float2*>(d_iq);
-        return m == 4 ? launch_front_pre<4, float2>(ctx, r, p, s, pll) : launch_front_pre<8, float2>(ctx, r, p, s, pll);
+    const BlockPlan::Input& in = ctx.block.in[u8];
+    if (ctx.block.front == FrontKernel::FrontPreMfma)
+        return launched(with_capture(ctx, d_iq, u8, [&](auto mm, auto* p) { launch_front_pre<decltype(mm)::value>(ctx, in, r, p, s, pll); }));
+    switch (in.front_input) {
+        case FrontInput::Phases: return launch_front(ctx, in, r, reinterpret_cast<const float*>(ctx.b.fm_in[r.buf]), s, pll);   // (k_predecim_mfma's output)
+        case FrontInput::FmIn: return launch_front(ctx, in, r, static_cast<const float2*>(ctx.b.fm_in[r.buf]), s, nullptr);
+        case FrontInput::U8: return launch_front(ctx, in, r, static_cast<const uchar2*>(d_iq), s, pll);
+        case FrontInput::Cf32: return launch_front(ctx, in, r, static_cast<const float2*>(d_iq), s, pll);
     }
-    if (ctx.d.m > 1) {
-        LaunchCtx c1 = ctx;
-        c1.d.N = ctx.d.n_fm_in; c1.d.m = 1;
-        c1.plan.front_lds_pad = front_lds_pad(c1.d.C, c1.d.m);      // (the front end sees a 256 kSa/s batch: the pad goes by the station count alone)
-        if (ctx.fast) return launch_front<float>(c1, r, reinterpret_cast<const float*>(ctx.b.fm_in[r.buf]), s, pll);   // (phases: k_predecim<.., true>)
-        return launch_front<float2>(c1, r, ctx.b.fm_in[r.buf], s);
-    }
-    if (u8) return launch_front<uchar2>(ctx, r, static_cast<const uchar2*>(d_iq), s, pll);
-    return launch_front<float2>(ctx, r, static_cast<const float2*>(d_iq), s, pll);
+    return hipErrorInvalidConfiguration;
 }
 
 static unsigned serial_waves(const Dims& d) { return (unsigned)((d.C + kWave - 1) / kWave); }
@@ -3136,35 +3121,30 @@ static unsigned serial_waves(const Dims& d) { return (unsigned)((d.C + kWave - 1
 hipError_t launch_stage_deemph(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
     const Dims& d = ctx.d;
     const Buffers& b = ctx.b;
-    if (ctx.fast) {   // a time constant beyond the in-tile form: in place on the plane (rows: kFoPad samples of history in front of the block)
+    const dim3 grid((unsigned)ctx.block.deemph_workgroups);
+    if (ctx.block.deemph_pilot_sums) {   // a time constant beyond the in-tile form: in place on the plane (rows: kFoPad samples of history in front of the block)
         FMD_LAUNCH(r, true, false, k_deemphasis, dim3(serial_waves(d)), dim3(2 * kWave), 0, s, d, b.fo_pl[r.buf] + kFoPad, b.deemph, b.state, kFoPad + d.n_fm_out);
-        const int ncol = d.n_fm_out / kSparseDec;
-        FMD_LAUNCH(r, false, true, k_pilot_sums, dim3((unsigned)(d.C * ((ncol + 63) / 64))), dim3(256), 0, s, d, b.fo_pl[r.buf], b.pv_pl[r.buf], b.sparse_tab);
+        FMD_LAUNCH(r, false, true, k_pilot_sums, grid, dim3(256), 0, s, d, b.fo_pl[r.buf], b.pv_pl[r.buf], b.sparse_tab);
         return hipGetLastError();
     }
     FMD_LAUNCH(r, true, false, k_deemphasis, dim3(serial_waves(d)), dim3(2 * kWave), 0, s, d, b.fm_out[r.buf], b.deemph, b.state, d.n_fm_out);
-    FMD_LAUNCH(r, false, true, k_hilbert, dim3((unsigned)(d.n_fm_out / 256 * d.C)), dim3(256), 0, s, d, b.fm_out[r.buf], b.fo_tail[r.par],
-                       b.fo_tail[r.par ^ 1], b.fm_out_iq[r.buf], ctx.front);
+    FMD_LAUNCH(r, false, true, k_hilbert, grid, dim3(256), 0, s, d, b.fm_out[r.buf], b.fo_tail[r.par], b.fo_tail[r.par ^ 1], b.fm_out_iq[r.buf], ctx.front);
     return hipGetLastError();
 }
 
 hipError_t launch_stage_power(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
     const Dims& d = ctx.d;
-    if (ctx.plan.power_rows) {
-        FMD_LAUNCH(r, true, true, k_pilot_power<true>, dim3(serial_waves(d)), dim3(kWave), 0, s, d, ctx.b.fm_out_iq[r.buf], ctx.b.pilot[r.buf], ctx.b.state,
+    return launched(with_constant<0, 1>(ctx.plan.power_rows, [&](auto rows) {
+        FMD_LAUNCH(r, true, true, k_pilot_power<decltype(rows)::value != 0>, dim3(serial_waves(d)), dim3(kWave), 0, s, d, ctx.b.fm_out_iq[r.buf], ctx.b.pilot[r.buf], ctx.b.state,
                    ctx.loops, (int)S_PILOT_POWER0 + r.buf);
-    } else {
-        FMD_LAUNCH(r, true, true, k_pilot_power<false>, dim3(serial_waves(d)), dim3(kWave), 0, s, d, ctx.b.fm_out_iq[r.buf], ctx.b.pilot[r.buf], ctx.b.state,
-                   ctx.loops, (int)S_PILOT_POWER0 + r.buf);
-    }
-    return hipGetLastError();
+    }));
 }
 
 hipError_t launch_stage_pll(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
     const Dims& d = ctx.d;
     if (ctx.fast) {
         const int nxt = (r.buf + 1) % kSlots;
-        const bool iq = ctx.b.fm_out_iq[r.buf] != nullptr;    // FMD_FLAG_KEEP_TAPS, or audio blocks that are not multiples of 256: the interleaved streams too
+        const bool iq = ctx.block.iq_streams;    // FMD_FLAG_KEEP_TAPS, or audio blocks that are not multiples of 256: the interleaved streams too
         // k_pll_sparse: 8 stations per wavefront, 4 wavefronts per workgroup.  In a block inside some station's start-up transient (r.warm)
         // k_pll_span runs behind it and takes those stations (fmd_kernels_fast.inc)
         FMD_LAUNCH(r, true, !iq && !r.warm, k_pll_sparse, dim3((unsigned)((d.C + 31) / 32)), dim3(4 * kWave), 0, s, d, ctx.b.pv_pl[r.buf], ctx.b.pv_hist[r.par], ctx.b.pv_hist[r.par ^ 1],
@@ -3186,81 +3166,56 @@ hipError_t launch_stage_pll(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
         return hipGetLastError();
     }
     unsigned int* chain = r.seq ? ctx.b.pll_chain : nullptr;
-    if (kernel == PllKernel::TimeParallel16) {
-        FMD_LAUNCH(r, true, true, k_pilot_pll<16>, dim3((unsigned)((d.C + 3) / 4)), dim3(kWave), 0, s, d, ctx.b.pilot[r.buf], ctx.b.pll_dt[r.buf], ctx.b.state,
+    return launched(with_constant<16, 8>(kernel == PllKernel::TimeParallel16 ? 16 : 8, [&](auto lanes) {
+        constexpr int K = decltype(lanes)::value, per_wave = kWave / K;     // stations a wavefront holds
+        FMD_LAUNCH(r, true, true, k_pilot_pll<K>, dim3((unsigned)((d.C + per_wave - 1) / per_wave)), dim3(kWave), 0, s, d, ctx.b.pilot[r.buf], ctx.b.pll_dt[r.buf], ctx.b.state,
                    ctx.loops, (int)S_PILOT_POWER0 + r.buf, ctx.b.spec_stats, chain, r.seq, ctx.b.pll_hint, ctx.pll_launch_no);
-    } else {
-        FMD_LAUNCH(r, true, true, k_pilot_pll<8>, dim3((unsigned)((d.C + 7) / 8)), dim3(kWave), 0, s, d, ctx.b.pilot[r.buf], ctx.b.pll_dt[r.buf], ctx.b.state,
-                   ctx.loops, (int)S_PILOT_POWER0 + r.buf, ctx.b.spec_stats, chain, r.seq, ctx.b.pll_hint, ctx.pll_launch_no);
-    }
-    return hipGetLastError();
+    }));
 }
 
 static inline int lmr_field(int par) { return par ? (int)S_LMR_PHASE_PREV : (int)S_LMR_PHASE_CUR; }   // state field holding P_k, k & 1 == par
 
-template <int TA, bool FAST = false>
-static void launch_extract_ta(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
-    const Dims& d = ctx.d;
-    const Buffers& b = ctx.b;
-    if constexpr (!FAST) {
-        if (ctx.fast) return launch_extract_ta<TA, true>(ctx, r, s);
-    }
-    if constexpr (FAST && TA == 256) {   // tolerance mode: the FIRs on the matrix cores
-        // round 5: the mixers behind the FIRs, a wavefront per tile (fmd_kernels_bp.inc)
-        const int tiles = d.n_audio / TA;
-        // a workgroup = station x 4 nt tiles, nt per wavefront (the station's tap tables are staged once per workgroup): the largest nt that
-        // still leaves kExtractMinWorkgroups for the chip
-        int nt = 1;
-        // (nt travels in the low 16 bits of one kernel argument, the development switch in bit 16: block_size has no cap, so the search is
-        //  clamped — ADVICE r5: at 8 bits a block of a million samples could wrap nt to 0)
-        constexpr int kNtMax = 0x7fff;
-        for (int v = (tiles + 3) / 4 < kNtMax ? (tiles + 3) / 4 : kNtMax; v >= 1; v--) if ((long)((tiles + 4 * v - 1) / (4 * v)) * d.C >= kExtractMinWorkgroups) { nt = v; break; }
-        int grid_x = (tiles + 4 * nt - 1) / (4 * nt) * d.C;
-        // round 6: two stations per workgroup (tables and the block edge's matrix fetched once for both) where a station is one workgroup anyway,
-        // every station has the same cut-offs and the pairs still are kExtractMinWorkgroups (Plan::extract_auto_pair); ctx.extract_pairing: 1 forces it (tests), 2 switches it off
-        const bool one_wg_per_station = 4 * nt >= tiles;
-        const bool pair = ctx.uniform_cutoffs && one_wg_per_station && 2 * tiles <= 4 * kNtMax && d.C >= 2 &&
-                          (ctx.extract_pairing == 1 || (ctx.extract_pairing == 0 && ctx.plan.extract_auto_pair));
-        if (pair) { nt = (2 * tiles + 3) / 4; grid_x = (d.C + 1) / 2; }
-        if (dev_env("FMD_BP_NOEDGE")) nt |= 0x10000;                     // (development, timing only: the first tile's sums over the previous block skipped)
-        if (pair) FMD_LAUNCH(r, true, true, k_extract_bp<2>, dim3((unsigned)grid_x), dim3(TA), 0, s, d, nt, b.fo_pl[r.buf], b.pll_poly[r.buf],
-                   b.bp_tab, b.aud_idx, b.rds_bp_tab, b.bp_edge, b.mix,
-                   b.state, b.audio[r.buf], b.rds[r.buf], b.lmr_est[r.par], b.lpr[r.buf], b.lmr[r.buf], ctx.keep_taps,
-                   ctx.plan.lmr_inline ? b.lmr_est[r.par ^ 1] : (const float*)nullptr, lmr_field(r.par), lmr_field(r.par ^ 1), b.rds_pow[r.buf]);
-        else FMD_LAUNCH(r, true, true, k_extract_bp<1>, dim3((unsigned)grid_x), dim3(TA), 0, s, d, nt, b.fo_pl[r.buf], b.pll_poly[r.buf],
-                   b.bp_tab, b.aud_idx, b.rds_bp_tab, b.bp_edge, b.mix,
-                   b.state, b.audio[r.buf], b.rds[r.buf], b.lmr_est[r.par], b.lpr[r.buf], b.lmr[r.buf], ctx.keep_taps,
-                   ctx.plan.lmr_inline ? b.lmr_est[r.par ^ 1] : (const float*)nullptr, lmr_field(r.par), lmr_field(r.par ^ 1), b.rds_pow[r.buf]);
-        return;
-    }
-    FMD_LAUNCH(r, true, true, (k_extract<TA, FAST>), dim3((unsigned)(d.n_audio / TA * d.C)), dim3(TA), 0, s, d, b.fm_out_iq[r.buf], b.pll_dt[r.buf],
-                       b.iq_tail[r.par], b.dt_tail[r.par], b.iq_tail[r.par ^ 1], b.dt_tail[r.par ^ 1], b.b_lpr, b.b_lmr, ctx.rds_taps, b.mix,
-                       b.state, b.audio[r.buf], b.rds[r.buf], b.lmr_est[r.par], b.lpr[r.buf], b.lmr[r.buf], ctx.keep_taps,
-                       ctx.plan.lmr_inline ? b.lmr_est[r.par ^ 1] : (const float*)nullptr, lmr_field(r.par), lmr_field(r.par ^ 1));
+// P_{b+1} from the estimates of the block of parity par, into out_row[C]: as a kernel of its own
+static void launch_lmr_phase(const LaunchCtx& ctx, int par, float* out_row, hipStream_t s) {
+    if (ctx.block.lmr_phase == LmrPhase::Serial)
+        hipLaunchKernelGGL(k_lmr_phase, dim3(serial_waves(ctx.d)), dim3(kWave), 0, s, ctx.d, ctx.b.lmr_est[par], ctx.b.state, lmr_field(par), out_row);
+    else
+        hipLaunchKernelGGL(k_lmr_phase_fast, dim3((unsigned)ctx.d.C), dim3(kWave), 0, s, ctx.d, ctx.b.lmr_est[par], ctx.b.state, lmr_field(par), out_row);
 }
 
 hipError_t launch_stage_extract(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
-    if (ctx.d.n_audio % 256 == 0) launch_extract_ta<256>(ctx, r, s);
-    else launch_extract_ta<128>(ctx, r, s);
-    if (!ctx.plan.lmr_inline) {   // P_{b+1} behind block b
-        if (ctx.fast && ctx.d.n_est <= kLmrInlineMax)
-            hipLaunchKernelGGL(k_lmr_phase_fast, dim3((unsigned)ctx.d.C), dim3(kWave), 0, s, ctx.d, ctx.b.lmr_est[r.par], ctx.b.state, lmr_field(r.par),
-                               ctx.b.state + (size_t)lmr_field(r.par ^ 1) * ctx.d.C);
-        else
-            hipLaunchKernelGGL(k_lmr_phase, dim3(serial_waves(ctx.d)), dim3(kWave), 0, s, ctx.d, ctx.b.lmr_est[r.par], ctx.b.state, lmr_field(r.par),
-                               ctx.b.state + (size_t)lmr_field(r.par ^ 1) * ctx.d.C);
+    const Dims& d = ctx.d;
+    const Buffers& b = ctx.b;
+    const BlockPlan& bp = ctx.block;
+    const bool lmr_inline = bp.lmr_phase == LmrPhase::Inline;
+    const float* lmr_prev = lmr_inline ? b.lmr_est[r.par ^ 1] : nullptr;
+    const dim3 grid((unsigned)bp.extract_grid_x);
+    bool found;
+    if (bp.extract_bp) {   // tolerance mode: the FIRs on the matrix cores, the mixers behind them, a wavefront per tile (fmd_kernels_bp.inc)
+        int nt = bp.extract_nt;
+        if (dev_env("FMD_BP_NOEDGE")) nt |= 0x10000;                     // (development, timing only: the first tile's sums over the previous block skipped)
+        found = with_constant<1, 2>(bp.extract_pair ? 2 : 1, [&](auto stations) {
+            FMD_LAUNCH(r, true, true, k_extract_bp<decltype(stations)::value>, grid, dim3(256), 0, s, d, nt, b.fo_pl[r.buf], b.pll_poly[r.buf], b.bp_tab, b.aud_idx, b.rds_bp_tab, b.bp_edge, b.mix,
+                       b.state, b.audio[r.buf], b.rds[r.buf], b.lmr_est[r.par], b.lpr[r.buf], b.lmr[r.buf], ctx.keep_taps, lmr_prev, lmr_field(r.par), lmr_field(r.par ^ 1), b.rds_pow[r.buf]);
+        });
+    } else {
+        found = with_constant<128, 256>(bp.extract_tile, [&](auto ta) { with_constant<0, 1>(ctx.fast, [&](auto fast) {
+            constexpr int TA = decltype(ta)::value;
+            FMD_LAUNCH(r, true, true, (k_extract<TA, decltype(fast)::value != 0>), grid, dim3(TA), 0, s, d, b.fm_out_iq[r.buf], b.pll_dt[r.buf], b.iq_tail[r.par], b.dt_tail[r.par],
+                       b.iq_tail[r.par ^ 1], b.dt_tail[r.par ^ 1], b.b_lpr, b.b_lmr, ctx.rds_taps, b.mix, b.state, b.audio[r.buf], b.rds[r.buf], b.lmr_est[r.par], b.lpr[r.buf], b.lmr[r.buf],
+                       ctx.keep_taps, lmr_prev, lmr_field(r.par), lmr_field(r.par ^ 1));
+        }); });
     }
-    return hipGetLastError();
+    if (!lmr_inline) launch_lmr_phase(ctx, r.par, b.state + (size_t)lmr_field(r.par ^ 1) * d.C, s);   // P_{b+1} behind block b
+    return launched(found);
 }
 
 // the value the reference's GetAudioLMRPhaseError() shows after the newest block (parity `par`): P_{b+1}, into out_row[C]
 hipError_t launch_lmr_phase_peek(const LaunchCtx& ctx, int par, float* out_row, hipStream_t s) {
-    if (ctx.fast && ctx.d.n_est <= kLmrInlineMax)
-        hipLaunchKernelGGL(k_lmr_phase_fast, dim3((unsigned)ctx.d.C), dim3(kWave), 0, s, ctx.d, ctx.b.lmr_est[par], ctx.b.state, lmr_field(par), out_row);
-    else
-        hipLaunchKernelGGL(k_lmr_phase, dim3(serial_waves(ctx.d)), dim3(kWave), 0, s, ctx.d, ctx.b.lmr_est[par], ctx.b.state, lmr_field(par), out_row);
+    launch_lmr_phase(ctx, par, out_row, s);
     return hipGetLastError();
 }
+
 
 #ifdef FMD_F_PROBE
 }  // namespace fmd
@@ -3300,53 +3255,42 @@ static hipError_t launch_stage_rds_decode(const LaunchCtx& ctx, SlotRef r, hipSt
 hipError_t launch_stage_rds(const LaunchCtx& ctx, SlotRef r, hipStream_t s) {
     const Dims& d = ctx.d;
     const Buffers& b = ctx.b;
+    const BlockPlan& bp = ctx.block;
     const bool dec = ctx.rds_decode != 0;
-    if (ctx.fast) {
-        const bool partials = d.n_audio % 256 == 0;       // k_extract_bp ran and left the block's power as 2 partial sums per tile
-        if (partials) {      // the loop split over mixer, clock and dump wavefronts (fmd_kernels_fast.inc)
-            FMD_LAUNCH(r, true, !dec, k_rds_sync3, dim3(serial_waves(d)), dim3(5 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
-                       b.rds_raw_sym[r.buf], b.rds_count[r.buf], b.rds_bytes[r.buf], b.rds_bytes_count[r.buf], ctx.bytes_cap, ctx.keep_taps,
-                       b.rds_pow[r.buf], 2 * (d.n_audio / 256));
-            return dec ? launch_stage_rds_decode(ctx, r, s) : hipGetLastError();
-        }
-        FMD_LAUNCH(r, true, !dec, k_rds_sync<true>, dim3(serial_waves(d)), dim3(2 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
-                   b.rds_raw_sym[r.buf], b.rds_count[r.buf], b.rds_bytes[r.buf], b.rds_bytes_count[r.buf], ctx.bytes_cap, ctx.keep_taps,
-                   partials ? b.rds_pow[r.buf] : (const float*)nullptr, 2 * (d.n_audio / 256), TapPtrs{});
+    if (bp.rds == RdsKernel::Sync3) {      // the loop split over mixer, clock and dump wavefronts (fmd_kernels_fast.inc); the block's power: k_extract_bp's partial sums
+        FMD_LAUNCH(r, true, !dec, k_rds_sync3, dim3(serial_waves(d)), dim3(5 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
+                   b.rds_raw_sym[r.buf], b.rds_count[r.buf], b.rds_bytes[r.buf], b.rds_bytes_count[r.buf], ctx.bytes_cap, ctx.keep_taps, b.rds_pow[r.buf], bp.rds_partials);
     } else {
-        FMD_LAUNCH(r, true, !dec, k_rds_sync<false>, dim3(serial_waves(d)), dim3(2 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
-                   b.rds_raw_sym[r.buf], b.rds_count[r.buf], b.rds_bytes[r.buf], b.rds_bytes_count[r.buf], ctx.bytes_cap, ctx.keep_taps, (const float*)nullptr, 0,
-                   tap_ptrs(ctx, r.buf));
+        with_constant<0, 1>(bp.rds == RdsKernel::SyncFast, [&](auto fast) {
+            constexpr bool FAST = decltype(fast)::value != 0;
+            FMD_LAUNCH(r, true, !dec, k_rds_sync<FAST>, dim3(serial_waves(d)), dim3(2 * kWave), 0, s, d, b.rds[r.buf], b.state, ctx.loops, b.rds_sym[r.buf],
+                       b.rds_raw_sym[r.buf], b.rds_count[r.buf], b.rds_bytes[r.buf], b.rds_bytes_count[r.buf], ctx.bytes_cap, ctx.keep_taps, (const float*)nullptr, bp.rds_partials,
+                       FAST ? TapPtrs{} : tap_ptrs(ctx, r.buf));
+        });
     }
     return dec ? launch_stage_rds_decode(ctx, r, s) : hipGetLastError();
 }
 
-template <typename InT, int TT = 512>
+// the dynamic LDS the front-end kernels may ask for: every form launch_front can launch with 512- and 1024-output tiles
+template <typename InT, int TT>
 static hipError_t prepare_front() {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_front<InT, TT>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)(sizeof(float) * FrontGeom<TT>::LDS_FLOATS));
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_front_mfma<InT, TT, 0, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(sizeof(float) * FrontGeomM<TT, 0>::LDS_FLOATS) + 49152);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_front_mfma<InT, TT, kDeemphWarmup, false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(sizeof(float) * FrontGeomM<TT, kDeemphWarmup>::LDS_FLOATS) + 49152);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_front_mfma<InT, TT, 0, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(sizeof(float) * FrontGeomM<TT, 0>::LDS_FLOATS) + 49152);
-    if (e != hipSuccess) return e;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_front_mfma<InT, TT, kDeemphWarmup, true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)(sizeof(float) * FrontGeomM<TT, kDeemphWarmup>::LDS_FLOATS) + 49152);
-    if (e != hipSuccess) return e;
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_front<InT, TT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(float) * FrontGeom<TT>::LDS_FLOATS));
+    for (int wu : {0, kDeemphWarmup}) for (int fused : {0, 1})
+        with_constant<0, kDeemphWarmup>(wu, [&](auto w) { with_constant<0, 1>(fused, [&](auto fu) {
+            constexpr int WU = decltype(w)::value;
+            if (e == hipSuccess) e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_front_mfma<InT, TT, WU, decltype(fu)::value != 0>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                         (int)(sizeof(float) * FrontGeomM<TT, WU>::LDS_FLOATS) + 49152);
+        }); });
     return e;
 }
 
 hipError_t prepare_kernels() {
     hipError_t e;
-    if ((e = prepare_front<float2>()) != hipSuccess) return e;
+    if ((e = prepare_front<float2, 512>()) != hipSuccess) return e;
     if ((e = prepare_front<float2, 1024>()) != hipSuccess) return e;
-    if ((e = prepare_front<uchar2>()) != hipSuccess) return e;
+    if ((e = prepare_front<uchar2, 512>()) != hipSuccess) return e;
     if ((e = prepare_front<uchar2, 1024>()) != hipSuccess) return e;
-    if ((e = prepare_front<float>()) != hipSuccess) return e;
+    if ((e = prepare_front<float, 512>()) != hipSuccess) return e;
     if ((e = prepare_front<float, 1024>()) != hipSuccess) return e;
     return hipSuccess;
 }

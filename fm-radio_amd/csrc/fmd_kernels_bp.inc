@@ -77,7 +77,7 @@ __device__ __forceinline__ float oct_sum_f32(float v) {
 
 // SPW = stations per workgroup (round 6).  2: one workgroup stages the tap tables and fetches the block edge's matrix ONCE for two stations
 // (every workgroup of a 64 ms block is a station's first AND only one: 16 KB of tables and 24 KB of matrix rows from L2 against 39 KB of window
-// data) — for batches that still give the chip 1536 workgroups and whose stations share their cut-offs (launch_extract_ta).  Same arithmetic per
+// data) — for batches that still give the chip 1536 workgroups and whose stations share their cut-offs (fmd_plan.cpp make_block_plan).  Same arithmetic per
 // output: results are bit-identical to SPW = 1.
 template <int SPW>
 __global__ __launch_bounds__(256, 4) void k_extract_bp(Dims d, int nt, const float* __restrict__ fo_pl, const float4* __restrict__ pll_poly,

@@ -3,9 +3,6 @@
 
 namespace fmd {
 
-const char* const kStageName[ST_COUNT] = {"k_front", "k_deemphasis+k_hilbert", "k_pilot_power", "k_pilot_pll", "k_extract", "k_rds_sync", "k_predecim"};
-const char* const kStageNameFast[ST_COUNT] = {"k_front_mfma", "k_deemphasis", "k_pilot_power", "k_pll_sparse", "k_extract_bp", "k_rds_sync", "k_predecim_mfma"};
-
 namespace {
 Event slot_event(EventKind k, int slot) { Event e; e.kind = k; e.slot = slot; return e; }
 Event timing_event(EventKind k, Stage st, int prof_block) { Event e; e.kind = k; e.stage = (unsigned char)st; e.slot = prof_block; return e; }
@@ -172,7 +169,9 @@ int Schedule::submit(const BlockFacts& f, ScheduleBackend& be) {
     if (!lazy) SCHED_TRY(wait_consumer(be, slot, sX, sR));
     // The first decimator (1.024 / 2.048 MSa/s) gets a queue of its own when the PLL launches do not need the own stream: it then
     // works on block b+1 while k_front works on block b (back to back on one queue the two were the longest stage)
-    const bool predecim = m > 1 && !front_takes_capture(m, fast, f.any_deemph, f.deemph_in_tile, cfg_.n_fm_out, f.split_front);   // (or one kernel, k_front_pre_mfma)
+    PlanFacts facts;
+    facts.any_deemph = f.any_deemph; facts.deemph_in_tile = f.deemph_in_tile; facts.split_front = f.split_front;
+    const bool predecim = m > 1 && !front_takes_capture(*plan_, facts);   // (or one kernel, k_front_pre_mfma)
     const Queue sP = (pipe && m > 1 && !chained) ? Q_OWN : sF;
     // Put-off schedule at 1.024 / 2.048 MSa/s: the front end (with the previous block's pilot stage riding it) follows the first
     // decimator on that queue, and the extract stages have the front end's queue to themselves: two queues that each run ahead,

@@ -18,10 +18,7 @@ namespace fmd {
 // block b and the power pass came in ~90 us before the PLL needed it: no room for the per-wavefront hand-over to overlap).
 static constexpr int kSlots = 6;
 
-enum Stage { ST_FRONT = 0, ST_DEEMPH, ST_POWER, ST_PLL, ST_EXTRACT, ST_RDS, ST_PREDECIM, ST_COUNT };
-extern const char* const kStageName[ST_COUNT];
-// ... and of the tolerance mode's kernels, as they appear in rocprofv3 kernel traces
-extern const char* const kStageNameFast[ST_COUNT];
+// (the stages themselves, enum Stage, and their kernels' names: fmd_plan.h)
 
 // Q_CALLER: the stream the caller passed to the entry point; Q_OWN: the handle's own stream (host-pointer entry points, uploads, resets; the second
 // pilot queue of the per-wavefront hand-over and the first decimator's queue — one more stream would be the ninth on the device with the caller's
@@ -70,7 +67,7 @@ struct ScheduleConfig {
 struct BlockFacts {
     bool ordered = true;          // fmd_process_*_dev: the caller's stream is ordered behind the library's read of the block; false: fmd_submit_*_dev
     bool have_stream = true;      // fmd_submit_*_dev: a ready stream was passed (NULL = the input is in place now)
-    bool any_deemph = false, deemph_in_tile = false, split_front = false;     // LaunchCtx's, after the control upload
+    bool any_deemph = false, deemph_in_tile = false, split_front = false;     // LaunchCtx::facts', after the control upload
     int prof_block = -1;          // index of the block's timing events (Schedule::profiling() != 0), or -1
 };
 

@@ -101,6 +101,41 @@ typedef struct {
     int pll_kernel;           /* FMD_PLL_KERNEL_* */
 } fmd_plan_info;
 int fmd_debug_plan(const fmd_config* cfg, int k16_max_channels, int time_parallel_max_channels, int unlocked_now, fmd_plan_info* out);
+/* Host-only (no GPU needed): each stage's kernel form and launch geometry for a configuration (fm-radio_amd/csrc/fmd_plan.h BlockPlan: what the
+ * block length, the input type — u8 != 0: fmd_process_u8, else cf32 — and the run-time facts decide on top of fmd_debug_plan's fields; the stage
+ * launchers read it and decide nothing).  facts: what the controls and the debug hooks leave behind — a station's de-emphasis as a stage of its own, or
+ * (tolerance mode) inside the front end's tile; fmd_debug_split_front; every station with the same audio cut-offs; fmd_debug_extract_pairing's mode.
+ * tests/test_plan_cpu.py compares every field with a restatement of the rules (tests/plan_model.py). */
+typedef struct { int any_deemph, deemph_in_tile, split_front, uniform_cutoffs, extract_pairing; } fmd_plan_facts;
+enum { FMD_FRONT_K_FRONT = 0, FMD_FRONT_K_FRONT_MFMA = 1, FMD_FRONT_K_FRONT_PRE_MFMA = 2 };
+enum { FMD_FRONT_INPUT_CF32 = 0, FMD_FRONT_INPUT_U8 = 1, FMD_FRONT_INPUT_FM_IN = 2, FMD_FRONT_INPUT_PHASES = 3 };
+enum { FMD_PREDECIM_NONE = 0, FMD_PREDECIM_K_PREDECIM = 1, FMD_PREDECIM_K_PREDECIM_PHASES = 2, FMD_PREDECIM_K_PREDECIM_MFMA = 3 };
+enum { FMD_LMR_PHASE_INLINE = 0, FMD_LMR_PHASE_FAST = 1, FMD_LMR_PHASE_SERIAL = 2 };
+enum { FMD_RDS_K_RDS_SYNC = 0, FMD_RDS_K_RDS_SYNC_FAST = 1, FMD_RDS_K_RDS_SYNC3 = 2 };
+typedef struct {
+    int iq_streams;           /* the handle materialises fm_out_iq / pll_dt */
+    int front_kernel;         /* FMD_FRONT_K_* */
+    int front_input;          /* FMD_FRONT_INPUT_*: the capture, or behind a first-decimator stage fm_in as samples or as phases */
+    int front_tile;           /* fm_out samples per workgroup: 512, 1024, 2048 */
+    int front_warmup;         /* k_front_mfma: samples the in-tile de-emphasis starts early (0, 128) */
+    int front_workgroups;     /* stations x tiles (without the pilot stage's workgroups that may ride in the launch) */
+    int front_lds_pad;        /* bytes of extra dynamic LDS */
+    int predecim_kernel;      /* FMD_PREDECIM_*: NONE exactly when the front end takes the capture */
+    int predecim_tile;        /* fm_in samples per workgroup */
+    int predecim_workgroups;
+    int deemph_pilot_sums;    /* the de-emphasis stage is k_deemphasis + k_pilot_sums, not k_deemphasis + k_hilbert */
+    int deemph_workgroups;    /* of the second kernel of the pair */
+    int pilot_power_rows;     /* k_pilot_power<true> */
+    int lmr_phase;            /* FMD_LMR_PHASE_* */
+    int extract_tile;         /* audio samples per tile: 128, 256 */
+    int extract_bp;           /* k_extract_bp, not k_extract */
+    int extract_nt;           /* k_extract_bp: tiles per wavefront */
+    int extract_pair;         /* k_extract_bp<2> */
+    int extract_grid_x;
+    int rds_kernel;           /* FMD_RDS_K_* */
+    int rds_partials;         /* partial sums of the block's RDS power per station */
+} fmd_block_plan_info;
+int fmd_debug_block_plan(const fmd_config* cfg, const fmd_plan_facts* facts, int u8, fmd_block_plan_info* out);
 /* Tolerance mode: k_extract_bp with two stations per workgroup (the tap tables and the block edge's matrix fetched once for both; results bit-identical):
  * 0 = where it pays (3072 stations and more with equal cut-offs, the default), 1 = wherever possible (so that tests reach it with a few stations), 2 = never. */
 int fmd_debug_extract_pairing(fmd_handle h, int mode);

@@ -131,15 +131,16 @@ def inject(e: np.ndarray, period: int, amplitude: float, lo: int, hi: int | None
 
 # ---- the geometry of one configuration: which periods and zones each stream has ---------------------------------------------------------
 
-def geometry(fs: int, block_size: int, u8: bool = False, deemph: bool = False, split_front: bool = False) -> dict:
-    """Periods and zones per stream, from the kernels' geometry constants (fm-radio_amd/csrc):
+def geometry(fs: int, block_size: int, u8: bool = False, deemph: bool = False, split_front: bool = False, n_ch: int = 8) -> dict:
+    """Periods and zones per stream of the tolerance mode, from the kernels' geometry constants (fm-radio_amd/csrc) and the tiles the block plan picks
+    (fmd_plan.h BlockPlan; restated here on purpose: tests/test_plan_cpu.py holds the two together for the configurations the seam test runs):
       n_fm_out = block / (fs / 256 k) / 2, n_audio = n_fm_out / 4                                            (fmd_kernels.h Dims)
-      front tile: launch_front (fmd_kernels.hip): 1024 fm_out samples when n_fm_out % 1024 == 0, else FrontGeom<512>; u8 captures at
-        256 kSa/s without de-emphasis: 2048 when n_fm_out % 2048 == 0; k_front_pre_mfma: 1024 (launch_front_pre).  63-sample halo
-        (FrontGeomM::NW), de-emphasis from a zero state kDeemphWarmup = 128 samples early, MFMA outputs in 16-column accumulators
-      first decimator on its own: launch_predecim: (8192 u8 | 2048 cf32) / M input samples per tile, else 256 outputs -> in fm_out samples / 2
+      front tile (BlockPlan::Input::front_tile): 1024 fm_out samples when n_fm_out % 1024 == 0, else 512; captures at 256 kSa/s without de-emphasis:
+        2048 when n_fm_out % 2048 == 0, u8 always, cf32 in batches of at least 12288 such tiles (n_ch stations); k_front_pre_mfma: 1024.  63-sample
+        halo (FrontGeomM::NW), de-emphasis (deemph: inside the tile) from a zero state kDeemphWarmup = 128 samples early, MFMA outputs in 16-column accumulators
+      first decimator on its own (predecim_tile): (8192 u8 | 2048 cf32) / M input samples per tile, else 256 outputs -> in fm_out samples / 2
       pilot loop: kSpan = 128, kSparseDec = 16 (fmd_tables.h)
-      extract: launch_stage_extract: 256 audio samples per tile when n_audio % 256 == 0, else 128; four tiles a round; kFoPad = 192 fm_out
+      extract (extract_tile): 256 audio samples per tile when n_audio % 256 == 0, else 128; four tiles a round; kFoPad = 192 fm_out
         samples = 47 audio samples of reach into the tile in front; the block's first 31 outputs through S_old (kBpEdgeRows = 31 * 8)
     Each entry: periods {kind: T}, zones [(name, kind of the period it is folded at, lo, hi)]."""
     m = fs // 256_000
@@ -147,7 +148,7 @@ def geometry(fs: int, block_size: int, u8: bool = False, deemph: bool = False, s
     n_au = n_fo // 4
     if m > 1 and not deemph and not split_front and n_fo % 1024 == 0:
         ft = 1024                                                   # k_front_pre_mfma (fmd_plan.h front_takes_capture)
-    elif m == 1 and u8 and not deemph and n_fo % 2048 == 0:
+    elif m == 1 and not deemph and n_fo % 2048 == 0 and (u8 or n_ch * (n_fo // 2048) >= 12288):
         ft = 2048
     else:
         ft = 1024 if n_fo % 1024 == 0 else 512

@@ -95,6 +95,92 @@ def test_what_the_hook_refuses(pkg):
     assert pkg.load_library().fmd_debug_plan(C.byref(ok), -1, -1, 0, None) == -1
 
 
+# ---- the block plan: each stage's kernel form and launch geometry (fmd_debug_block_plan) ------------------------------------------------------------
+
+BLOCK_KS = tuple(range(1, 71)) + (128, 1024)          # block = 1024 m k samples: every tile count up to 70 front tiles, and two long ones (n_est > 512)
+BLOCK_STATIONS = (1, 2, 3) + tuple(t + d for t in (384, 768, 1024, 1536, 1792, 3071, 3072, 6144, 12288) for d in (-2, -1, 0, 1, 2))
+DEEMPH = ((0, 0), (0, 1), (1, 0))                     # (any_deemph, deemph_in_tile): no de-emphasis, inside the front tile, as a stage
+
+
+def test_the_binding_names_the_block_plan_fields_in_the_model_s_order(pkg):
+    assert tuple(n for n, _ in pkg.BlockPlanInfo._fields_) == M.BLOCK_FIELDS
+    assert tuple(n for n, _ in pkg.PlanFacts._fields_) == ("any_deemph", "deemph_in_tile", "split_front", "uniform_cutoffs", "extract_pairing")
+
+
+def test_block_plan_against_the_model_and_its_invariants(pkg):
+    """fmd_debug_block_plan against tests/plan_model.py over the whole product — rate x cf32 / u8 x mode x FMD_FLAG_KEEP_TAPS x block length x de-emphasis (none, in
+    the tile, as a stage) x fmd_debug_split_front x equal cut-offs x pairing mode x station count — and, on the library's answer alone, what any plan must
+    satisfy: tiles divide the stream they tile and cover it exactly once, nt fits its 15 bits, paired and unpaired grids are what k_extract_bp indexes by,
+    the first decimator is a stage exactly when the front end does not take the capture, and the interleaved streams are left out only where nothing reads
+    them."""
+    lib, F = pkg.load_library(), M.BLOCK_FIELDS
+    out, facts = pkg.BlockPlanInfo(), pkg.PlanFacts()
+    view = (C.c_int * len(F)).from_buffer(out)
+    i_ = {n: k for k, n in enumerate(F)}
+    (I_IQ, I_FK, I_FT, I_FW, I_PK, I_PT, I_PW, I_ET, I_BP, I_NT, I_PAIR, I_GRID) = (i_[n] for n in (
+        "iq_streams", "front_kernel", "front_tile", "front_workgroups", "predecim_kernel", "predecim_tile", "predecim_workgroups", "extract_tile", "extract_bp", "extract_nt",
+        "extract_pair", "extract_grid_x"))
+    checked = 0
+    for fs, u8, fast, keep, k in itertools.product((K256, K1024, K2048), (False, True), (0, M.FAST_MATH), (0, M.KEEP_TAPS), BLOCK_KS):
+        m, flags = fs // K256, fast | keep
+        bs = 1024 * m * k
+        n_in, n_fo, n_au = bs // m, bs // m // 2, bs // m // 8
+        for n in BLOCK_STATIONS:
+            cfg = pkg.Config(n, bs, fs, -1, flags)
+            for (any_de, in_tile), split, uniform, pairing in itertools.product(DEEMPH, (0, 1), (0, 1), (0, 1, 2)):
+                facts.any_deemph, facts.deemph_in_tile, facts.split_front, facts.uniform_cutoffs, facts.extract_pairing = any_de, in_tile, split, uniform, pairing
+                assert lib.fmd_debug_block_plan(C.byref(cfg), C.byref(facts), u8, C.byref(out)) == 0
+                g = tuple(view)
+                want = M.block_plan(n, fs, bs, flags, u8, bool(any_de), bool(in_tile), bool(split), bool(uniform), pairing)
+                assert g == want, (n, bs, fs, flags, u8, any_de, in_tile, split, uniform, pairing, dict(zip(F, g)), dict(zip(F, want)))
+                # invariants, from the answer alone
+                assert n_fo % g[I_FT] == 0 and g[I_FW] * g[I_FT] == n_fo * n
+                assert n_au % g[I_ET] == 0
+                takes_capture = m == 1 or g[I_FK] == M.K_FRONT_PRE_MFMA
+                assert (g[I_PK] == M.NO_PREDECIM) == takes_capture
+                if not takes_capture:
+                    assert n_in % g[I_PT] == 0 and g[I_PW] * g[I_PT] == n_in * n
+                if g[I_BP]:
+                    tiles = n_au // g[I_ET]
+                    assert 1 <= g[I_NT] <= 0x7fff
+                    if g[I_PAIR]:
+                        assert g[I_GRID] == (n + 1) // 2 and 4 * g[I_NT] >= 2 * tiles
+                    else:
+                        assert g[I_GRID] == -(-tiles // (4 * g[I_NT])) * n and (g[I_GRID] >= 1536 or g[I_NT] == 1)
+                else:
+                    assert not g[I_PAIR] and g[I_GRID] * g[I_ET] == n_au * n
+                assert g[I_IQ] == int(not (fast and not keep and n_fo % 1024 == 0))
+                checked += 1
+    assert checked == 3 * 2 * 2 * 2 * len(BLOCK_KS) * len(BLOCK_STATIONS) * 36
+
+
+def test_what_the_block_plan_hook_refuses(pkg):
+    lib = pkg.load_library()
+    ok, facts, out = pkg.Config(12, 16384, K256, -1, 0), pkg.PlanFacts(), pkg.BlockPlanInfo()
+    assert lib.fmd_debug_block_plan(C.byref(ok), C.byref(facts), 0, C.byref(out)) == 0
+    assert lib.fmd_debug_block_plan(C.byref(ok), None, 0, C.byref(out)) == -1 and lib.fmd_debug_block_plan(C.byref(ok), C.byref(facts), 0, None) == -1
+    assert lib.fmd_debug_block_plan(C.byref(pkg.Config(12, 10240, K1024, -1, 0)), C.byref(facts), 0, C.byref(out)) == -1      # no multiple of 1024 m
+    facts.extract_pairing = 3
+    assert lib.fmd_debug_block_plan(C.byref(ok), C.byref(facts), 0, C.byref(out)) == -1
+
+
+def test_seam_geometry_agrees_with_the_block_plan(pkg):
+    """tests/seam_stats.geometry keeps its own arithmetic (it is the independent side of tests/test_gpu_fast_seams.py); for every configuration that test runs,
+    its front tile, extract tile and first-decimator period are the plan's."""
+    import seam_stats as S
+    import test_gpu_fast_seams as T
+    for name, f in T.FORMS.items():
+        u8, deemph, split = f.get("u8", False), f.get("deemph", False), f.get("split_front", False)
+        geo = S.geometry(f["fs"], f["bs"], u8, deemph, split, n_ch=f["n_ch"])
+        facts = pkg.PlanFacts(0, int(deemph), int(split), 1, 0)         # (50 us on every station: inside the front tile)
+        got = pkg.block_plan(pkg.Config(f["n_ch"], f["bs"], f["fs"], -1, M.FAST_MATH), facts, u8)
+        assert (geo["front_tile"], geo["extract_tile"]) == (got.front_tile, got.extract_tile), name
+        assert geo["fm_out_iq"]["periods"].get("predecim", 0) == got.predecim_tile // 2, name
+    # cf32 captures get 2048-output tiles from 12288 such workgroups on, at any batch size
+    for n_ch, want in ((3071, 1024), (3072, 2048)):
+        assert S.geometry(K256, 16384, n_ch=n_ch)["front_tile"] == want == pkg.block_plan(pkg.Config(n_ch, 16384, K256, -1, M.FAST_MATH)).front_tile
+
+
 # The cases of tests/test_gpu_every_station.py whose "why" names a switch: (mode, stations, rate) -> (the plan fields that change there, the largest
 # station count on the other side).  "pll_kernel" is the kernel while every loop holds lock, "pll_kernel/unlocked" the one while some do not.  A case
 # sits on the first count past its switch, with two exceptions that sit on the second: 1025 (1024 is the first on the put-off schedule and with

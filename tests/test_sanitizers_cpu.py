@@ -105,10 +105,24 @@ def test_kernel_selection_plan_under_sanitizers_equals_the_model(asan_build, tmp
                 cases += [(c, m, n_fm_out, n_est, flags, None, u) for c in M.stations_to_try() for u in (0, 1)]
     cases += [(c, 1, 8192, 205, 0, th, u) for c in (5, 12) for th in ((4, 7168), (4, 4), (2, 7168), (2, 2)) for u in (0, 1)]
     (tmp_path / "cases.txt").write_text("".join(f"{c} {m} {nf} {ne} {fl} {th[0] if th else -1} {th[1] if th else -1} {u}\n" for c, m, nf, ne, fl, th, u in cases))
-    out = _run([asan_build / "plan_main", tmp_path / "cases.txt"]).stdout.split("\n")[:-1]
-    assert len(out) == len(cases) > 20_000
+    # ... and the block plan (make_block_plan) over a handful of tests/test_plan_cpu.py's product: the three rates, both modes and input types, every
+    # fact, at block lengths with 1, 3, 6, 9, 16, 64 and 1024 half-tiles and station counts on the tile, pad and pairing switches
+    import itertools
+    blocks = []
+    for fs, k, c, fl, u8 in itertools.product((256_000, 1_024_000, 2_048_000), (1, 3, 6, 9, 16, 64, 1024), (1, 3, 1024, 1793, 3071, 3072, 12290), (0, M.FAST_MATH, M.FAST_MATH | M.KEEP_TAPS),
+                                               (0, 1)):
+        blocks += [(c, fs, 1024 * (fs // 256_000) * k, fl, u8) + facts
+                   for facts in ((0, 0, 0, 0, 0), (0, 1, 0, 1, 0), (1, 0, 0, 1, 1), (0, 0, 1, 1, 0), (0, 0, 0, 1, 1), (0, 0, 1, 1, 2), (1, 0, 1, 0, 1))]
+    (tmp_path / "blocks.txt").write_text("".join(f"{c} {M.lengths(fs, bs)[0]} {M.lengths(fs, bs)[1]} {M.lengths(fs, bs)[2]} {fl} {u8} {a} {t} {s} {u} {p}\n"
+                                                 for c, fs, bs, fl, u8, a, t, s, u, p in blocks))
+    out = _run([asan_build / "plan_main", tmp_path / "cases.txt", tmp_path / "blocks.txt"]).stdout.split("\n")[:-1]
+    assert len(out) == len(cases) + 1 + len(blocks) and len(cases) > 20_000 and out[len(cases)] == "--" and len(blocks) > 5000
     for line, (c, m, nf, ne, fl, th, u) in zip(out, cases):
         assert tuple(map(int, line.split())) == M.plan(c, m, nf, ne, fl, th, bool(u)), (c, m, nf, ne, fl, th, u)
+    for line, (c, fs, bs, fl, u8, a, t, s, u, p) in zip(out[len(cases) + 1:], blocks):
+        want = M.block_plan(c, fs, bs, fl, bool(u8), bool(a), bool(t), bool(s), bool(u), p)
+        names = (("k_front", "k_front_mfma", "k_front_pre_mfma")[want[M.BLOCK_FIELDS.index("front_kernel")]], "k_extract_bp" if fl & M.FAST_MATH else "k_extract")
+        assert tuple(line.split()) == tuple(map(str, want)) + names, (c, fs, bs, fl, u8, a, t, s, u, p)
 
 
 def test_table_designers_under_sanitizers_reproduce_the_pinned_tables(asan_build, tmp_path):
