@@ -214,8 +214,9 @@ int upload_controls(fmd_handle h, hipStream_t s) {
     HIP_TRY(h, hipMemcpyAsync(b.mix, mix.data(), mix.size() * 4, hipMemcpyHostToDevice, s));
     HIP_TRY(h, hipStreamSynchronize(s));  // the host vectors die here
     // FMD_FLAG_FAST_MATH: the IIR runs inside k_front's tile (no state, no extra stage) unless a channel's time constant is too long
-    // for its warm-up; a switch between the two forms (controls changed across ~79 us) restarts the filter from the state the other
-    // form last left: a transient of a millisecond on those channels
+    // for its warm-up.  The in-tile form leaves each block's last sample where the serial stage keeps its state (k_front_mfma), so a
+    // handle that falls back to the serial stage continues the filter; the in-tile form itself has no state (zero, 128 samples early), so
+    // where the reference's IIR resumes from a frozen state, or from another time constant's, the two differ for about a millisecond
     PlanFacts& f = h->ctx.facts;
     f.deemph_in_tile = h->ctx.fast && any && !slow_pole;
     if (f.deemph_in_tile) { f.any_deemph = false; h->deemph_linger = false; h->deemph_on = false; }

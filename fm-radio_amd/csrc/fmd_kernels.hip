@@ -365,7 +365,8 @@ template <int TT, int WU, bool TIES = false>
 __device__ __forceinline__ void front_from_phases(const Dims& d, float* smem, const float* theta, uint32_t* dem32, int c, int o0, int tid, float fm_gain,
                                                   const float* __restrict__ deemph, const FrontOps& op, float* __restrict__ fo_pl,
                                                   float4* __restrict__ pv_pl, const PllSparseTab* __restrict__ sp,
-                                                  const uchar2* __restrict__ raw_c = nullptr, const float2* __restrict__ raw_tail = nullptr, int raw_tail_len = 0, int g_lo = 0) {
+                                                  const uchar2* __restrict__ raw_c = nullptr, const float2* __restrict__ raw_tail = nullptr, int raw_tail_len = 0, int g_lo = 0,
+                                                  float* __restrict__ de_state = nullptr) {
     using G = FrontGeomM<TT, WU>;
     constexpr int T = G::T, NW = G::NW, NF = G::NF;
     const int lane = tid & (kWave - 1), wv = tid >> 6, lrow = lane & 15, lq = lane >> 4;
@@ -458,7 +459,7 @@ __device__ __forceinline__ void front_from_phases(const Dims& d, float* smem, co
         if (deemph[4 * c + 3] != 0.0f) {
             float* zs = smem + G::OFF_ZS;
             constexpr int NSEG = NF / 8;
-            float yv[8];
+            float yv[8], x_last = 0.0f;
             if (tid < 16) zs[tid] = 0.0f;
             if (tid < NSEG) {
                 const float4 xa = *reinterpret_cast<const float4*>(fo + 8 * tid), xb = *reinterpret_cast<const float4*>(fo + 8 * tid + 4);
@@ -467,6 +468,7 @@ __device__ __forceinline__ void front_from_phases(const Dims& d, float* smem, co
 #pragma unroll
                 for (int k = 0; k < 8; k++) { z = fmaf(a0, z, fmaf(xs[k], b1, xp * b0)); yv[k] = z; xp = xs[k]; }
                 zs[16 + tid] = z;
+                x_last = xp;
             }
             __syncthreads();
             if (tid < NSEG) {
@@ -479,6 +481,10 @@ __device__ __forceinline__ void front_from_phases(const Dims& d, float* smem, co
                 for (int k = 0; k < 8; k++) { yv[k] = fmaf(pw, e, yv[k]); pw *= a0; }
                 *reinterpret_cast<float4*>(fo + 8 * tid) = make_float4(yv[0], yv[1], yv[2], yv[3]);
                 *reinterpret_cast<float4*>(fo + 8 * tid + 4) = make_float4(yv[4], yv[5], yv[6], yv[7]);
+                // the block's last sample is the state the reference's IIR holds from here on (x[n-1], y[n-1]; frozen while the filter is switched off):
+                // left where k_deemphasis keeps it, so that a handle that falls back to the serial stage (a time constant beyond this form)
+                // continues the filter and does not restart it from whatever that stage last held
+                if (de_state && tid == NSEG - 1 && o0 + T == d.n_fm_out) { st(de_state, S_DE_X1, d.C, c) = x_last; st(de_state, S_DE_Y1, d.C, c) = yv[7]; }
             }
             __syncthreads();
         }
@@ -623,8 +629,8 @@ __global__ __launch_bounds__(256, FUSED ? 6 : 5) void k_front_mfma(Dims d, const
     __syncthreads();
     F_STAMP(1);
     if constexpr (sizeof(InT) == 2) front_from_phases<TT, WU, true>(d, smem, theta, reinterpret_cast<uint32_t*>(smem), c, o0, tid, fm_gain, deemph, op, fo_pl, pv_pl, sp,
-                                                                    in_c, tail_c, G::TAIL, g_lo);
-    else front_from_phases<TT, WU>(d, smem, theta, reinterpret_cast<uint32_t*>(smem), c, o0, tid, fm_gain, deemph, op, fo_pl, pv_pl, sp);
+                                                                    in_c, tail_c, G::TAIL, g_lo, pf.state);
+    else front_from_phases<TT, WU>(d, smem, theta, reinterpret_cast<uint32_t*>(smem), c, o0, tid, fm_gain, deemph, op, fo_pl, pv_pl, sp, nullptr, nullptr, 0, 0, pf.state);
     if (tile == tiles - 1) {
         float2* tout = tail_out + (size_t)c * d.tail_base;
         for (int idx = tid; idx < d.tail_base; idx += 256) tout[idx] = load_iq(in_c, (unsigned)(d.N - d.tail_base + idx));
@@ -3019,8 +3025,8 @@ static_assert(kDeemphWarmup == kFrontDeemphWarmup && PredecimGeom<4>::TP == 512 
 
 // the pilot stage of the block in slot pll->buf as the first workgroups of a front-end launch (none: n_wg = 0)
 static PllFusedArgs fused_pilot_args(const LaunchCtx& ctx, const SlotRef* pll) {
-    if (!pll) return PllFusedArgs{};
     const Buffers& b = ctx.b;
+    if (!pll) { PllFusedArgs none{}; none.state = b.state; return none; }     // (state: also where k_front_mfma's in-tile de-emphasis leaves its last sample)
     const int nxt = (pll->buf + 1) % kSlots;
     return PllFusedArgs{(ctx.d.C + 31) / 32, b.pv_pl[pll->buf], b.pv_hist[pll->par], b.pv_hist[pll->par ^ 1], b.fo_pl[pll->buf], b.fo_pl[nxt],
                         b.pll_poly[pll->buf], b.pll_poly[nxt], b.state, ctx.loops, b.sparse_tab, b.spec_stats};

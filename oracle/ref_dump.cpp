@@ -7,8 +7,12 @@
 // exposes through its getters, so the C restatement in oracle/fm_oracle.c (and
 // through it the HIP path) can be pinned against the real thing.
 //
-//   fm_ref_dump chain     <capture.u8>   <outdir> <block_size> [deemph=us audio=lpr|lmr|stereo mix=f lpr=hz lmr=hz]   App::Process path (u8 ingest)
-//   fm_ref_dump cf32chain <capture.cf32> <outdir> <block_size>   Broadcast_FM_Demod::Process path
+//   fm_ref_dump chain     <capture.u8>   <outdir> <block_size> [controls] [at=<block> controls]...   App::Process path (u8 ingest)
+//   fm_ref_dump cf32chain <capture.cf32> <outdir> <block_size> [controls] [at=<block> controls]...   Broadcast_FM_Demod::Process path
+//       controls: deemph=us|on|off tus=us audio=lpr|lmr|stereo mix=f lpr=hz lmr=hz.  Those in front of the first at= are set before the
+//       first block; those behind at=<block> before the first sample of that block reaches the demodulator (chain mode feeds
+//       16384-sample pieces: there a schedule needs a block size that is a multiple of 16384).  deemph=us switches the filter on
+//       with that time constant, tus=us moves the time constant alone, deemph=on|off the switch alone.
 //   fm_ref_dump prims     <indir>        <outdir>                per-primitive vectors
 //
 // Reference API used: App (src/app.h:19-47), Broadcast_FM_Demod getters
@@ -116,7 +120,10 @@ static void apply_controls(Broadcast_FM_Demod& d, int argc, char** argv) {
     auto& c = d.GetControls();
     for (int i = 0; i < argc; i++) {
         const char* a = argv[i];
-        if (!strncmp(a, "deemph=", 7)) { c.is_use_deemphasis_filter = true; c.filt_deemphasis_cutoff.SetValue(atoi(a + 7)); }
+        if (!strcmp(a, "deemph=off")) c.is_use_deemphasis_filter = false;
+        else if (!strcmp(a, "deemph=on")) c.is_use_deemphasis_filter = true;
+        else if (!strncmp(a, "deemph=", 7)) { c.is_use_deemphasis_filter = true; c.filt_deemphasis_cutoff.SetValue(atoi(a + 7)); }
+        else if (!strncmp(a, "tus=", 4)) c.filt_deemphasis_cutoff.SetValue(atoi(a + 4));
         else if (!strncmp(a, "audio=", 6)) {
             if (!strcmp(a + 6, "lpr")) c.audio_out = Broadcast_FM_Demod_Controls::LPR;
             else if (!strcmp(a + 6, "lmr")) c.audio_out = Broadcast_FM_Demod_Controls::LMR;
@@ -129,20 +136,47 @@ static void apply_controls(Broadcast_FM_Demod& d, int argc, char** argv) {
     }
 }
 
+// the control arguments as a schedule: the arguments in front of the first at= (applied at once), then per at=<block> the run behind it
+struct ControlSchedule {
+    struct Event { long block; int argc; char** argv; };
+    int argc0 = 0;
+    char** argv0 = nullptr;
+    std::vector<Event> events;
+    size_t next = 0;
+    ControlSchedule(int argc, char** argv) {
+        int i = 0;
+        while (i < argc && strncmp(argv[i], "at=", 3)) i++;
+        argc0 = i; argv0 = argv;
+        while (i < argc) {
+            Event e{atol(argv[i] + 3), 0, argv + i + 1};
+            if (e.block < 0 || (!events.empty() && e.block < events.back().block)) { fprintf(stderr, "at= blocks must ascend from 0\n"); exit(2); }
+            for (i++; i < argc && strncmp(argv[i], "at=", 3); i++) e.argc++;
+            events.push_back(e);
+        }
+    }
+    // everything scheduled for blocks up to `block`, in the order given
+    void apply_up_to(Broadcast_FM_Demod& d, long block) {
+        for (; next < events.size() && events[next].block <= block; next++) apply_controls(d, events[next].argc, events[next].argv);
+    }
+};
+
 static int run_chain(const char* in, const char* outdir, int block_size, int argc, char** argv) {
     Sink sink{outdir};
     ChainDump dump(sink);
     auto data = slurp<std::complex<uint8_t>>(in);
     App app(block_size);
     auto& demod = app.GetFMDemod();
-    apply_controls(demod, argc, argv);
+    ControlSchedule sched(argc, argv);
+    apply_controls(demod, sched.argc0, sched.argv0);
     app.OnAudioBlock().Attach([&](tcb::span<const Frame<float>> x, const int Fs) { (void)Fs; dump.on_block(demod, x); });
     app.On_RDS_Bytes().Attach([&](tcb::span<const uint8_t> x) { put(dump.rds_bytes, x.data(), x.size()); });
     const size_t n_blocks = data.size() / (size_t)block_size;
     // feed in odd-sized pieces to exercise the reference's re-blocking (src/app.cpp:39-50)
     const size_t total = n_blocks * (size_t)block_size;
     size_t pos = 0, piece = 16384;
+    if (!sched.events.empty() && block_size % (int)piece) { fprintf(stderr, "a schedule needs a block size that is a multiple of %zu\n", piece); return 2; }
     while (pos < total) {
+        if (pos % (size_t)block_size == 0) sched.apply_up_to(demod, (long)(pos / (size_t)block_size));
         size_t n = (total - pos < piece) ? (total - pos) : piece;
         app.Process(tcb::span<const std::complex<uint8_t>>(data.data() + pos, n));
         pos += n;
@@ -157,7 +191,8 @@ static int run_cf32chain(const char* in, const char* outdir, int block_size, int
     ChainDump dump(sink);
     auto data = slurp<cf32>(in);
     Broadcast_FM_Demod demod(block_size);
-    apply_controls(demod, argc, argv);
+    ControlSchedule sched(argc, argv);
+    apply_controls(demod, sched.argc0, sched.argv0);
     uint8_t bytes_buf[16];
     DifferentialManchesterDecoder manchester{tcb::span<uint8_t>(bytes_buf, 16)};
     demod.OnAudioOut().Attach([&](tcb::span<const Frame<float>> x, const int Fs) { (void)Fs; dump.on_block(demod, x); });
@@ -165,6 +200,7 @@ static int run_cf32chain(const char* in, const char* outdir, int block_size, int
     manchester.OnBytes().Attach([&](tcb::span<const uint8_t> x) { put(dump.rds_bytes, x.data(), x.size()); });
     const size_t n_blocks = data.size() / (size_t)block_size;
     for (size_t b = 0; b < n_blocks; b++) {
+        sched.apply_up_to(demod, (long)b);
         demod.Process(tcb::span<const cf32>(data.data() + b * (size_t)block_size, (size_t)block_size));
     }
     dump.close_all();
@@ -299,6 +335,6 @@ int main(int argc, char** argv) {
     if (argc >= 5 && !strcmp(argv[1], "chain")) return run_chain(argv[2], argv[3], atoi(argv[4]), argc - 5, argv + 5);
     if (argc >= 5 && !strcmp(argv[1], "cf32chain")) return run_cf32chain(argv[2], argv[3], atoi(argv[4]), argc - 5, argv + 5);
     if (argc >= 4 && !strcmp(argv[1], "prims")) return run_prims(argv[2], argv[3]);
-    fprintf(stderr, "usage: fm_ref_dump chain|cf32chain <in> <outdir> <block> | prims <indir> <outdir>\n");
+    fprintf(stderr, "usage: fm_ref_dump chain|cf32chain <in> <outdir> <block> [controls] [at=<block> controls]... | prims <indir> <outdir>\n");
     return 1;
 }

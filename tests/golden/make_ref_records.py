@@ -44,6 +44,9 @@ def main() -> None:
             chain(V.controls_key(args), cap[: 65536 * 6], block_size=65536, extra_args=args)
         chain("oracle_vs_ref/cf32", V.cf32_capture(), block_size=65536, u8=False)
         chain("oracle_vs_ref/noise", V.noise_capture(), block_size=65536)
+        import control_schedules as CS  # noqa: E402
+        for name, sched, cf32 in V.schedule_cases():
+            chain(V.schedule_key(name), V.schedule_capture(cf32), block_size=16384, u8=not cf32, extra_args=CS.ref_args(sched))
 
         for noise, seed in G.CASES:
             d = td / f"gs_{seed}"

@@ -255,6 +255,14 @@ def have_ref() -> bool:
     return REF_DUMP.exists() and os.access(REF_DUMP, os.X_OK)
 
 
+def ref_takes_schedules() -> bool:
+    """Whether the fm_ref_dump at hand knows the at=<block> arguments (its usage line says so): a binary kept from before
+    oracle/ref_dump.cpp learnt them does not, and the tests that need them then compare against the recorded digests."""
+    if not have_ref():
+        return False
+    return "at=<block>" in subprocess.run([str(REF_DUMP)], capture_output=True, text=True).stderr
+
+
 def digest(a) -> str:
     """dtype, size and sha256 of an array's bytes: equal digests <=> bit-identical arrays (what the recorded reference outputs hold)."""
     a = np.ascontiguousarray(a)

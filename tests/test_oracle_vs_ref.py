@@ -69,9 +69,9 @@ def _assert_same(ref, orc):
     assert np.array_equal(ref["rds_bytes"], orc["rds_bytes"])
 
 
-def _check(key, cap, orc, tmp_path, **ref_kw):
-    """The oracle's streams `orc` for capture `cap` against the reference: live where oracle/_ref exists, else as recorded."""
-    if O.have_ref():
+def _check(key, cap, orc, tmp_path, live=None, **ref_kw):
+    """The oracle's streams `orc` for capture `cap` against the reference: live where oracle/_ref exists (`live`: and can run the case), else as recorded."""
+    if O.have_ref() if live is None else live:
         _assert_same(O.run_ref_chain(cap, tmp_path, **ref_kw), orc)
         return
     rec = O.ref_records()[key]
@@ -104,6 +104,46 @@ def _ctl(**kw):
 def test_controls_bit_exact(tmp_path, capture_u8, args, ctl):
     cap = capture_u8[: 65536 * 6]
     _check(controls_key(args), cap, O.run_chain(cap, 65536, controls=_ctl(**ctl)), tmp_path, block_size=65536, extra_args=args)
+
+
+def schedule_cases():
+    """(name, one-station schedule, cf32?): every station that S1-S4 (tests/control_schedules.py) touch, as a run of its own, and one cf32 run."""
+    import control_schedules as S
+    cases = []
+    for name in ("S1", "S2", "S3", "S4", "S4b"):
+        for st in sorted(S.touched(S.SCHEDULES[name], S.N_STATIONS)):
+            one = S.station_schedule(S.SCHEDULES[name], st)
+            if name == "S4b" and one == S.station_schedule(S.S4, st):
+                continue
+            cases.append((f"{name}/station{st}", one, False))
+    cases.append(("S3/station0/cf32", S.station_schedule(S.S3, 0), True))
+    return cases
+
+
+def schedule_key(name) -> str:
+    return "oracle_vs_ref/schedule/" + name
+
+
+def schedule_capture(cf32: bool) -> np.ndarray:
+    return cf32_capture()[: 16384 * 12] if cf32 else chain_capture()[: 16384 * 12]
+
+
+def flat(res: dict) -> dict:
+    """The blockwise driver's one-station result in run_chain's form."""
+    import control_schedules as S
+    return {k: S.joined(res, k, 0) for k in res}
+
+
+@pytest.mark.parametrize("name,sched,cf32", schedule_cases(), ids=[c[0] for c in schedule_cases()])
+def test_control_schedule_bit_exact(tmp_path, name, sched, cf32):
+    """Controls changed between blocks: a filter re-designed under a live history, a de-emphasis IIR whose state stays frozen while
+    it is switched off, the mixing switched from one block to the next (reference UpdateFilters, broadcast_fm_demod.cpp:330-389, and
+    the switch at :404): twelve 16384-sample blocks, the reference given the events as at=<block> arguments (oracle/ref_dump.cpp).
+    An fm_ref_dump kept from before the harness took those arguments cannot run the case: then, as without oracle/_ref, the recorded digests decide."""
+    import control_schedules as S
+    cap = schedule_capture(cf32)
+    orc = flat(S.run_oracle(cap[None], 16384, 1_024_000, sched, streams=STREAMS + list(BOOL_TRACES)))
+    _check(schedule_key(name), cap, orc, tmp_path, live=O.ref_takes_schedules(), block_size=16384, u8=not cf32, extra_args=S.ref_args(sched))
 
 
 def test_cf32_boundary_bit_exact(tmp_path):
