@@ -180,6 +180,23 @@ MODMON_STATUS_DTYPE = np.dtype([("samples", "<u8"), ("intervals", "<u8"), ("seco
 MODMON_BINS = 300
 
 
+class SquelchConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_samples", C.c_longlong), ("device", C.c_int)]
+
+
+class SquelchParams(C.Structure):
+    """include/fmdemod.h fmd_squelch_params"""
+    _fields_ = [("open_db", C.c_double), ("close_db", C.c_double), ("min_level_db", C.c_double), ("open_intervals", C.c_int),
+                ("close_intervals", C.c_int), ("mode", C.c_int)]
+
+
+# include/fmdemod.h fmd_squelch_status (368 bytes)
+SQUELCH_STATUS_DTYPE = np.dtype([("samples", "<u8"), ("intervals", "<u8"), ("intervals_open", "<u8"), ("ring_s2", "<f8", (20,)),
+                                 ("ring_s4", "<f8", (20,)), ("last_peak", "<f4"), ("hold_peak", "<f4"), ("run", "<u4"), ("transitions", "<u4"),
+                                 ("nonfinite", "<u4"), ("open", "u1"), ("mode", "u1"), ("reserved", "u1", (2,))])
+FMD_SQUELCH_AUTO, FMD_SQUELCH_FORCE_OPEN, FMD_SQUELCH_FORCE_CLOSED = 0, 1, 2
+
+
 class PlanInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("effective_channels", "pilot_power_rows", "pll_k_adaptive", "pll_chained", "pll_waves", "lmr_inline", "lazy_capable",
                                        "front_lds_pad", "front_big_tile", "extract_auto_pair", "pll_kernel")]
@@ -392,6 +409,25 @@ def load_library():
     L.fmd_modmon_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.fmd_modmon_last_error.restype = C.c_char_p
     L.fmd_modmon_last_error.argtypes = [C.c_void_p]
+    L.fmd_squelch_default_params.argtypes = [C.POINTER(SquelchParams)]
+    L.fmd_squelch_default_params.restype = None
+    L.fmd_squelch_threshold.argtypes = [C.c_double]
+    L.fmd_squelch_threshold.restype = C.c_double
+    L.fmd_squelch_level_db.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+    L.fmd_squelch_cnr_db.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.fmd_squelch_powers.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.fmd_squelch_create.argtypes = [C.POINTER(SquelchConfig), C.POINTER(C.c_void_p)]
+    L.fmd_squelch_destroy.argtypes = [C.c_void_p]
+    L.fmd_squelch_reset.argtypes = [C.c_void_p, C.c_int]
+    L.fmd_squelch_reset_peaks.argtypes = [C.c_void_p, C.c_int]
+    L.fmd_squelch_set_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SquelchParams)]
+    L.fmd_squelch_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SquelchParams)]
+    L.fmd_squelch_process_cf32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fmd_squelch_process_u8_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fmd_squelch_get_status.argtypes = [C.c_void_p, C.c_void_p]
+    L.fmd_squelch_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.fmd_squelch_last_error.restype = C.c_char_p
+    L.fmd_squelch_last_error.argtypes = [C.c_void_p]
     L.fmd_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.argtypes = [C.c_void_p]
@@ -1698,4 +1734,153 @@ class ModulationMonitor:
         """fmd_modmon_status_dev: the address of the device's own [C] records, valid until the next process call"""
         p = C.c_void_p()
         self._check(self.L.fmd_modmon_status_dev(self.m, C.byref(p)))
+        return p.value
+
+
+def _squelch_raise(L, rc):
+    raise FmdError(rc, L.fmd_squelch_last_error(None).decode() or L.fmd_status_string(rc).decode())
+
+
+def squelch_default_params() -> SquelchParams:
+    """fmd_squelch_default_params: 10 dB to open, 7 dB to stay open, no level floor, 2 intervals to open, 10 to close, FMD_SQUELCH_AUTO"""
+    p = SquelchParams()
+    load_library().fmd_squelch_default_params(C.byref(p))
+    return p
+
+
+def squelch_threshold(db: float) -> float:
+    """fmd_squelch_threshold (host only): (k k) / ((1 + k) (1 + k)), k = 10^(db / 10) -- what the gate compares (2 S2^2 - M S4) / S2^2 with"""
+    return load_library().fmd_squelch_threshold(float(db))
+
+
+def _squelch_record(record):
+    r = np.ascontiguousarray(record, SQUELCH_STATUS_DTYPE).reshape(-1)
+    if r.size != 1:
+        raise ValueError("one status record at a time")
+    return r
+
+
+def squelch_level_db(record, fs: int) -> float:
+    """fmd_squelch_level_db of one SQUELCH_STATUS_DTYPE record: the newest interval's mean power in dB of the input's own units
+    (FMD_ERR_STATE before the first interval)"""
+    L, r, out = load_library(), _squelch_record(record), C.c_double(0.0)
+    rc = L.fmd_squelch_level_db(r.ctypes.data_as(C.c_void_p), int(fs), C.byref(out))
+    if rc != FMD_OK:
+        _squelch_raise(L, rc)
+    return out.value
+
+
+def squelch_cnr_db(record, fs: int, window: int = 1) -> float:
+    """fmd_squelch_cnr_db: the envelope-constancy carrier-to-noise ratio over the newest `window` (1 ... 20) intervals in dB, -inf where no
+    carrier shows and +inf where no noise does (FMD_ERR_STATE while fewer intervals are complete)"""
+    L, r, out = load_library(), _squelch_record(record), C.c_double(0.0)
+    rc = L.fmd_squelch_cnr_db(r.ctypes.data_as(C.c_void_p), int(fs), int(window), C.byref(out))
+    if rc != FMD_OK:
+        _squelch_raise(L, rc)
+    return out.value
+
+
+def squelch_powers(record, fs: int, window: int = 1):
+    """fmd_squelch_powers: (carrier, noise) power per sample over the newest `window` intervals, in the input's own units squared"""
+    L, r, a, b = load_library(), _squelch_record(record), C.c_double(0.0), C.c_double(0.0)
+    rc = L.fmd_squelch_powers(r.ctypes.data_as(C.c_void_p), int(fs), int(window), C.byref(a), C.byref(b))
+    if rc != FMD_OK:
+        _squelch_raise(L, rc)
+    return a.value, b.value
+
+
+class Squelch:
+    """Carrier squelch of C stations' baseband on the GPU (fmd_squelch_*): per station and 50 ms interval the power moments behind an
+    envelope-constancy CNR, a hysteresis gate, and the [C] uint8 mask that AudioMixer.process(active=...), LoudnessMeter.process and
+    ModulationMonitor.process take as it is.  Feed it the [C, n, 2] float32 or uint8 CUDA tensors the demodulator takes (a channeliser's
+    output); it changes nothing in them.  status() returns SQUELCH_STATUS_DTYPE records; the squelch_* functions turn them into dB."""
+
+    def __init__(self, n_channels: int, fs: int, max_input_samples: int = 1 << 20, device: int = -1):
+        self.L = load_library()
+        cfg = SquelchConfig(int(n_channels), int(fs), int(max_input_samples), device)
+        self.q = C.c_void_p()
+        rc = self.L.fmd_squelch_create(C.byref(cfg), C.byref(self.q))
+        if rc != FMD_OK:
+            self.q = None
+            _squelch_raise(self.L, rc)
+        self.n_channels, self.fs = int(n_channels), int(fs)
+
+    def close(self):
+        if getattr(self, "q", None):
+            self.L.fmd_squelch_destroy(self.q)
+            self.q = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc < 0:
+            raise FmdError(rc, (self.L.fmd_squelch_last_error(self.q) or b"").decode() or self.L.fmd_status_string(rc).decode())
+        return rc
+
+    def process(self, x, n: int | None = None, active=None, mask=None, stream=None):
+        """takes the first n samples (default all) of x: [C, >= n, 2] float32 or uint8 on the device, contiguous samples; active: None or a
+        [C] uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole and keeps its mask byte); mask: the [C] uint8 CUDA tensor
+        to write, None = a new one.  Returns the mask tensor.  Asynchronous on `stream` (default: torch's current)."""
+        import torch
+        if not (x.is_cuda and x.dtype in (torch.float32, torch.uint8) and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
+                and x.stride(2) == 1 and x.stride(1) == 2):
+            raise ValueError("x must be a CUDA float32 or uint8 tensor [C, n, 2] with contiguous samples")
+        n = int(x.shape[1]) if n is None else int(n)
+        if active is not None:
+            if active.dtype == torch.bool:
+                active = active.view(torch.uint8)
+            if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (self.n_channels,) and active.is_contiguous()):
+                raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        if mask is None:
+            # zeroed on the stream the call then writes it on (0 is the default stream, on which torch works unless told otherwise)
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=x.device) if stream else torch.cuda.default_stream(x.device)):
+                mask = torch.zeros(self.n_channels, dtype=torch.uint8, device=x.device)
+        elif not (mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == (self.n_channels,) and mask.is_contiguous()):
+            raise ValueError("mask must be a contiguous [C] uint8 CUDA tensor")
+        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
+        fn = self.L.fmd_squelch_process_cf32_dev if x.dtype == torch.float32 else self.L.fmd_squelch_process_u8_dev
+        self._check(fn(self.q, C.c_void_p(x.data_ptr()), in_stride, n, None if active is None else C.c_void_p(active.data_ptr()),
+                       C.c_void_p(mask.data_ptr()), C.c_void_p(stream)))
+        return mask
+
+    def set_params(self, channel: int = -1, **fields):
+        """fmd_squelch_set_params: the named fields of SquelchParams for station `channel` (-1 = every station, each keeping its other
+        fields); ordered behind the squelch's earlier work, they apply from the next interval that ends"""
+        for c in (range(self.n_channels) if channel < 0 else (int(channel),)):
+            p = self.params(c)
+            for k, v in fields.items():
+                if k not in dict(SquelchParams._fields_):
+                    raise TypeError(f"SquelchParams has no field {k}")
+                setattr(p, k, v)
+            self._check(self.L.fmd_squelch_set_params(self.q, c, C.byref(p)))
+
+    def params(self, channel: int) -> SquelchParams:
+        p = SquelchParams()
+        self._check(self.L.fmd_squelch_get_params(self.q, int(channel), C.byref(p)))
+        return p
+
+    def reset(self, channel: int = -1):
+        self._check(self.L.fmd_squelch_reset(self.q, int(channel)))
+
+    def reset_peaks(self, channel: int = -1):
+        self._check(self.L.fmd_squelch_reset_peaks(self.q, int(channel)))
+
+    def status(self) -> np.ndarray:
+        """[C] SQUELCH_STATUS_DTYPE records; waits for the squelch's work"""
+        out = np.zeros(self.n_channels, SQUELCH_STATUS_DTYPE)
+        self._check(self.L.fmd_squelch_get_status(self.q, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def status_dev_ptr(self) -> int:
+        """fmd_squelch_status_dev: the address of the device's own [C] records, valid until the next process call"""
+        p = C.c_void_p()
+        self._check(self.L.fmd_squelch_status_dev(self.q, C.byref(p)))
         return p.value

@@ -1,0 +1,375 @@
+// Carrier squelch, device side (include/fmdemod.h, "Carrier squelch").
+//
+// NOT in the reference.  Per station and per 50 ms interval the power moments S2 = sum |z|^2 and S4 = sum |z|^4 and the peak of the
+// station baseband [C][in_stride][2] (cf32 or u8) that the demodulator takes and the channeliser writes, read in place; at an interval's
+// end the hysteresis gate, and at a call's end the [C] mask byte that the other side objects take as d_active.
+//
+// One kernel per call, k_squelch<format>.  One wavefront per station; lane l owns partials 4 l ... 4 l + 3 of the two interval sums
+// outright and adds its terms in ascending r, r the sample's place in its interval.  The wavefront walks rows of 256 consecutive samples
+// (2 KB of cf32 as two 16-byte loads per lane, 512 bytes of u8 as one 8-byte load, non-temporal: the IQ is read once), four rows in
+// registers ahead of the row it works on.  A row starts at a multiple of 256 of r, so the first row of a call and the rows around an
+// interval's end are partial: a lane's sample outside the segment at hand is not loaded and reads as (+0, +0), which changes no partial
+// (p = +0, s + +0 = s, fma(+0, +0, s) = s: a partial is never -0) and no peak.  An interval's end is wave-uniform: the partials fold by
+// cross-lane moves in the contract's halving order, and lane 0 alone runs the gate and stores, with ordinary stores.  The open
+// interval's 4 KB of partials are read at the call's start and written at its end.  No atomics, no LDS, no scratch.
+//
+// Denormals: fp64 and fp32 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "fmd_iq.h"
+#include "fmd_squelch_design.h"
+#include "fmdemod.h"
+
+using fmd::kSquelchPartials;
+using fmd::kSquelchRing;
+using fmd::SquelchGate;
+
+namespace {
+
+constexpr int kT = 64;               // threads per workgroup: one wavefront, one station
+constexpr int kQ = 4;                // samples (and partials) per lane and row
+constexpr int kRow = kT * kQ;        // samples per row
+constexpr int kPf = 4;               // rows loaded ahead
+constexpr int kPartD = 2 * kSquelchPartials;   // doubles per station: the open interval's s2 and s4 partials
+static_assert(kSquelchPartials == kRow && kSquelchRing == 20, "k_squelch's lane layout");
+
+static_assert(sizeof(fmd_squelch_status) == 368 && offsetof(fmd_squelch_status, intervals) == 8 && offsetof(fmd_squelch_status, intervals_open) == 16 &&
+              offsetof(fmd_squelch_status, ring_s2) == 24 && offsetof(fmd_squelch_status, ring_s4) == 184 && offsetof(fmd_squelch_status, last_peak) == 344 &&
+              offsetof(fmd_squelch_status, hold_peak) == 348 && offsetof(fmd_squelch_status, run) == 352 && offsetof(fmd_squelch_status, transitions) == 356 &&
+              offsetof(fmd_squelch_status, nonfinite) == 360 && offsetof(fmd_squelch_status, open) == 364 && offsetof(fmd_squelch_status, mode) == 365 &&
+              offsetof(fmd_squelch_status, reserved) == 366, "fmd_squelch_status layout");
+static_assert(sizeof(SquelchGate) == 40, "SquelchGate layout");
+
+// A lane's four samples of a row, loaded at once.  The station's rows are aligned to a sample only (8 bytes of cf32, 2 of u8): the types
+// carry that alignment, and the device's global loads take any.
+typedef float sq_f4 __attribute__((ext_vector_type(4), aligned(8)));
+typedef float sq_f2 __attribute__((ext_vector_type(2)));
+typedef unsigned sq_u2 __attribute__((ext_vector_type(2), aligned(2)));
+
+__device__ __forceinline__ void sq_load4(const float2* p, float2 (&z)[kQ]) {
+    const sq_f4 a = __builtin_nontemporal_load(reinterpret_cast<const sq_f4*>(p));
+    const sq_f4 b = __builtin_nontemporal_load(reinterpret_cast<const sq_f4*>(p + 2));
+    z[0] = make_float2(a.x, a.y); z[1] = make_float2(a.z, a.w); z[2] = make_float2(b.x, b.y); z[3] = make_float2(b.z, b.w);
+}
+__device__ __forceinline__ void sq_load4(const unsigned short* p, unsigned short (&z)[kQ]) {
+    const sq_u2 a = __builtin_nontemporal_load(reinterpret_cast<const sq_u2*>(p));
+    z[0] = (unsigned short)(a.x & 0xffffu); z[1] = (unsigned short)(a.x >> 16); z[2] = (unsigned short)(a.y & 0xffffu); z[3] = (unsigned short)(a.y >> 16);
+}
+__device__ __forceinline__ float2 sq_load1(const float2* p) {
+    const sq_f2 v = __builtin_nontemporal_load(reinterpret_cast<const sq_f2*>(p));
+    return make_float2(v.x, v.y);
+}
+__device__ __forceinline__ unsigned short sq_load1(const unsigned short* p) { return __builtin_nontemporal_load(p); }
+
+// in [C][in_stride] IQ pairs; gate [C]; status [C]; part [C][2][256]; carry [C]; mask [C] or null
+template <typename S>
+__global__ __launch_bounds__(kT) void k_squelch(const typename fmd::Iq<S>::raw* __restrict__ in, long long in_stride, long long n,
+                                                const uint8_t* __restrict__ active, int M, const SquelchGate* __restrict__ gate,
+                                                fmd_squelch_status* __restrict__ status, double* __restrict__ part, float* __restrict__ carry,
+                                                uint8_t* __restrict__ mask) {
+    using raw = typename fmd::Iq<S>::raw;
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (active && active[c] == 0) return;                                    // (uniform over the wavefront)
+    fmd_squelch_status* st = status + c;
+    const SquelchGate gt = gate[c];
+    unsigned open = st->open;
+    if (n == 0) {                                                            // nothing of the station changes; its mask byte is still written
+        if (lane == 0 && mask) mask[c] = (uint8_t)(gt.mode == FMD_SQUELCH_AUTO ? open : gt.mode == FMD_SQUELCH_FORCE_OPEN);
+        return;
+    }
+    const raw* base = in + (size_t)c * (size_t)in_stride;
+    double* pp = part + (size_t)c * kPartD + kQ * lane;
+
+    const unsigned long long samples0 = st->samples;
+    unsigned long long G = st->intervals;
+    int r0 = __builtin_amdgcn_readfirstlane((int)(samples0 - G * (unsigned long long)M));   // the first sample's place in its interval
+    // the gate's state: lane 0's copies are the ones that are updated and stored
+    unsigned run = st->run, transitions = st->transitions, nonfinite = st->nonfinite;
+    unsigned long long g_open = st->intervals_open;
+    float cpk = carry[c];                                                    // the open interval's peak before this call
+    double s2[kQ], s4[kQ];
+#pragma unroll
+    for (int k = 0; k < kQ; k++) { s2[k] = pp[k]; s4[k] = pp[kSquelchPartials + k]; }
+    float pk = 0.0f;                                                         // the lane's, over the segment at hand
+    float hmax = 0.0f;                                                       // over the call
+
+    long long s0 = 0;                                                        // the segment's first sample: a segment ends with its interval or the call
+    while (s0 < n) {
+        const long long left = (long long)(M - r0);
+        const long long seg_end = n - s0 < left ? n : s0 + left;
+        const long long rb = s0 - (long long)(r0 & (kRow - 1));              // the first row's sample 0 (before s0: those samples read as zero)
+
+        raw nxt[kPf][kQ];
+        auto fetch = [&](long long row) {
+#pragma unroll
+            for (int p = 0; p < kPf; p++) {
+                const long long i = row + (long long)p * kRow + kQ * lane;
+                if (i >= s0 && i + kQ <= seg_end) sq_load4(base + i, nxt[p]);
+                else {
+#pragma unroll
+                    for (int k = 0; k < kQ; k++) {
+                        nxt[p][k] = fmd::Iq<S>::zero();
+                        if (i + k >= s0 && i + k < seg_end) nxt[p][k] = sq_load1(base + i + k);
+                    }
+                }
+            }
+        };
+        auto process = [&](const raw (&v)[kQ]) {
+#pragma unroll
+            for (int k = 0; k < kQ; k++) {
+                const float2 z = fmd::Iq<S>::cf32(v[k]);
+                const double I = (double)z.x, Q = (double)z.y;
+                const double p = fma(I, I, Q * Q);
+                s2[k] = s2[k] + p;
+                s4[k] = fma(p, p, s4[k]);
+                pk = fmaxf(pk, fmaxf(fabsf(z.x), fabsf(z.y)));
+            }
+        };
+
+        fetch(rb);
+        for (long long row = rb; row < seg_end; row += (long long)kPf * kRow) {
+            raw cur[kPf][kQ];
+#pragma unroll
+            for (int p = 0; p < kPf; p++)
+#pragma unroll
+                for (int k = 0; k < kQ; k++) cur[p][k] = nxt[p][k];
+            if (row + (long long)kPf * kRow < seg_end) fetch(row + (long long)kPf * kRow);   // in flight while these rows run
+#pragma unroll
+            for (int p = 0; p < kPf; p++)
+                if (row + (long long)p * kRow < seg_end) process(cur[p]);
+        }
+
+        // the segment's peak: no operand is ever a NaN, so the order of a maximum does not matter
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) pk = fmaxf(pk, __shfl_xor(pk, d));
+        cpk = fmaxf(cpk, pk);
+        hmax = fmaxf(hmax, pk);
+        pk = 0.0f;
+        r0 += (int)(seg_end - s0);
+        if (r0 == M) {                                                       // the interval is complete (wave-uniform)
+#pragma unroll
+            for (int w = kT / 2; w >= 1; w >>= 1) {                          // p_j += p_{j+w} for j < w, w = 128 ... 4: partial j + w sits 'w / 4' lanes up
+#pragma unroll
+                for (int k = 0; k < kQ; k++) { s2[k] += __shfl_down(s2[k], w); s4[k] += __shfl_down(s4[k], w); }
+            }
+            s2[0] += s2[2]; s2[1] += s2[3]; s2[0] += s2[1];                  // w = 2, 1
+            s4[0] += s4[2]; s4[1] += s4[3]; s4[0] += s4[1];
+            if (lane == 0) {
+                const double S2 = s2[0], S4 = s4[0];
+                const int k = (int)(G % (unsigned long long)kSquelchRing);
+                st->ring_s2[k] = S2; st->ring_s4[k] = S4; st->last_peak = cpk;
+                const bool finite = fabs(S2) <= 1.7976931348623157e308 && fabs(S4) <= 1.7976931348623157e308;   // neither inf nor NaN
+                if (!finite) nonfinite++;
+                const double a = S2 * S2;
+                const double d = fma(-(double)M, S4, 2.0 * a);
+                const bool level = finite && S2 >= gt.min_s2;
+                if (!open) {
+                    run = level && d > gt.c_open * a ? run + 1 : 0;
+                    if (run >= (unsigned)gt.open_intervals) { open = 1; run = 0; transitions++; }
+                } else {
+                    run = level && d > gt.c_close * a ? 0 : run + 1;
+                    if (run >= (unsigned)gt.close_intervals) { open = 0; run = 0; transitions++; }
+                }
+                if (open) g_open++;
+            }
+            G++;
+#pragma unroll
+            for (int k = 0; k < kQ; k++) { s2[k] = 0.0; s4[k] = 0.0; }
+            cpk = 0.0f;
+            r0 = 0;
+        }
+        s0 = seg_end;
+    }
+
+    // what the next call needs: the open interval's partials and peak, and the gate
+#pragma unroll
+    for (int k = 0; k < kQ; k++) { pp[k] = s2[k]; pp[kSquelchPartials + k] = s4[k]; }
+    if (lane == 0) {
+        carry[c] = cpk;
+        st->hold_peak = fmaxf(st->hold_peak, hmax);
+        st->samples = samples0 + (unsigned long long)n;
+        st->intervals = G;
+        st->intervals_open = g_open;
+        st->run = run; st->transitions = transitions; st->nonfinite = nonfinite;
+        st->open = (unsigned char)open;
+        if (mask) mask[c] = (uint8_t)(gt.mode == FMD_SQUELCH_AUTO ? open : gt.mode == FMD_SQUELCH_FORCE_OPEN);
+    }
+}
+
+// stations c0 ... as after create (everything 0, the gate closed, the mode the parameters'), or with `peaks` their hold_peak alone
+__global__ __launch_bounds__(kT) void k_squelch_reset(int c0, int peaks, const SquelchGate* __restrict__ gate, fmd_squelch_status* __restrict__ status,
+                                                      double* __restrict__ part, float* __restrict__ carry) {
+    const int c = c0 + blockIdx.x, t = threadIdx.x;
+    fmd_squelch_status* st = status + c;
+    if (peaks) {
+        if (t == 0) st->hold_peak = 0.0f;
+        return;
+    }
+    unsigned* w = reinterpret_cast<unsigned*>(st);
+    for (int i = t; i < (int)(sizeof(fmd_squelch_status) / 4); i += kT) w[i] = 0u;
+    for (int i = t; i < kPartD; i += kT) part[(size_t)c * kPartD + i] = 0.0;
+    __syncthreads();
+    if (t == 0) { carry[c] = 0.0f; st->mode = (unsigned char)gate[c].mode; }
+}
+
+// the parameters of stations c0 ...
+__global__ __launch_bounds__(kT) void k_squelch_set(int c0, int cn, SquelchGate g, SquelchGate* __restrict__ gate, fmd_squelch_status* __restrict__ status) {
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (i >= cn) return;
+    gate[c0 + i] = g;
+    status[c0 + i].mode = (unsigned char)g.mode;
+}
+
+}  // namespace
+
+struct fmd_squelch_s {
+    int device = 0, C = 0, fs = 0, M = 0;
+    long long max_in = 0;
+    std::vector<fmd_squelch_params> params;  // [C], as set
+    fmd_squelch_status* d_status = nullptr;  // [C]
+    SquelchGate* d_gate = nullptr;           // [C]
+    double* d_part = nullptr;                // [C][2][256]
+    float* d_carry = nullptr;                // [C]
+    hipEvent_t done = nullptr;               // end of the previous call's work
+    bool have_done = false;
+    std::string err;
+};
+
+static int sq_fail(fmd_squelch q, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
+    if (q) q->err = buf; else fmd::squelch_global_error() = buf;
+    return code;
+}
+
+static bool sq_quiesce(fmd_squelch q) {
+    return hipSetDevice(q->device) == hipSuccess && (!q->have_done || hipEventSynchronize(q->done) == hipSuccess);
+}
+
+static int sq_reset(fmd_squelch q, int channel, int peaks) {
+    if (!q) return FMD_ERR_ARG;
+    if (channel < -1 || channel >= q->C) return sq_fail(q, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, q->C);
+    if (!sq_quiesce(q)) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
+    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? q->C : 1;
+    hipLaunchKernelGGL(k_squelch_reset, dim3((unsigned)cn), dim3(kT), 0, nullptr, c0, peaks, q->d_gate, q->d_status, q->d_part, q->d_carry);
+    if (hipGetLastError() != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "k_squelch_reset launch failed");
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    return FMD_OK;
+}
+
+template <typename S>
+static int sq_process(fmd_squelch q, const void* d_in, size_t align, long long in_stride, long long n, const uint8_t* d_active, uint8_t* d_mask, void* stream) {
+    if (!q) return FMD_ERR_ARG;
+    if (!d_in || reinterpret_cast<uintptr_t>(d_in) % align != 0) return sq_fail(q, FMD_ERR_ARG, "null input, or input not aligned to %zu bytes", align);
+    if (n < 0 || n > in_stride || n > q->max_in)
+        return sq_fail(q, FMD_ERR_ARG, "n %lld outside [0, in_stride %lld] or above max_input_samples %lld", n, in_stride, q->max_in);
+    if (n == 0 && !d_mask) return FMD_OK;                                    // nothing of any station changes and there is no mask to write
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipSetDevice(q->device) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "hipSetDevice failed");
+    // every station's state carries over from call to call: a caller that switches streams is ordered behind the previous call
+    if (q->have_done && hipStreamWaitEvent(s, q->done, 0) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "stream wait failed");
+    hipLaunchKernelGGL(k_squelch<S>, dim3((unsigned)q->C), dim3(kT), 0, s, static_cast<const typename fmd::Iq<S>::raw*>(d_in), in_stride, n, d_active, q->M,
+                       q->d_gate, q->d_status, q->d_part, q->d_carry, d_mask);
+    if (hipGetLastError() != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "k_squelch launch failed");
+    if (hipEventRecord(q->done, s) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "event record failed");
+    q->have_done = true;
+    return FMD_OK;
+}
+
+extern "C" {
+
+int fmd_squelch_create(const fmd_squelch_config* cfg, fmd_squelch* out) {
+    if (!cfg || !out) return sq_fail(nullptr, FMD_ERR_ARG, "null configuration or handle");
+    if (cfg->n_channels <= 0 || cfg->max_input_samples <= 0 || cfg->max_input_samples > (1LL << 30))
+        return sq_fail(nullptr, FMD_ERR_ARG, "n_channels %d is not positive or max_input_samples %lld outside (0, 2^30]", cfg->n_channels, cfg->max_input_samples);
+    const int M = fmd::squelch_interval(cfg->fs);
+    if (M == 0) return sq_fail(nullptr, FMD_ERR_ARG, "fs %d is not a multiple of 1000 in 192000 ... 384000", cfg->fs);
+    if (fmd_device_count() <= 0) return sq_fail(nullptr, FMD_ERR_NO_DEVICE, "no gfx950 device");
+    int dev = cfg->device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return sq_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
+    fmd_squelch q = new fmd_squelch_s();
+    q->device = dev; q->C = cfg->n_channels; q->fs = cfg->fs; q->M = M; q->max_in = cfg->max_input_samples;
+    fmd_squelch_params p{};
+    fmd_squelch_default_params(&p);
+    q->params.assign((size_t)q->C, p);
+    const size_t C = (size_t)q->C;
+    bool ok = hipSetDevice(dev) == hipSuccess;
+    ok = ok && hipMalloc(&q->d_status, sizeof(fmd_squelch_status) * C) == hipSuccess;
+    ok = ok && hipMalloc(&q->d_gate, sizeof(SquelchGate) * C) == hipSuccess;
+    ok = ok && hipMalloc(&q->d_part, sizeof(double) * kPartD * C) == hipSuccess;
+    ok = ok && hipMalloc(&q->d_carry, sizeof(float) * C) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&q->done, hipEventDisableTiming) == hipSuccess;
+    if (!ok || fmd_squelch_set_params(q, -1, &p) != FMD_OK || fmd_squelch_reset(q, -1) != FMD_OK) {
+        fmd_squelch_destroy(q);
+        return sq_fail(nullptr, FMD_ERR_DEVICE, "device allocation failed");
+    }
+    *out = q;
+    return FMD_OK;
+}
+
+int fmd_squelch_destroy(fmd_squelch q) {
+    if (!q) return FMD_ERR_ARG;
+    (void)sq_quiesce(q);
+    for (void* p : {(void*)q->d_status, (void*)q->d_gate, (void*)q->d_part, (void*)q->d_carry})
+        if (p) (void)hipFree(p);
+    if (q->done) (void)hipEventDestroy(q->done);
+    delete q;
+    return FMD_OK;
+}
+
+int fmd_squelch_reset(fmd_squelch q, int channel) { return sq_reset(q, channel, 0); }
+
+int fmd_squelch_reset_peaks(fmd_squelch q, int channel) { return sq_reset(q, channel, 1); }
+
+int fmd_squelch_set_params(fmd_squelch q, int channel, const fmd_squelch_params* p) {
+    if (!q) return FMD_ERR_ARG;
+    if (channel < -1 || channel >= q->C) return sq_fail(q, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, q->C);
+    SquelchGate g;
+    if (fmd::squelch_gate(p, q->M, &g, &q->err) != FMD_OK) return FMD_ERR_ARG;
+    if (!sq_quiesce(q)) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
+    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? q->C : 1;
+    hipLaunchKernelGGL(k_squelch_set, dim3((unsigned)((cn + kT - 1) / kT)), dim3(kT), 0, nullptr, c0, cn, g, q->d_gate, q->d_status);
+    if (hipGetLastError() != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "k_squelch_set launch failed");
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    for (int c = c0; c < c0 + cn; c++) q->params[(size_t)c] = *p;
+    return FMD_OK;
+}
+
+int fmd_squelch_get_params(fmd_squelch q, int channel, fmd_squelch_params* p) {
+    if (!q || !p) return sq_fail(q, FMD_ERR_ARG, "null squelch or output");
+    if (channel < 0 || channel >= q->C) return sq_fail(q, FMD_ERR_ARG, "channel %d outside [0, %d)", channel, q->C);
+    *p = q->params[(size_t)channel];
+    return FMD_OK;
+}
+
+int fmd_squelch_process_cf32_dev(fmd_squelch q, const float* d_in, long long in_stride, long long n, const uint8_t* d_active, uint8_t* d_mask, void* stream) {
+    return sq_process<float2>(q, d_in, 8, in_stride, n, d_active, d_mask, stream);
+}
+
+int fmd_squelch_process_u8_dev(fmd_squelch q, const uint8_t* d_in, long long in_stride, long long n, const uint8_t* d_active, uint8_t* d_mask, void* stream) {
+    return sq_process<uint8_t>(q, d_in, 2, in_stride, n, d_active, d_mask, stream);
+}
+
+int fmd_squelch_get_status(fmd_squelch q, fmd_squelch_status* out) {
+    if (!q || !out) return sq_fail(q, FMD_ERR_ARG, "null squelch or output");
+    if (!sq_quiesce(q)) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
+    if (hipMemcpy(out, q->d_status, sizeof(fmd_squelch_status) * (size_t)q->C, hipMemcpyDeviceToHost) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "copy failed");
+    return FMD_OK;
+}
+
+int fmd_squelch_status_dev(fmd_squelch q, const fmd_squelch_status** d_status) {
+    if (!q || !d_status) return sq_fail(q, FMD_ERR_ARG, "null squelch or output");
+    *d_status = q->d_status;
+    return FMD_OK;
+}
+
+const char* fmd_squelch_last_error(fmd_squelch q) { return q ? q->err.c_str() : fmd::squelch_global_error().c_str(); }
+
+}  // extern "C"

@@ -934,6 +934,123 @@ int fmd_modmon_get_histogram(fmd_modmon m, unsigned* hist);
 int fmd_modmon_status_dev(fmd_modmon m, const fmd_modmon_status** d_status);
 const char* fmd_modmon_last_error(fmd_modmon m);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Carrier squelch (NOT part of the reference, which tunes one station in hardware): whether there is a station in a channel at all,
+ * and how clean it is.  It reads the device array [C][in_stride][2] (cf32 or u8) that the demodulator takes and the channeliser writes,
+ * changes nothing in it, keeps per station and per 50 ms interval the two power moments S2 = sum |z|^2 and S4 = sum |z|^4, runs a
+ * hysteresis gate on the device and writes the [C] uint8 mask that the mixer, the loudness meter and the modulation monitor take as
+ * d_active, with no host round trip.
+ *   The estimator: an FM carrier has a constant envelope A, channel noise is complex Gaussian of variance s^2.  Then E|z|^2 = A^2 + s^2
+ *   and E|z|^4 = A^4 + 4 A^2 s^2 + 2 s^4, so 2 (E|z|^2)^2 - E|z|^4 = A^4: over M samples the carrier power is sqrt(2 S2^2 - M S4) / M and
+ *   the noise power what remains of S2 / M.  With k = 10^(dB / 10), "CNR > dB" is (2 S2^2 - M S4) > (k^2 / (1 + k)^2) S2^2: no square
+ *   root, division or logarithm on the device.  The figure is an ENVELOPE-CONSTANCY carrier-to-noise ratio, not a calibrated one:
+ *   multipath, fading, adjacent-channel leakage and a clipping converter all break the constant envelope and read as a lower ratio (a u8
+ *   input whose peak reaches the rails reads wrong: last_peak and hold_peak exist to flag that).  That is what a squelch wants.
+ * Arithmetic, restated in C by tests/cpp/squelch_ref.c; NP = 256 partials, RING = 20 intervals (one second):
+ *   input       u8 converts as (float)v - 127 (fmd_process_u8_*); everything below sees floats i, q.  fp32 and fp64 denormals are kept.
+ *   design      host, double, host libm; fs a multiple of 1000 in 192000 ... 384000 (the modulation monitor's range: at 1.024 and
+ *               2.048 MSa/s a station's feed holds its neighbours and the envelope is not constant):
+ *                 M = fs / 20 (samples of a 50 ms interval)
+ *                 threshold(db) = (k * k) / ((1 + k) * (1 + k)), k = pow(10, db / 10);  c_open = threshold(open_db), c_close likewise
+ *                 min_s2 = pow(10, min_level_db / 10) * M, and +0 for min_level_db = -inf
+ *   per sample  n counted absolutely in 64 bits since the station's reset; interval g = n / M, r = n - g M.
+ *                 I = (double)i, Q = (double)q;  p = fma(I, I, Q * Q)          (the product is exact in double)
+ *               Partial j = r mod 256 takes its terms in ascending r, from +0 at the interval's start:
+ *                 s2_j = s2_j + p;  s4_j = fma(p, p, s4_j)
+ *                 pk = fmaxf(pk, fmaxf(fabsf(i), fabsf(q))) from +0 at the interval's start (a NaN is dropped); the same update goes into
+ *                 hold_peak (+0 at create, reset and reset_peaks).
+ *               An open interval carries pk and its 2 x 256 partials to the next call (4 KB per station).
+ *   interval end  per sum the halving tree p_j += p_{j+w} for j < w, w = 128, 64, ... 1;  S = p_0.
+ *                 ring_s2[g % 20] = S2, ring_s4[g % 20] = S4, last_peak = pk, intervals++
+ *                 finite = isfinite(S2) && isfinite(S4);  not finite -> nonfinite++
+ *                 a = S2 * S2;  d = fma(-(double)M, S4, 2.0 * a)
+ *                 good_open = finite && S2 >= min_s2 && d > c_open * a;  good_close the same with c_close.  The comparisons are strict:
+ *                 an all-zero interval is not good, and a NaN compares false.
+ *   gate        closed: run = good_open ? run + 1 : 0;  run >= open_intervals -> the gate opens, run = 0, transitions++
+ *               open:   run = good_close ? 0 : run + 1; run >= close_intervals -> the gate closes, run = 0, transitions++
+ *               intervals_open++ where the gate is open after the update.
+ *               mask byte = mode == FMD_SQUELCH_AUTO ? open : (mode == FMD_SQUELCH_FORCE_OPEN).  The state machine runs in every mode.
+ *               No atomics; ordinary stores.  Nothing depends, bit for bit, on how the samples are split into calls, on streams, on the
+ *               format, on the batch or on the station's row.
+ *   read-out    host, double, pure functions; fs as in the design (else FMD_ERR_ARG); FMD_ERR_STATE while intervals < window:
+ *                 level_db = 10 * log10(ring_s2[newest] / (double)M)                      (window = 1)
+ *                 cnr_db(window), 1 <= window <= 20: over the newest `window` intervals, oldest first, from +0: e2 += ring_s2, e4 += ring_s4;
+ *                   N = (double)M * (double)window;  d = fma(-N, e4, 2 * e2 * e2);  d <= 0 -> -inf
+ *                   c = sqrt(d) / N;  nz = e2 / N - c;  nz <= 0 -> +inf;  else 10 * log10(c / nz)
+ *                   (a NaN or infinite ring entry in the window makes d a NaN, and the result is a NaN)
+ *                 powers(window): c and nz of the same sums (d <= 0: c = 0 and nz = e2 / N)
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define FMD_SQUELCH_AUTO         0   /* the mask byte follows the gate */
+#define FMD_SQUELCH_FORCE_OPEN   1   /* the mask byte is 1 */
+#define FMD_SQUELCH_FORCE_CLOSED 2   /* the mask byte is 0 */
+typedef struct fmd_squelch_s* fmd_squelch;
+typedef struct {
+    int       n_channels;         /* C: station rows of the input */
+    int       fs;                 /* the baseband's rate: a multiple of 1000 in 192000 ... 384000 */
+    long long max_input_samples;  /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_squelch_config;
+/* defaults: 10.0, 7.0, -inf, 2, 10, FMD_SQUELCH_AUTO.  Valid: 0 <= close_db <= open_db <= 60; min_level_db = -inf or finite;
+ * open_intervals and close_intervals in 1 ... 1000; mode one of FMD_SQUELCH_* */
+typedef struct {
+    double open_db, close_db;     /* the gate opens above open_db and stays open above close_db, in dB of envelope-constancy CNR */
+    double min_level_db;          /* an interval below this mean power, 10 log10(S2 / M) in the input's own units, is never good */
+    int    open_intervals;        /* good intervals in a row that open the gate */
+    int    close_intervals;       /* bad intervals in a row that close it (the hold) */
+    int    mode;
+} fmd_squelch_params;
+/* one per station, 368 bytes: samples at byte 0, intervals 8, intervals_open 16, ring_s2 24, ring_s4 184, last_peak 344, hold_peak 348,
+ * run 352, transitions 356, nonfinite 360, open 364, mode 365, reserved 366 */
+typedef struct {
+    unsigned long long samples;        /* samples seen since reset */
+    unsigned long long intervals;      /* completed 50 ms intervals */
+    unsigned long long intervals_open; /* ... of them with the gate open after their update */
+    double   ring_s2[20], ring_s4[20]; /* interval g at [g % 20]: sum |z|^2 and sum |z|^4 */
+    float    last_peak;                /* max(|i|, |q|) over the newest interval */
+    float    hold_peak;                /* ... since reset or reset_peaks */
+    unsigned run;                      /* the gate's run of good (closed) or bad (open) intervals */
+    unsigned transitions;              /* openings and closings since reset */
+    unsigned nonfinite;                /* intervals with a non-finite S2 or S4 */
+    unsigned char open;                /* the gate: 1 open, 0 closed */
+    unsigned char mode;                /* the station's FMD_SQUELCH_* mode */
+    unsigned char reserved[2];
+} fmd_squelch_status;
+
+/* host-only (no GPU needed) */
+void fmd_squelch_default_params(fmd_squelch_params* p);
+/* (k * k) / ((1 + k) * (1 + k)), k = pow(10, db / 10): what d / S2^2 is compared with */
+double fmd_squelch_threshold(double db);
+int fmd_squelch_level_db(const fmd_squelch_status* s, int fs, double* db);
+int fmd_squelch_cnr_db(const fmd_squelch_status* s, int fs, int window, double* db);
+int fmd_squelch_powers(const fmd_squelch_status* s, int fs, int window, double* carrier, double* noise);
+
+int fmd_squelch_create(const fmd_squelch_config* cfg, fmd_squelch* out);
+int fmd_squelch_destroy(fmd_squelch q);
+/* everything of station `channel` (-1 = every station) as after create: counters, ring, peaks, the open interval and the gate (closed);
+ * its parameters are kept.  Waits for the squelch's earlier work */
+int fmd_squelch_reset(fmd_squelch q, int channel);
+/* hold_peak of station `channel` (-1 = every station) to +0; nothing else */
+int fmd_squelch_reset_peaks(fmd_squelch q, int channel);
+/* the parameters of station `channel` (-1 = every station): ordered behind the squelch's earlier work, they apply from the next interval
+ * that ends.  FMD_ERR_ARG for values outside the ranges above, and nothing changes */
+int fmd_squelch_set_params(fmd_squelch q, int channel, const fmd_squelch_params* p);
+int fmd_squelch_get_params(fmd_squelch q, int channel, fmd_squelch_params* p);
+/* takes n samples of every station.  d_in [C][in_stride][2] on the device, cf32 (8-byte aligned) or u8 (2-byte aligned); d_active: [C]
+ * uint8 on the device, NULL = all: a station whose byte is 0 is skipped whole, and its mask byte is left as it is.  d_mask: [C] uint8 on
+ * the device, caller-owned, may be NULL: behind its work on `stream` the call writes every other station's byte, 1 or 0, also when
+ * n == 0 and for a station whose gate did not move.  n < 0, n > in_stride, n > max_input_samples or a misaligned d_in return FMD_ERR_ARG
+ * and change nothing.  Asynchronous on `stream`; consecutive calls may use different streams (the library orders them). */
+int fmd_squelch_process_cf32_dev(fmd_squelch q, const float* d_in, long long in_stride, long long n, const uint8_t* d_active,
+                                 uint8_t* d_mask, void* stream);
+int fmd_squelch_process_u8_dev(fmd_squelch q, const uint8_t* d_in, long long in_stride, long long n, const uint8_t* d_active,
+                               uint8_t* d_mask, void* stream);
+/* out [C]; synchronises with the squelch's work */
+int fmd_squelch_get_status(fmd_squelch q, fmd_squelch_status* out);
+/* the device's own [C] records, for a consumer on the device: ordered behind the squelch's work on the stream of its last process call,
+ * valid until the next process call */
+int fmd_squelch_status_dev(fmd_squelch q, const fmd_squelch_status** d_status);
+const char* fmd_squelch_last_error(fmd_squelch q);
+
 #ifdef __cplusplus
 }
 #endif
