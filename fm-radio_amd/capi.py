@@ -197,6 +197,24 @@ SQUELCH_STATUS_DTYPE = np.dtype([("samples", "<u8"), ("intervals", "<u8"), ("int
 FMD_SQUELCH_AUTO, FMD_SQUELCH_FORCE_OPEN, FMD_SQUELCH_FORCE_CLOSED = 0, 1, 2
 
 
+class AudmonConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
+
+
+class AudmonParams(C.Structure):
+    """include/fmdemod.h fmd_audmon_params"""
+    _fields_ = [("silence_db", C.c_double), ("loss_db", C.c_double), ("antiphase_corr", C.c_double), ("mono_db", C.c_double),
+                ("raise_intervals", C.c_int * 5), ("clear_intervals", C.c_int * 5), ("alarm_mask", C.c_uint)]
+
+
+# include/fmdemod.h fmd_audmon_status (840 bytes)
+AUDMON_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("intervals", "<u8"), ("intervals_flagged", "<u8", (5,)), ("ring_ll", "<f8", (30,)),
+                                ("ring_rr", "<f8", (30,)), ("ring_lr", "<f8", (30,)), ("last_peak", "<f4", (2,)), ("hold_peak", "<f4", (2,)),
+                                ("run", "<u4", (5,)), ("transitions", "<u4", (5,)), ("nonfinite", "<u4"), ("flags", "u1"), ("ok", "u1"),
+                                ("reserved", "u1", (2,))])
+AUDMON_SILENCE, AUDMON_LEFT_LOST, AUDMON_RIGHT_LOST, AUDMON_ANTIPHASE, AUDMON_MONO = 1, 2, 4, 8, 16
+
+
 class PlanInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("effective_channels", "pilot_power_rows", "pll_k_adaptive", "pll_chained", "pll_waves", "lmr_inline", "lazy_capable",
                                        "front_lds_pad", "front_big_tile", "extract_auto_pair", "pll_kernel")]
@@ -428,6 +446,23 @@ def load_library():
     L.fmd_squelch_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.fmd_squelch_last_error.restype = C.c_char_p
     L.fmd_squelch_last_error.argtypes = [C.c_void_p]
+    L.fmd_audmon_default_params.argtypes = [C.POINTER(AudmonParams)]
+    L.fmd_audmon_default_params.restype = None
+    L.fmd_audmon_level_db.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.fmd_audmon_balance_db.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.fmd_audmon_correlation.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.fmd_audmon_side_mid_db.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.fmd_audmon_create.argtypes = [C.POINTER(AudmonConfig), C.POINTER(C.c_void_p)]
+    L.fmd_audmon_destroy.argtypes = [C.c_void_p]
+    L.fmd_audmon_reset.argtypes = [C.c_void_p, C.c_int]
+    L.fmd_audmon_reset_peaks.argtypes = [C.c_void_p, C.c_int]
+    L.fmd_audmon_set_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(AudmonParams)]
+    L.fmd_audmon_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(AudmonParams)]
+    L.fmd_audmon_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fmd_audmon_get_status.argtypes = [C.c_void_p, C.c_void_p]
+    L.fmd_audmon_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
+    L.fmd_audmon_last_error.restype = C.c_char_p
+    L.fmd_audmon_last_error.argtypes = [C.c_void_p]
     L.fmd_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.restype = C.c_char_p
     L.fmd_rdsdec_last_error.argtypes = [C.c_void_p]
@@ -1883,4 +1918,160 @@ class Squelch:
         """fmd_squelch_status_dev: the address of the device's own [C] records, valid until the next process call"""
         p = C.c_void_p()
         self._check(self.L.fmd_squelch_status_dev(self.q, C.byref(p)))
+        return p.value
+
+
+def _audmon_raise(L, rc):
+    raise FmdError(rc, L.fmd_audmon_last_error(None).decode() or L.fmd_status_string(rc).decode())
+
+
+def audmon_default_params() -> AudmonParams:
+    """fmd_audmon_default_params: silence at -60 dB, a rail lost 30 dB down, antiphase below a correlation of -0.5, mono with side 40 dB
+    under mid; 100, 100, 100, 50, 100 intervals to raise and 10 to clear; alarm_mask 15 (MONO is an indication, not an alarm)"""
+    p = AudmonParams()
+    load_library().fmd_audmon_default_params(C.byref(p))
+    return p
+
+
+def _audmon_record(record):
+    r = np.ascontiguousarray(record, AUDMON_STATUS_DTYPE).reshape(-1)
+    if r.size != 1:
+        raise ValueError("one status record at a time")
+    return r
+
+
+def _audmon_read(fn: str, record, fs: int, *args) -> float:
+    L, r, out = load_library(), _audmon_record(record), C.c_double(0.0)
+    rc = getattr(L, fn)(r.ctypes.data_as(C.c_void_p), int(fs), *[int(a) for a in args], C.byref(out))
+    if rc != FMD_OK:
+        _audmon_raise(L, rc)
+    return out.value
+
+
+def audmon_level_db(record, fs: int, rail: int = 2, window: int = 1) -> float:
+    """fmd_audmon_level_db of one AUDMON_STATUS_DTYPE record: the mean power of rail 0 (L), 1 (R) or 2 (both) over the newest `window`
+    (1 ... 30) intervals in dB of full scale 1.0, -inf for silence (FMD_ERR_STATE while fewer intervals are complete)"""
+    return _audmon_read("fmd_audmon_level_db", record, fs, rail, window)
+
+
+def audmon_balance_db(record, fs: int, window: int = 1) -> float:
+    """fmd_audmon_balance_db: L over R in dB (NaN for 0 / 0)"""
+    return _audmon_read("fmd_audmon_balance_db", record, fs, window)
+
+
+def audmon_correlation(record, fs: int, window: int = 1) -> float:
+    """fmd_audmon_correlation: sum L R / sqrt(sum L^2 sum R^2), -1 ... 1 (NaN for 0 / 0)"""
+    return _audmon_read("fmd_audmon_correlation", record, fs, window)
+
+
+def audmon_side_mid_db(record, fs: int, window: int = 1) -> float:
+    """fmd_audmon_side_mid_db: sum (L - R)^2 over sum (L + R)^2 in dB, -inf for R == L (NaN for 0 / 0)"""
+    return _audmon_read("fmd_audmon_side_mid_db", record, fs, window)
+
+
+class AudioMonitor:
+    """Audio fault monitor of C stations' audio on the GPU (fmd_audmon_*): per station and 100 ms interval the sums of L^2, R^2 and L R
+    and the rail peaks, five hysteresis detectors (AUDMON_SILENCE, _LEFT_LOST, _RIGHT_LOST, _ANTIPHASE, _MONO), and two [C] uint8 tensors:
+    the flags and the ok bytes, which AudioMixer.process(active=...) and LoudnessMeter.process take as they are.  Feed it the same
+    [C, n, 2] float32 CUDA tensors as AudioResampler, AudioMixer and LoudnessMeter (BatchDemod.audio_tensor() at 32 kHz, or a resampler's
+    output at fs); it changes nothing in them.  status() returns AUDMON_STATUS_DTYPE records; the audmon_* functions turn them into dB."""
+
+    def __init__(self, n_channels: int, fs: int, max_input_frames: int = 1 << 16, device: int = -1):
+        self.L = load_library()
+        cfg = AudmonConfig(int(n_channels), int(fs), int(max_input_frames), device)
+        self.a = C.c_void_p()
+        rc = self.L.fmd_audmon_create(C.byref(cfg), C.byref(self.a))
+        if rc != FMD_OK:
+            self.a = None
+            _audmon_raise(self.L, rc)
+        self.n_channels, self.fs = int(n_channels), int(fs)
+
+    def close(self):
+        if getattr(self, "a", None):
+            self.L.fmd_audmon_destroy(self.a)
+            self.a = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int):
+        if rc < 0:
+            raise FmdError(rc, (self.L.fmd_audmon_last_error(self.a) or b"").decode() or self.L.fmd_status_string(rc).decode())
+        return rc
+
+    def process(self, x, n: int | None = None, active=None, flags=None, ok=None, stream=None):
+        """takes the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
+        uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole and keeps its two bytes); flags, ok: the [C] uint8 CUDA
+        tensors to write, None = a new one, False = not written.  Returns (flags, ok), None for one not written.  Asynchronous on
+        `stream` (default: torch's current)."""
+        import torch
+        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
+                and x.stride(2) == 1 and x.stride(1) == 2):
+            raise ValueError("x must be a CUDA float32 tensor [C, n, 2] with contiguous frames")
+        n = int(x.shape[1]) if n is None else int(n)
+        if active is not None:
+            if active.dtype == torch.bool:
+                active = active.view(torch.uint8)
+            if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (self.n_channels,) and active.is_contiguous()):
+                raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
+        if stream is None:
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+        elif hasattr(stream, "cuda_stream"):
+            stream = stream.cuda_stream
+        outs = []
+        for name, t in (("flags", flags), ("ok", ok)):
+            if t is None:
+                # zeroed on the stream the call then writes it on (0 is the default stream, on which torch works unless told otherwise)
+                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=x.device) if stream else torch.cuda.default_stream(x.device)):
+                    t = torch.zeros(self.n_channels, dtype=torch.uint8, device=x.device)
+            elif t is False:
+                t = None
+            elif not (t.is_cuda and t.dtype == torch.uint8 and t.shape == (self.n_channels,) and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous [C] uint8 CUDA tensor")
+            outs.append(t)
+        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
+        self._check(self.L.fmd_audmon_process_f32_dev(self.a, C.c_void_p(x.data_ptr()), in_stride, n,
+                                                      None if active is None else C.c_void_p(active.data_ptr()),
+                                                      None if outs[0] is None else C.c_void_p(outs[0].data_ptr()),
+                                                      None if outs[1] is None else C.c_void_p(outs[1].data_ptr()), C.c_void_p(stream)))
+        return outs[0], outs[1]
+
+    def set_params(self, channel: int = -1, **fields):
+        """fmd_audmon_set_params: the named fields of AudmonParams for station `channel` (-1 = every station, each keeping its other
+        fields); raise_intervals and clear_intervals take five values or one for all five.  Ordered behind the monitor's earlier work,
+        they apply from the next interval that ends"""
+        for c in (range(self.n_channels) if channel < 0 else (int(channel),)):
+            p = self.params(c)
+            for k, v in fields.items():
+                if k not in dict(AudmonParams._fields_):
+                    raise TypeError(f"AudmonParams has no field {k}")
+                if k in ("raise_intervals", "clear_intervals"):
+                    v = (C.c_int * 5)(*([int(v)] * 5 if np.isscalar(v) else [int(a) for a in v]))
+                setattr(p, k, v)
+            self._check(self.L.fmd_audmon_set_params(self.a, c, C.byref(p)))
+
+    def params(self, channel: int) -> AudmonParams:
+        p = AudmonParams()
+        self._check(self.L.fmd_audmon_get_params(self.a, int(channel), C.byref(p)))
+        return p
+
+    def reset(self, channel: int = -1):
+        self._check(self.L.fmd_audmon_reset(self.a, int(channel)))
+
+    def reset_peaks(self, channel: int = -1):
+        self._check(self.L.fmd_audmon_reset_peaks(self.a, int(channel)))
+
+    def status(self) -> np.ndarray:
+        """[C] AUDMON_STATUS_DTYPE records; waits for the monitor's work"""
+        out = np.zeros(self.n_channels, AUDMON_STATUS_DTYPE)
+        self._check(self.L.fmd_audmon_get_status(self.a, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def status_dev_ptr(self) -> int:
+        """fmd_audmon_status_dev: the address of the device's own [C] records, valid until the next process call"""
+        p = C.c_void_p()
+        self._check(self.L.fmd_audmon_status_dev(self.a, C.byref(p)))
         return p.value

@@ -1,0 +1,375 @@
+// Audio fault monitor, device side (include/fmdemod.h, "Audio fault monitor").
+//
+// NOT in the reference.  Per station and per 100 ms interval the sums LL = sum L^2, RR = sum R^2, LR = sum L R and the two rail peaks of
+// the station audio [C][in_stride][2] f32 that the resampler, the mixer and the loudness meter read, read in place; at an interval's end
+// the five hysteresis detectors (silence, left lost, right lost, antiphase, mono), and at a call's end the [C] flags and ok bytes.
+//
+// One kernel per call, k_audmon.  Interleaved L, R f32 has the byte layout of the carrier squelch's cf32, and k_squelch's geometry
+// carries over: one wavefront per station over rows of 256 consecutive frames that start at a multiple of 256 of r, r the frame's place
+// in its interval; lane l loads frames 4 l ... 4 l + 3 with two 16-byte non-temporal loads, four rows in registers ahead of the row it
+// works on.  With NP = 64 and j = (r >> 2) & 63 lane l owns exactly partial l of each of the three sums and adds its four terms of a row
+// in ascending r.  A frame outside the segment at hand is not loaded and reads as (+0, +0), which changes no partial (fma(+0, +0, s) = s:
+// a partial is never -0) and no peak.  An interval's end is wave-uniform: the partials fold by cross-lane moves in the contract's halving
+// order, and lane 0 alone writes the ring, runs the detectors on the station's record and stores, with ordinary stores.  The open
+// interval's 1.5 KB of partials are read at the call's start and written at its end.  No atomics, no LDS, no scratch.
+//
+// Denormals: fp64 and fp32 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstddef>
+#include <cstdint>
+#include <cstdio>
+#include <string>
+#include <vector>
+
+#include "fmd_audmon_design.h"
+#include "fmdemod.h"
+
+using fmd::AudmonGate;
+using fmd::kAudmonDetectors;
+using fmd::kAudmonPartials;
+using fmd::kAudmonRing;
+
+namespace {
+
+constexpr int kT = 64;               // threads per workgroup: one wavefront, one station
+constexpr int kQ = 4;                // frames per lane and row
+constexpr int kRow = kT * kQ;        // frames per row
+constexpr int kPf = 4;               // rows loaded ahead
+constexpr int kPartD = 3 * kAudmonPartials;    // doubles per station: the open interval's ll, rr and lr partials
+static_assert(kAudmonPartials == kT && kAudmonRing == 30 && kAudmonDetectors == 5, "k_audmon's lane layout");
+
+static_assert(sizeof(fmd_audmon_status) == 840 && offsetof(fmd_audmon_status, intervals) == 8 && offsetof(fmd_audmon_status, intervals_flagged) == 16 &&
+              offsetof(fmd_audmon_status, ring_ll) == 56 && offsetof(fmd_audmon_status, ring_rr) == 296 && offsetof(fmd_audmon_status, ring_lr) == 536 &&
+              offsetof(fmd_audmon_status, last_peak) == 776 && offsetof(fmd_audmon_status, hold_peak) == 784 && offsetof(fmd_audmon_status, run) == 792 &&
+              offsetof(fmd_audmon_status, transitions) == 812 && offsetof(fmd_audmon_status, nonfinite) == 832 && offsetof(fmd_audmon_status, flags) == 836 &&
+              offsetof(fmd_audmon_status, ok) == 837 && offsetof(fmd_audmon_status, reserved) == 838, "fmd_audmon_status layout");
+static_assert(sizeof(AudmonGate) == 80 && sizeof(fmd_audmon_params) == 80, "AudmonGate and fmd_audmon_params layout");
+
+// A lane's four frames of a row, loaded at once.  The station's rows are aligned to a frame only (8 bytes): the types carry that
+// alignment, and the device's global loads take any.
+typedef float am_f4 __attribute__((ext_vector_type(4), aligned(8)));
+typedef float am_f2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ void am_load4(const float2* p, float2 (&z)[kQ]) {
+    const am_f4 a = __builtin_nontemporal_load(reinterpret_cast<const am_f4*>(p));
+    const am_f4 b = __builtin_nontemporal_load(reinterpret_cast<const am_f4*>(p + 2));
+    z[0] = make_float2(a.x, a.y); z[1] = make_float2(a.z, a.w); z[2] = make_float2(b.x, b.y); z[3] = make_float2(b.z, b.w);
+}
+__device__ __forceinline__ float2 am_load1(const float2* p) {
+    const am_f2 v = __builtin_nontemporal_load(reinterpret_cast<const am_f2*>(p));
+    return make_float2(v.x, v.y);
+}
+
+// One detector's update on the station's record (lane 0, at an interval's end)
+__device__ __forceinline__ unsigned am_detect(fmd_audmon_status* st, int k, unsigned flags, bool bad, int raise, int clear) {
+    const unsigned bit = 1u << k;
+    unsigned run = st->run[k];
+    if (!(flags & bit)) {
+        run = bad ? run + 1 : 0;
+        if (run >= (unsigned)raise) { flags |= bit; run = 0; st->transitions[k]++; }
+    } else {
+        run = bad ? 0 : run + 1;
+        if (run >= (unsigned)clear) { flags &= ~bit; run = 0; st->transitions[k]++; }
+    }
+    st->run[k] = run;
+    return flags;
+}
+
+// in [C][in_stride] frames (L, R); gate [C]; status [C]; part [C][3][64]; carry [C][2]; out_flags, out_ok [C] or null
+__global__ __launch_bounds__(kT) void k_audmon(const float2* __restrict__ in, long long in_stride, long long n, const uint8_t* __restrict__ active, int M,
+                                               const AudmonGate* __restrict__ gate, fmd_audmon_status* __restrict__ status, double* __restrict__ part,
+                                               float* __restrict__ carry, uint8_t* __restrict__ out_flags, uint8_t* __restrict__ out_ok) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (active && active[c] == 0) return;                                    // (uniform over the wavefront)
+    fmd_audmon_status* st = status + c;
+    const AudmonGate gt = gate[c];                                           // (uniform: read once)
+    unsigned flags = st->flags;
+    if (n == 0) {                                                            // nothing of the station changes but its bytes, which are still written
+        if (lane == 0) {
+            const uint8_t ok = (uint8_t)((flags & gt.alarm_mask) == 0);
+            st->ok = ok;
+            if (out_flags) out_flags[c] = (uint8_t)flags;
+            if (out_ok) out_ok[c] = ok;
+        }
+        return;
+    }
+    const float2* base = in + (size_t)c * (size_t)in_stride;
+    double* pp = part + (size_t)c * kPartD + lane;
+
+    const unsigned long long frames0 = st->frames;
+    unsigned long long G = st->intervals;
+    int r0 = __builtin_amdgcn_readfirstlane((int)(frames0 - G * (unsigned long long)M));   // the first frame's place in its interval
+    float cpl = carry[2 * c], cpr = carry[2 * c + 1];                        // the open interval's peaks before this call
+    double ll = pp[0], rr = pp[kAudmonPartials], lr = pp[2 * kAudmonPartials];
+    float pl = 0.0f, pr = 0.0f;                                              // the lane's, over the segment at hand
+    float hl = 0.0f, hr = 0.0f;                                              // over the call
+
+    long long s0 = 0;                                                        // the segment's first frame: a segment ends with its interval or the call
+    while (s0 < n) {
+        const long long left = (long long)(M - r0);
+        const long long seg_end = n - s0 < left ? n : s0 + left;
+        const long long rb = s0 - (long long)(r0 & (kRow - 1));              // the first row's frame 0 (before s0: those frames read as zero)
+
+        float2 nxt[kPf][kQ];
+        auto fetch = [&](long long row) {
+#pragma unroll
+            for (int p = 0; p < kPf; p++) {
+                const long long i = row + (long long)p * kRow + kQ * lane;
+                if (i >= s0 && i + kQ <= seg_end) am_load4(base + i, nxt[p]);
+                else {
+#pragma unroll
+                    for (int k = 0; k < kQ; k++) {
+                        nxt[p][k] = make_float2(0.0f, 0.0f);
+                        if (i + k >= s0 && i + k < seg_end) nxt[p][k] = am_load1(base + i + k);
+                    }
+                }
+            }
+        };
+        auto process = [&](const float2 (&v)[kQ]) {
+#pragma unroll
+            for (int k = 0; k < kQ; k++) {
+                const double l = (double)v[k].x, r_ = (double)v[k].y;
+                ll = fma(l, l, ll);
+                rr = fma(r_, r_, rr);
+                lr = fma(l, r_, lr);
+                pl = fmaxf(pl, fabsf(v[k].x));
+                pr = fmaxf(pr, fabsf(v[k].y));
+            }
+        };
+
+        fetch(rb);
+        for (long long row = rb; row < seg_end; row += (long long)kPf * kRow) {
+            float2 cur[kPf][kQ];
+#pragma unroll
+            for (int p = 0; p < kPf; p++)
+#pragma unroll
+                for (int k = 0; k < kQ; k++) cur[p][k] = nxt[p][k];
+            if (row + (long long)kPf * kRow < seg_end) fetch(row + (long long)kPf * kRow);   // in flight while these rows run
+#pragma unroll
+            for (int p = 0; p < kPf; p++)
+                if (row + (long long)p * kRow < seg_end) process(cur[p]);
+        }
+
+        // the segment's peaks: no operand is ever a NaN, so the order of a maximum does not matter
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) { pl = fmaxf(pl, __shfl_xor(pl, d)); pr = fmaxf(pr, __shfl_xor(pr, d)); }
+        cpl = fmaxf(cpl, pl); cpr = fmaxf(cpr, pr);
+        hl = fmaxf(hl, pl); hr = fmaxf(hr, pr);
+        pl = 0.0f; pr = 0.0f;
+        r0 += (int)(seg_end - s0);
+        if (r0 == M) {                                                       // the interval is complete (wave-uniform)
+#pragma unroll
+            for (int w = kT / 2; w >= 1; w >>= 1) {                          // p_j += p_{j+w} for j < w, w = 32 ... 1: partial j + w sits w lanes up
+                ll += __shfl_down(ll, w); rr += __shfl_down(rr, w); lr += __shfl_down(lr, w);
+            }
+            if (lane == 0) {
+                const double LL = ll, RR = rr, LR = lr;
+                const int k = (int)(G % (unsigned long long)kAudmonRing);
+                st->ring_ll[k] = LL; st->ring_rr[k] = RR; st->ring_lr[k] = LR;
+                st->last_peak[0] = cpl; st->last_peak[1] = cpr;
+                const double big = 1.7976931348623157e308;                   // neither inf nor NaN
+                const bool finite = fabs(LL) <= big && fabs(RR) <= big && fabs(LR) <= big;
+                if (!finite) st->nonfinite++;
+                const double E = LL + RR;
+                const bool silent = !(finite && E > gt.min_e);
+                flags = am_detect(st, 0, flags, silent, gt.raise_intervals[0], gt.clear_intervals[0]);
+                if (!silent) {                                               // (silent: detectors 1 ... 4 hold)
+                    const double c_loss = gt.c_loss;
+                    const double S = fma(-2.0, LR, E), Md = fma(2.0, LR, E);
+                    flags = am_detect(st, 1, flags, LL < c_loss * RR, gt.raise_intervals[1], gt.clear_intervals[1]);
+                    flags = am_detect(st, 2, flags, RR < c_loss * LL, gt.raise_intervals[2], gt.clear_intervals[2]);
+                    flags = am_detect(st, 3, flags, LR < 0.0 && LR * LR > gt.c_anti * (LL * RR), gt.raise_intervals[3], gt.clear_intervals[3]);
+                    flags = am_detect(st, 4, flags, S < gt.c_mono * Md, gt.raise_intervals[4], gt.clear_intervals[4]);
+                }
+#pragma unroll
+                for (int d = 0; d < kAudmonDetectors; d++)
+                    if (flags & (1u << d)) st->intervals_flagged[d]++;
+            }
+            G++;
+            ll = 0.0; rr = 0.0; lr = 0.0;
+            cpl = 0.0f; cpr = 0.0f;
+            r0 = 0;
+        }
+        s0 = seg_end;
+    }
+
+    // what the next call needs: the open interval's partials and peaks, and the record
+    pp[0] = ll; pp[kAudmonPartials] = rr; pp[2 * kAudmonPartials] = lr;
+    if (lane == 0) {
+        carry[2 * c] = cpl; carry[2 * c + 1] = cpr;
+        st->hold_peak[0] = fmaxf(st->hold_peak[0], hl);
+        st->hold_peak[1] = fmaxf(st->hold_peak[1], hr);
+        st->frames = frames0 + (unsigned long long)n;
+        st->intervals = G;
+        const uint8_t ok = (uint8_t)((flags & gt.alarm_mask) == 0);
+        st->flags = (unsigned char)flags;
+        st->ok = ok;
+        if (out_flags) out_flags[c] = (uint8_t)flags;
+        if (out_ok) out_ok[c] = ok;
+    }
+}
+
+// stations c0 ... as after create (everything 0, every flag clear, ok = 1), or with `peaks` their hold_peak alone
+__global__ __launch_bounds__(kT) void k_audmon_reset(int c0, int peaks, fmd_audmon_status* __restrict__ status, double* __restrict__ part, float* __restrict__ carry) {
+    const int c = c0 + blockIdx.x, t = threadIdx.x;
+    fmd_audmon_status* st = status + c;
+    if (peaks) {
+        if (t == 0) { st->hold_peak[0] = 0.0f; st->hold_peak[1] = 0.0f; }
+        return;
+    }
+    unsigned* w = reinterpret_cast<unsigned*>(st);
+    for (int i = t; i < (int)(sizeof(fmd_audmon_status) / 4); i += kT) w[i] = 0u;
+    for (int i = t; i < kPartD; i += kT) part[(size_t)c * kPartD + i] = 0.0;
+    __syncthreads();
+    if (t == 0) { carry[2 * c] = 0.0f; carry[2 * c + 1] = 0.0f; st->ok = 1; }
+}
+
+// the parameters of stations c0 ...
+__global__ __launch_bounds__(kT) void k_audmon_set(int c0, int cn, AudmonGate g, AudmonGate* __restrict__ gate, fmd_audmon_status* __restrict__ status) {
+    const int i = blockIdx.x * kT + threadIdx.x;
+    if (i >= cn) return;
+    gate[c0 + i] = g;
+    status[c0 + i].ok = (unsigned char)((status[c0 + i].flags & g.alarm_mask) == 0);
+}
+
+}  // namespace
+
+struct fmd_audmon_s {
+    int device = 0, C = 0, fs = 0, M = 0;
+    long long max_in = 0;
+    std::vector<fmd_audmon_params> params;   // [C], as set
+    fmd_audmon_status* d_status = nullptr;   // [C]
+    AudmonGate* d_gate = nullptr;            // [C]
+    double* d_part = nullptr;                // [C][3][64]
+    float* d_carry = nullptr;                // [C][2]
+    hipEvent_t done = nullptr;               // end of the previous call's work
+    bool have_done = false;
+    std::string err;
+};
+
+static int am_fail(fmd_audmon a, int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
+    if (a) a->err = buf; else fmd::audmon_global_error() = buf;
+    return code;
+}
+
+static bool am_quiesce(fmd_audmon a) {
+    return hipSetDevice(a->device) == hipSuccess && (!a->have_done || hipEventSynchronize(a->done) == hipSuccess);
+}
+
+static int am_reset(fmd_audmon a, int channel, int peaks) {
+    if (!a) return FMD_ERR_ARG;
+    if (channel < -1 || channel >= a->C) return am_fail(a, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, a->C);
+    if (!am_quiesce(a)) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
+    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? a->C : 1;
+    hipLaunchKernelGGL(k_audmon_reset, dim3((unsigned)cn), dim3(kT), 0, nullptr, c0, peaks, a->d_status, a->d_part, a->d_carry);
+    if (hipGetLastError() != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "k_audmon_reset launch failed");
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    return FMD_OK;
+}
+
+extern "C" {
+
+int fmd_audmon_create(const fmd_audmon_config* cfg, fmd_audmon* out) {
+    if (!cfg || !out) return am_fail(nullptr, FMD_ERR_ARG, "null configuration or handle");
+    if (cfg->n_channels <= 0 || cfg->max_input_frames <= 0 || cfg->max_input_frames > (1LL << 30))
+        return am_fail(nullptr, FMD_ERR_ARG, "n_channels %d is not positive or max_input_frames %lld outside (0, 2^30]", cfg->n_channels, cfg->max_input_frames);
+    const int M = fmd::audmon_interval(cfg->fs);
+    if (M == 0) return am_fail(nullptr, FMD_ERR_ARG, "fs %d is not a multiple of 10 in 8000 ... 192000", cfg->fs);
+    if (fmd_device_count() <= 0) return am_fail(nullptr, FMD_ERR_NO_DEVICE, "no gfx950 device");
+    int dev = cfg->device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return am_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
+    fmd_audmon a = new fmd_audmon_s();
+    a->device = dev; a->C = cfg->n_channels; a->fs = cfg->fs; a->M = M; a->max_in = cfg->max_input_frames;
+    fmd_audmon_params p{};
+    fmd_audmon_default_params(&p);
+    a->params.assign((size_t)a->C, p);
+    const size_t C = (size_t)a->C;
+    bool ok = hipSetDevice(dev) == hipSuccess;
+    ok = ok && hipMalloc(&a->d_status, sizeof(fmd_audmon_status) * C) == hipSuccess;
+    ok = ok && hipMalloc(&a->d_gate, sizeof(AudmonGate) * C) == hipSuccess;
+    ok = ok && hipMalloc(&a->d_part, sizeof(double) * kPartD * C) == hipSuccess;
+    ok = ok && hipMalloc(&a->d_carry, sizeof(float) * 2 * C) == hipSuccess;
+    ok = ok && hipEventCreateWithFlags(&a->done, hipEventDisableTiming) == hipSuccess;
+    // (the reset first: set_params reads the record's flags)
+    if (!ok || fmd_audmon_reset(a, -1) != FMD_OK || fmd_audmon_set_params(a, -1, &p) != FMD_OK) {
+        fmd_audmon_destroy(a);
+        return am_fail(nullptr, FMD_ERR_DEVICE, "device allocation failed");
+    }
+    *out = a;
+    return FMD_OK;
+}
+
+int fmd_audmon_destroy(fmd_audmon a) {
+    if (!a) return FMD_ERR_ARG;
+    (void)am_quiesce(a);
+    for (void* p : {(void*)a->d_status, (void*)a->d_gate, (void*)a->d_part, (void*)a->d_carry})
+        if (p) (void)hipFree(p);
+    if (a->done) (void)hipEventDestroy(a->done);
+    delete a;
+    return FMD_OK;
+}
+
+int fmd_audmon_reset(fmd_audmon a, int channel) { return am_reset(a, channel, 0); }
+
+int fmd_audmon_reset_peaks(fmd_audmon a, int channel) { return am_reset(a, channel, 1); }
+
+int fmd_audmon_set_params(fmd_audmon a, int channel, const fmd_audmon_params* p) {
+    if (!a) return FMD_ERR_ARG;
+    if (channel < -1 || channel >= a->C) return am_fail(a, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, a->C);
+    AudmonGate g;
+    if (fmd::audmon_gate(p, a->M, &g, &a->err) != FMD_OK) return FMD_ERR_ARG;
+    if (!am_quiesce(a)) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
+    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? a->C : 1;
+    hipLaunchKernelGGL(k_audmon_set, dim3((unsigned)((cn + kT - 1) / kT)), dim3(kT), 0, nullptr, c0, cn, g, a->d_gate, a->d_status);
+    if (hipGetLastError() != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "k_audmon_set launch failed");
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    for (int c = c0; c < c0 + cn; c++) a->params[(size_t)c] = *p;
+    return FMD_OK;
+}
+
+int fmd_audmon_get_params(fmd_audmon a, int channel, fmd_audmon_params* p) {
+    if (!a || !p) return am_fail(a, FMD_ERR_ARG, "null monitor or output");
+    if (channel < 0 || channel >= a->C) return am_fail(a, FMD_ERR_ARG, "channel %d outside [0, %d)", channel, a->C);
+    *p = a->params[(size_t)channel];
+    return FMD_OK;
+}
+
+int fmd_audmon_process_f32_dev(fmd_audmon a, const float* d_in, long long in_stride, long long n, const uint8_t* d_active, uint8_t* d_flags, uint8_t* d_ok,
+                               void* stream) {
+    if (!a) return FMD_ERR_ARG;
+    if (!d_in || reinterpret_cast<uintptr_t>(d_in) % 8 != 0) return am_fail(a, FMD_ERR_ARG, "null input, or input not aligned to 8 bytes");
+    if (n < 0 || n > in_stride || n > a->max_in)
+        return am_fail(a, FMD_ERR_ARG, "n %lld outside [0, in_stride %lld] or above max_input_frames %lld", n, in_stride, a->max_in);
+    if (n == 0 && !d_flags && !d_ok) return FMD_OK;                          // nothing of any station changes and there is no byte to write
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (hipSetDevice(a->device) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "hipSetDevice failed");
+    // every station's state carries over from call to call: a caller that switches streams is ordered behind the previous call
+    if (a->have_done && hipStreamWaitEvent(s, a->done, 0) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "stream wait failed");
+    hipLaunchKernelGGL(k_audmon, dim3((unsigned)a->C), dim3(kT), 0, s, reinterpret_cast<const float2*>(d_in), in_stride, n, d_active, a->M, a->d_gate,
+                       a->d_status, a->d_part, a->d_carry, d_flags, d_ok);
+    if (hipGetLastError() != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "k_audmon launch failed");
+    if (hipEventRecord(a->done, s) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "event record failed");
+    a->have_done = true;
+    return FMD_OK;
+}
+
+int fmd_audmon_get_status(fmd_audmon a, fmd_audmon_status* out) {
+    if (!a || !out) return am_fail(a, FMD_ERR_ARG, "null monitor or output");
+    if (!am_quiesce(a)) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
+    if (hipMemcpy(out, a->d_status, sizeof(fmd_audmon_status) * (size_t)a->C, hipMemcpyDeviceToHost) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "copy failed");
+    return FMD_OK;
+}
+
+int fmd_audmon_status_dev(fmd_audmon a, const fmd_audmon_status** d_status) {
+    if (!a || !d_status) return am_fail(a, FMD_ERR_ARG, "null monitor or output");
+    *d_status = a->d_status;
+    return FMD_OK;
+}
+
+const char* fmd_audmon_last_error(fmd_audmon a) { return a ? a->err.c_str() : fmd::audmon_global_error().c_str(); }
+
+}  // extern "C"

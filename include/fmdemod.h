@@ -1051,6 +1051,135 @@ int fmd_squelch_get_status(fmd_squelch q, fmd_squelch_status* out);
 int fmd_squelch_status_dev(fmd_squelch q, const fmd_squelch_status** d_status);
 const char* fmd_squelch_last_error(fmd_squelch q);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Audio fault monitor (NOT part of the reference): the faults of the demodulated programme that a broadcast monitor alarms on first --
+ * dead air (the carrier is up, the programme is silent), a lost rail (one of L / R is gone), antiphase (L and R cancel in every mono
+ * receiver and in a bus that sums stations) and a mono programme on a station that should be stereo.  It reads the device array
+ * [C][in_stride][2] f32 (interleaved L, R) that the resampler, the mixer and the loudness meter read -- fmd_audio_dev's view or a
+ * resampler's output -- changes nothing in it, keeps per station and per 100 ms interval the sums LL = sum L^2, RR = sum R^2,
+ * LR = sum L R and the two rail peaks, runs five hysteresis detectors on the device with comparisons only, and writes a [C] uint8 flags
+ * byte and a [C] uint8 ok byte per station.  The ok bytes are what the mixer takes as d_active: a dead or antiphase station leaves a
+ * bus with no host round trip.  (The loudness meter does not answer these questions: its energies are K-weighted, summed over both
+ * rails, and it keeps no cross term.)
+ * Arithmetic, restated in C by tests/cpp/audmon_ref.c; NP = 64 partials, RING = 30 intervals (three seconds), five detectors:
+ *   design      host, double, host libm; fs a multiple of 10 in 8000 ... 192000 (the loudness meter's range):
+ *                 M = fs / 10 (frames of a 100 ms interval)
+ *                 min_e  = pow(10, silence_db / 10) * (2.0 * (double)M), and +0 for silence_db = -inf
+ *                 c_loss = pow(10, -loss_db / 10);  c_anti = antiphase_corr * antiphase_corr;  c_mono = pow(10, -mono_db / 10)
+ *   per frame   n counted absolutely in 64 bits since the station's reset; interval g = n / M, r = n - g M.
+ *                 l = (double)L, r_ = (double)R                                  (every product below is exact in double)
+ *               Partial j = (r >> 2) & 63 takes its terms in ascending r, from +0 at the interval's start:
+ *                 ll_j = fma(l, l, ll_j);  rr_j = fma(r_, r_, rr_j);  lr_j = fma(l, r_, lr_j)
+ *                 pkL = fmaxf(pkL, fabsf(L)), pkR = fmaxf(pkR, fabsf(R)) from +0 at the interval's start (a NaN is dropped); the same
+ *                 updates go into hold_peak[0], hold_peak[1] (+0 at create, reset and reset_peaks).
+ *               fp32 and fp64 denormals are kept.  An open interval carries its two peaks and its 3 x 64 partials (1.5 KB per station)
+ *               to the next call.
+ *   interval end  per sum the halving tree p_j += p_{j+w} for j < w, w = 32, 16, ... 1;  S = p_0: LL, RR, LR.
+ *                 ring_ll[g % 30] = LL, ring_rr[g % 30] = RR, ring_lr[g % 30] = LR, last_peak = {pkL, pkR}, intervals++
+ *                 finite = isfinite(LL) && isfinite(RR) && isfinite(LR);  not finite -> nonfinite++
+ *                 E = LL + RR
+ *                 bad[0] = !(finite && E > min_e)        strict: digital silence is silent at any threshold, also at -inf, and an
+ *                                                        interval that is not finite counts as no usable programme
+ *                 only where bad[0] is false:
+ *                   bad[1] = LL < c_loss * RR
+ *                   bad[2] = RR < c_loss * LL
+ *                   bad[3] = LR < 0 && LR * LR > c_anti * (LL * RR)
+ *                   S = fma(-2.0, LR, E);  Md = fma(2.0, LR, E);  bad[4] = S < c_mono * Md        (S = sum (L - R)^2, Md = sum (L + R)^2)
+ *                 where bad[0] is true, detectors 1 ... 4 HOLD: their flag and their run do not change (silence says nothing about
+ *                 phase or balance).
+ *   detector k  (bit k of flags; k = 0 always runs, k = 1 ... 4 unless held)
+ *               flag clear: run = bad ? run + 1 : 0;  run >= raise_intervals[k] -> the flag is set, run = 0, transitions[k]++
+ *               flag set:   run = bad ? 0 : run + 1;  run >= clear_intervals[k] -> the flag is cleared, run = 0, transitions[k]++
+ *               intervals_flagged[k]++ where the flag is set after the interval, held or not.
+ *   bytes       flags = the five bits;  ok = (flags & alarm_mask) == 0, with the station's alarm_mask as it is when the bytes are written
+ *               (a process call, set_params, reset).  No atomics; ordinary stores.  Nothing depends, bit for bit, on how the frames are
+ *               split into calls, on streams, on the batch or on the station's row.
+ *   read-out    host, double, pure functions over one record; fs as in the design and 1 <= window <= 30 (else FMD_ERR_ARG);
+ *               FMD_ERR_STATE while intervals < window.  Over the newest `window` intervals, oldest first, from +0:
+ *                 ll += ring_ll, rr += ring_rr, lr += ring_lr;  N = (double)M * (double)window
+ *                 level_db(rail): 0 (L) 10 * log10(ll / N);  1 (R) 10 * log10(rr / N);  2 (both) 10 * log10((ll + rr) / (2.0 * N))
+ *                 balance_db     10 * log10(ll / rr)
+ *                 correlation    lr / sqrt(ll * rr)
+ *                 side_mid_db    10 * log10(fma(-2.0, lr, ll + rr) / fma(2.0, lr, ll + rr))
+ *               Nothing is special-cased: where a division is 0 / 0 (silence: balance, correlation and side / mid) or a ring entry is
+ *               not finite, the IEEE result is returned as it comes -- a NaN, or -inf for the level of silence and for the side / mid
+ *               ratio of R == L.
+ * ------------------------------------------------------------------------------------------------------------------ */
+#define FMD_AUDMON_SILENCE    1u    /* detector 0: the interval's energy is not above the silence threshold */
+#define FMD_AUDMON_LEFT_LOST  2u    /* detector 1: L is loss_db or more below R */
+#define FMD_AUDMON_RIGHT_LOST 4u    /* detector 2: R is loss_db or more below L */
+#define FMD_AUDMON_ANTIPHASE  8u    /* detector 3: the correlation of L and R is below -antiphase_corr */
+#define FMD_AUDMON_MONO       16u   /* detector 4: the side signal is mono_db or more below the mid signal */
+typedef struct fmd_audmon_s* fmd_audmon;
+typedef struct {
+    int       n_channels;         /* C: station rows of the input */
+    int       fs;                 /* the audio's rate: a multiple of 10 in 8000 ... 192000 */
+    long long max_input_frames;   /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_audmon_config;
+/* defaults: -60.0, 30.0, 0.5, 40.0, {100, 100, 100, 50, 100}, {10, 10, 10, 10, 10}, 15 (MONO is an indication, not an alarm).
+ * Valid: silence_db = -inf or finite; loss_db and mono_db in (0, 120]; antiphase_corr in (0, 1); every raise_intervals and
+ * clear_intervals in 1 ... 36000 (an hour); alarm_mask with no bit above bit 4.  80 bytes */
+typedef struct {
+    double   silence_db;          /* an interval whose mean power over both rails, 10 log10(E / 2M), is not above this is silent */
+    double   loss_db;             /* a rail this far below the other is lost */
+    double   antiphase_corr;      /* L and R are in antiphase where their correlation is below minus this */
+    double   mono_db;             /* the programme is mono where side is this far below mid */
+    int      raise_intervals[5];  /* bad intervals in a row that set detector k's flag */
+    int      clear_intervals[5];  /* good intervals in a row that clear it */
+    unsigned alarm_mask;          /* the FMD_AUDMON_* flags that take the station's ok byte to 0 */
+} fmd_audmon_params;
+/* one per station, 840 bytes: frames at byte 0, intervals 8, intervals_flagged 16, ring_ll 56, ring_rr 296, ring_lr 536, last_peak 776,
+ * hold_peak 784, run 792, transitions 812, nonfinite 832, flags 836, ok 837, reserved 838 */
+typedef struct {
+    unsigned long long frames;               /* frames seen since reset */
+    unsigned long long intervals;            /* completed 100 ms intervals */
+    unsigned long long intervals_flagged[5]; /* ... of them with detector k's flag set after the interval */
+    double   ring_ll[30], ring_rr[30], ring_lr[30]; /* interval g at [g % 30]: sum L^2, sum R^2, sum L R */
+    float    last_peak[2];                   /* max |L|, max |R| over the newest interval */
+    float    hold_peak[2];                   /* ... since reset or reset_peaks */
+    unsigned run[5];                         /* detector k's run of bad (flag clear) or good (flag set) intervals */
+    unsigned transitions[5];                 /* raises and clears of detector k since reset */
+    unsigned nonfinite;                      /* intervals with a non-finite LL, RR or LR */
+    unsigned char flags;                     /* FMD_AUDMON_* */
+    unsigned char ok;                        /* (flags & alarm_mask) == 0 */
+    unsigned char reserved[2];
+} fmd_audmon_status;
+
+/* host-only (no GPU needed) */
+void fmd_audmon_default_params(fmd_audmon_params* p);
+/* rail: 0 L, 1 R, 2 both */
+int fmd_audmon_level_db(const fmd_audmon_status* s, int fs, int rail, int window, double* db);
+int fmd_audmon_balance_db(const fmd_audmon_status* s, int fs, int window, double* db);
+int fmd_audmon_correlation(const fmd_audmon_status* s, int fs, int window, double* corr);
+int fmd_audmon_side_mid_db(const fmd_audmon_status* s, int fs, int window, double* db);
+
+int fmd_audmon_create(const fmd_audmon_config* cfg, fmd_audmon* out);
+int fmd_audmon_destroy(fmd_audmon a);
+/* everything of station `channel` (-1 = every station) as after create: counters, ring, peaks, the open interval, the detectors (every
+ * flag clear, ok = 1); its parameters are kept.  Waits for the monitor's earlier work */
+int fmd_audmon_reset(fmd_audmon a, int channel);
+/* hold_peak of station `channel` (-1 = every station) to +0; nothing else */
+int fmd_audmon_reset_peaks(fmd_audmon a, int channel);
+/* the parameters of station `channel` (-1 = every station): ordered behind the monitor's earlier work, they apply from the next interval
+ * that ends (alarm_mask: from the next bytes written, the record's ok at once).  FMD_ERR_ARG for values outside the ranges above, and
+ * nothing changes */
+int fmd_audmon_set_params(fmd_audmon a, int channel, const fmd_audmon_params* p);
+int fmd_audmon_get_params(fmd_audmon a, int channel, fmd_audmon_params* p);
+/* takes n frames of every station.  d_in [C][in_stride][2] f32 on the device, 8-byte aligned; d_active: [C] uint8 on the device,
+ * NULL = all: a station whose byte is 0 is skipped whole, and its two output bytes are left as they are.  d_flags, d_ok: [C] uint8 on
+ * the device, caller-owned, each may be NULL: behind its work on `stream` the call writes every other station's byte, also when n == 0
+ * and for a station whose detectors did not move.  n < 0, n > in_stride, n > max_input_frames or a misaligned d_in return FMD_ERR_ARG
+ * and change nothing.  Asynchronous on `stream`; consecutive calls may use different streams (the library orders them). */
+int fmd_audmon_process_f32_dev(fmd_audmon a, const float* d_in, long long in_stride, long long n, const uint8_t* d_active,
+                               uint8_t* d_flags, uint8_t* d_ok, void* stream);
+/* out [C]; synchronises with the monitor's work */
+int fmd_audmon_get_status(fmd_audmon a, fmd_audmon_status* out);
+/* the device's own [C] records, for a consumer on the device: ordered behind the monitor's work on the stream of its last process call,
+ * valid until the next process call */
+int fmd_audmon_status_dev(fmd_audmon a, const fmd_audmon_status** d_status);
+const char* fmd_audmon_last_error(fmd_audmon a);
+
 #ifdef __cplusplus
 }
 #endif
