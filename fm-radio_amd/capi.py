@@ -332,30 +332,24 @@ def load_library():
     L.fmd_chan_default_taps_per_phase.restype = C.c_int
     L.fmd_chan_default_taps_per_phase.argtypes = [C.c_double, C.c_double]
     L.fmd_chan_create.argtypes = [C.POINTER(ChanConfig), C.POINTER(C.c_void_p)]
-    L.fmd_chan_destroy.argtypes = [C.c_void_p]
     L.fmd_chan_reset.argtypes = [C.c_void_p]
     L.fmd_chan_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
     L.fmd_chan_get_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
     for fmt in ("cf32", "u8", "s8", "s16"):
         getattr(L, f"fmd_chan_process_{fmt}_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
-    L.fmd_chan_last_error.restype = C.c_char_p
-    L.fmd_chan_last_error.argtypes = [C.c_void_p]
     L.fmd_scan_default_nfft.restype = C.c_int
     L.fmd_scan_default_nfft.argtypes = [C.c_double]
     L.fmd_scan_default_params.restype = None
     L.fmd_scan_default_params.argtypes = [C.POINTER(ScanParams)]
     L.fmd_scan_detect.argtypes = [C.c_void_p, C.c_int, C.c_double, C.POINTER(ScanParams), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
     L.fmd_scan_create.argtypes = [C.POINTER(ScanConfig), C.POINTER(C.c_void_p)]
-    L.fmd_scan_destroy.argtypes = [C.c_void_p]
     L.fmd_scan_reset.argtypes = [C.c_void_p]
     for fmt in ("cf32", "u8", "s8", "s16"):
         getattr(L, f"fmd_scan_process_{fmt}_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.fmd_scan_get_psd.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_longlong)]
     L.fmd_scan_stations.argtypes = [C.c_void_p, C.POINTER(ScanParams), C.c_void_p, C.c_int, C.POINTER(C.c_int)]
-    L.fmd_scan_last_error.restype = C.c_char_p
-    L.fmd_scan_last_error.argtypes = [C.c_void_p]
     L.fmd_iqcorr_create.argtypes = [C.POINTER(IqcorrConfig), C.POINTER(C.c_void_p)]
-    for name in ("fmd_iqcorr_destroy", "fmd_iqcorr_reset", "fmd_iqcorr_reset_moments"):
+    for name in ("fmd_iqcorr_reset", "fmd_iqcorr_reset_moments"):
         getattr(L, name).argtypes = [C.c_void_p]
     for fmt in ("cf32", "u8", "s8", "s16"):
         getattr(L, f"fmd_iqcorr_process_{fmt}_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
@@ -364,27 +358,19 @@ def load_library():
     L.fmd_iqcorr_set_correction.argtypes = [C.c_void_p, C.POINTER(_IqCorrectionC)]
     L.fmd_iqcorr_get_correction.argtypes = [C.c_void_p, C.POINTER(_IqCorrectionC)]
     L.fmd_iqcorr_calibrate.argtypes = [C.c_void_p, C.POINTER(_IqCorrectionC)]
-    L.fmd_iqcorr_last_error.restype = C.c_char_p
-    L.fmd_iqcorr_last_error.argtypes = [C.c_void_p]
     L.fmd_resampler_design.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.fmd_resampler_create.argtypes = [C.POINTER(ResamplerConfig), C.POINTER(C.c_void_p)]
-    L.fmd_resampler_destroy.argtypes = [C.c_void_p]
     L.fmd_resampler_reset.argtypes = [C.c_void_p, C.c_int]
     L.fmd_resampler_set_input_rate.argtypes = [C.c_void_p, C.c_int]
     L.fmd_resampler_output_frames.argtypes = [C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]
     for name in ("fmd_resampler_process_f32_dev", "fmd_resampler_process_pcm16_dev", "fmd_resampler_process_f32_host"):
         getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong), C.c_void_p]
-    L.fmd_resampler_last_error.restype = C.c_char_p
-    L.fmd_resampler_last_error.argtypes = [C.c_void_p]
     L.fmd_mixer_create.argtypes = [C.POINTER(MixerConfig), C.POINTER(C.c_void_p)]
-    L.fmd_mixer_destroy.argtypes = [C.c_void_p]
     L.fmd_mixer_set_sources.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.fmd_mixer_set_gain.argtypes = [C.c_void_p, C.c_int, C.c_float]
     L.fmd_mixer_get_gain.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
     for name in ("fmd_mixer_process_f32_dev", "fmd_mixer_process_f32_host"):
         getattr(L, name).argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
-    L.fmd_mixer_last_error.restype = C.c_char_p
-    L.fmd_mixer_last_error.argtypes = [C.c_void_p]
     L.fmd_meter_design.argtypes = [C.c_int, C.POINTER(MeterDesign)]
     L.fmd_meter_lufs.restype = C.c_double
     L.fmd_meter_lufs.argtypes = [C.c_double]
@@ -392,13 +378,8 @@ def load_library():
     L.fmd_meter_momentary.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.fmd_meter_short_term.argtypes = [C.c_void_p, C.POINTER(C.c_double)]
     L.fmd_meter_create.argtypes = [C.POINTER(MeterConfig), C.POINTER(C.c_void_p)]
-    L.fmd_meter_destroy.argtypes = [C.c_void_p]
-    L.fmd_meter_reset.argtypes = [C.c_void_p, C.c_int]
-    L.fmd_meter_reset_peaks.argtypes = [C.c_void_p, C.c_int]
     L.fmd_meter_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p]
-    L.fmd_meter_get_status.argtypes = [C.c_void_p, C.c_void_p]
     L.fmd_meter_get_histogram.argtypes = [C.c_void_p, C.c_void_p]
-    L.fmd_meter_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.fmd_meter_create_ex.argtypes = [C.POINTER(MeterConfig), C.c_uint, C.POINTER(C.c_void_p)]
     L.fmd_meter_features.argtypes = [C.c_void_p, C.POINTER(C.c_uint)]
     L.fmd_meter_tp_design.argtypes = [C.c_int, C.POINTER(MeterTpDesign)]
@@ -408,8 +389,6 @@ def load_library():
     L.fmd_meter_r128_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.fmd_meter_get_range_histogram.argtypes = [C.c_void_p, C.c_void_p]
     L.fmd_meter_range.argtypes = [C.c_void_p, C.POINTER(MeterDesign), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]
-    L.fmd_meter_last_error.restype = C.c_char_p
-    L.fmd_meter_last_error.argtypes = [C.c_void_p]
     L.fmd_modmon_design.argtypes = [C.c_int, C.POINTER(ModmonDesign)]
     for fn in ("fmd_modmon_deviation_hz", "fmd_modmon_offset_hz", "fmd_modmon_pilot_hz"):
         getattr(L, fn).argtypes = [C.c_void_p, C.POINTER(ModmonDesign), C.POINTER(C.c_double)]
@@ -417,16 +396,9 @@ def load_library():
     L.fmd_modmon_exceedance.argtypes = [C.c_void_p, C.c_uint, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_ulonglong)]
     L.fmd_modmon_percentile.argtypes = [C.c_void_p, C.c_uint, C.c_double, C.POINTER(C.c_double)]
     L.fmd_modmon_create.argtypes = [C.POINTER(ModmonConfig), C.POINTER(C.c_void_p)]
-    L.fmd_modmon_destroy.argtypes = [C.c_void_p]
-    L.fmd_modmon_reset.argtypes = [C.c_void_p, C.c_int]
-    L.fmd_modmon_reset_peaks.argtypes = [C.c_void_p, C.c_int]
     L.fmd_modmon_process_cf32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p]
     L.fmd_modmon_process_u8_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p]
-    L.fmd_modmon_get_status.argtypes = [C.c_void_p, C.c_void_p]
     L.fmd_modmon_get_histogram.argtypes = [C.c_void_p, C.c_void_p]
-    L.fmd_modmon_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.fmd_modmon_last_error.restype = C.c_char_p
-    L.fmd_modmon_last_error.argtypes = [C.c_void_p]
     L.fmd_squelch_default_params.argtypes = [C.POINTER(SquelchParams)]
     L.fmd_squelch_default_params.restype = None
     L.fmd_squelch_threshold.argtypes = [C.c_double]
@@ -435,17 +407,10 @@ def load_library():
     L.fmd_squelch_cnr_db.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.fmd_squelch_powers.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.fmd_squelch_create.argtypes = [C.POINTER(SquelchConfig), C.POINTER(C.c_void_p)]
-    L.fmd_squelch_destroy.argtypes = [C.c_void_p]
-    L.fmd_squelch_reset.argtypes = [C.c_void_p, C.c_int]
-    L.fmd_squelch_reset_peaks.argtypes = [C.c_void_p, C.c_int]
     L.fmd_squelch_set_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SquelchParams)]
     L.fmd_squelch_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SquelchParams)]
     L.fmd_squelch_process_cf32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fmd_squelch_process_u8_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.fmd_squelch_get_status.argtypes = [C.c_void_p, C.c_void_p]
-    L.fmd_squelch_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.fmd_squelch_last_error.restype = C.c_char_p
-    L.fmd_squelch_last_error.argtypes = [C.c_void_p]
     L.fmd_audmon_default_params.argtypes = [C.POINTER(AudmonParams)]
     L.fmd_audmon_default_params.restype = None
     L.fmd_audmon_level_db.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
@@ -453,19 +418,20 @@ def load_library():
     L.fmd_audmon_correlation.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.fmd_audmon_side_mid_db.argtypes = [C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double)]
     L.fmd_audmon_create.argtypes = [C.POINTER(AudmonConfig), C.POINTER(C.c_void_p)]
-    L.fmd_audmon_destroy.argtypes = [C.c_void_p]
-    L.fmd_audmon_reset.argtypes = [C.c_void_p, C.c_int]
-    L.fmd_audmon_reset_peaks.argtypes = [C.c_void_p, C.c_int]
     L.fmd_audmon_set_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(AudmonParams)]
     L.fmd_audmon_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(AudmonParams)]
     L.fmd_audmon_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.fmd_audmon_get_status.argtypes = [C.c_void_p, C.c_void_p]
-    L.fmd_audmon_status_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
-    L.fmd_audmon_last_error.restype = C.c_char_p
-    L.fmd_audmon_last_error.argtypes = [C.c_void_p]
+    # what every side object declares alike
+    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "rdsdec"):
+        getattr(L, f"fmd_{pre}_destroy").argtypes = [C.c_void_p]
+        getattr(L, f"fmd_{pre}_last_error").restype = C.c_char_p
+        getattr(L, f"fmd_{pre}_last_error").argtypes = [C.c_void_p]
+    for pre in ("meter", "modmon", "squelch", "audmon"):
+        getattr(L, f"fmd_{pre}_reset").argtypes = [C.c_void_p, C.c_int]
+        getattr(L, f"fmd_{pre}_reset_peaks").argtypes = [C.c_void_p, C.c_int]
+        getattr(L, f"fmd_{pre}_get_status").argtypes = [C.c_void_p, C.c_void_p]
+        getattr(L, f"fmd_{pre}_status_dev").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.fmd_last_error.restype = C.c_char_p
-    L.fmd_rdsdec_last_error.restype = C.c_char_p
-    L.fmd_rdsdec_last_error.argtypes = [C.c_void_p]
     L.fmd_last_error.argtypes = [H]
     if L.fmd_output_lifetime_blocks() != FMD_OUTPUT_LIFETIME_BLOCKS:
         raise RuntimeError("libfmdemod.so and capi.py disagree on FMD_OUTPUT_LIFETIME_BLOCKS")
@@ -558,24 +524,98 @@ def _groups_lists(raw: np.ndarray, counts: np.ndarray) -> list:
     return [_groups_view(raw[c, : int(counts[c])]) for c in range(raw.shape[0])]
 
 
-class RDSDecoder:
-    """Standalone batched RDS decoding chain on the GPU (fmd_rdsdec_*): the reference's RDS_Decoding_Chain for C byte streams from
-    any source (a demodulator's RDS bytes, the scraper's _rds.bin files).  State carries over between process() calls."""
+def _stream_ptr(stream, device=None):
+    """a call's stream as a raw stream pointer: None is torch's current stream on `device`; a torch stream (anything with .cuda_stream) or
+    an int is taken as given"""
+    if stream is None:
+        import torch
+        return torch.cuda.current_stream(device).cuda_stream
+    return getattr(stream, "cuda_stream", stream)
 
-    def __init__(self, n_channels: int, device: int = -1):
+
+def _batch_input(x, n_channels: int, n, dtypes: tuple, noun: str):
+    """the per-station input of a side object, x: [C, >= n, 2] of one of `dtypes` (torch dtype names) on the device with contiguous `noun`
+    (frames or samples) -> (pointer, in_stride, n), n defaulting to all of x"""
+    import torch
+    if not (x.is_cuda and x.dtype in [getattr(torch, d) for d in dtypes] and x.dim() == 3 and x.shape[0] == n_channels and x.shape[2] == 2
+            and x.stride(2) == 1 and x.stride(1) == 2):
+        raise ValueError(f"x must be a CUDA {' or '.join(dtypes)} tensor [C, n, 2] with contiguous {noun}")
+    in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
+    return C.c_void_p(x.data_ptr()), in_stride, int(x.shape[1]) if n is None else int(n)
+
+
+def _active_ptr(active, n_channels: int):
+    """the `active` argument of a process call, None or a [C] uint8 / bool CUDA tensor -> the pointer the library takes (None: every station)"""
+    if active is None:
+        return None
+    import torch
+    if active.dtype == torch.bool:
+        active = active.view(torch.uint8)
+    if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (n_channels,) and active.is_contiguous()):
+        raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
+    return C.c_void_p(active.data_ptr())
+
+
+def _byte_out(t, name: str, n_channels: int, device, stream):
+    """a [C] uint8 output of a process call -> (tensor, pointer): the caller's tensor, None = a new one, False = not written (None, None)"""
+    import torch
+    if t is False:
+        return None, None
+    if t is None:
+        # zeroed on the stream the call then writes it on (0 is the default stream, on which torch works unless told otherwise)
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device) if stream else torch.cuda.default_stream(device)):
+            t = torch.zeros(n_channels, dtype=torch.uint8, device=device)
+    elif not (t.is_cuda and t.dtype == torch.uint8 and t.shape == (n_channels,) and t.is_contiguous()):
+        raise ValueError(f"{name} must be a contiguous [C] uint8 CUDA tensor")
+    return t, C.c_void_p(t.data_ptr())
+
+
+def _global_error(L, prefix: str, rc: int) -> FmdError:
+    """the FmdError of a call without a handle (a create, a host-only function): the object's global message, else the status string"""
+    return FmdError(rc, getattr(L, f"{prefix}_last_error")(None).decode() or L.fmd_status_string(rc).decode())
+
+
+def _record_read(prefix: str, fn: str, record, dtype, *args, outs: int = 1):
+    """prefix_fn(record, *args, &out ...) of one status record of `dtype` (host only): the double read out, or a tuple of `outs` of them"""
+    L = load_library()
+    r = np.ascontiguousarray(record, dtype).reshape(-1)
+    if r.size != 1:
+        raise ValueError("one status record at a time")
+    out = [C.c_double(0.0) for _ in range(outs)]
+    rc = getattr(L, f"{prefix}_{fn}")(r.ctypes.data_as(C.c_void_p), *args, *(C.byref(o) for o in out))
+    if rc != FMD_OK:
+        raise _global_error(L, prefix, rc)
+    return out[0].value if outs == 1 else tuple(o.value for o in out)
+
+
+class _Handle:
+    """What the side classes and RDSDecoder share: the library in self.L and one opaque handle of the C object `_prefix`, kept in the
+    attribute named `_attr` (None after a failed create and after close())."""
+    _prefix = ""
+    _attr = "h"
+
+    @property
+    def _h(self):
+        return getattr(self, self._attr, None)
+
+    def _fn(self, name: str):
+        """the library's function prefix_name"""
+        return getattr(self.L, f"{self._prefix}_{name}")
+
+    def _create(self, fn: str, *args):
+        """self.L and the handle from prefix_fn(*args, &handle); raises FmdError with create's own message (else the status string)"""
         self.L = load_library()
-        self.d = C.c_void_p()
-        rc = self.L.fmd_rdsdec_create(n_channels, device, C.byref(self.d))
+        h = C.c_void_p()
+        rc = self._fn(fn)(*args, C.byref(h))
+        setattr(self, self._attr, h if rc == FMD_OK else None)
         if rc != FMD_OK:
-            self.d = None
-            raise FmdError(rc, self.L.fmd_rdsdec_last_error(None).decode() or self.L.fmd_status_string(rc).decode())
-        self.n_channels = n_channels
-        self._gcap = 0
+            raise _global_error(self.L, self._prefix, rc)
 
     def close(self):
-        if getattr(self, "d", None):
-            self.L.fmd_rdsdec_destroy(self.d)
-            self.d = None
+        """destroys the C object (waiting for its work); safe to repeat, and after a failed create"""
+        if self._h:
+            self._fn("destroy")(self._h)
+            setattr(self, self._attr, None)
 
     def __del__(self):
         try:
@@ -584,8 +624,72 @@ class RDSDecoder:
             pass
 
     def _check(self, rc: int):
-        if rc != FMD_OK:
-            raise FmdError(rc, (self.L.fmd_rdsdec_last_error(self.d) or b"").decode() or self.L.fmd_status_string(rc).decode())
+        """a C call's status: raises FmdError for an error, with the handle's message (else the status string); returns rc otherwise"""
+        if rc < 0:
+            raise FmdError(rc, (self._fn("last_error")(self._h) or b"").decode() or self.L.fmd_status_string(rc).decode())
+        return rc
+
+
+class _Monitor(_Handle):
+    """The four per-station monitors (meter, modmon, squelch, audmon): [C] status records of `_status_dtype` that reset the same way."""
+    _status_dtype = None
+
+    def reset(self, channel: int = -1):
+        """station `channel` (-1 = every station) as after create; waits for the object's work"""
+        self._check(self._fn("reset")(self._h, int(channel)))
+
+    def reset_peaks(self, channel: int = -1):
+        """the held peaks alone of station `channel` (-1 = every station)"""
+        self._check(self._fn("reset_peaks")(self._h, int(channel)))
+
+    def status(self) -> np.ndarray:
+        """[C] records of the class's status dtype; waits for the object's work"""
+        out = np.zeros(self.n_channels, self._status_dtype)
+        self._check(self._fn("get_status")(self._h, out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def status_dev_ptr(self) -> int:
+        """prefix_status_dev: the address of the device's own [C] records, valid until the next process call"""
+        p = C.c_void_p()
+        self._check(self._fn("status_dev")(self._h, C.byref(p)))
+        return p.value
+
+
+class _Gated(_Monitor):
+    """The monitors with per-station parameters (squelch, audmon): a ctypes structure `_params_type` read and set by field name."""
+    _params_type = None
+
+    def _field(self, name: str, value):
+        """a field's value as the structure takes it"""
+        return value
+
+    def set_params(self, channel: int = -1, **fields):
+        """prefix_set_params: the named fields of the parameters for station `channel` (-1 = every station, each keeping its other
+        fields); ordered behind the object's earlier work, they apply from the next interval that ends"""
+        for c in (range(self.n_channels) if channel < 0 else (int(channel),)):
+            p = self.params(c)
+            for k, v in fields.items():
+                if k not in dict(self._params_type._fields_):
+                    raise TypeError(f"{self._params_type.__name__} has no field {k}")
+                setattr(p, k, self._field(k, v))
+            self._check(self._fn("set_params")(self._h, c, C.byref(p)))
+
+    def params(self, channel: int):
+        """prefix_get_params: station `channel`'s parameters, as set"""
+        p = self._params_type()
+        self._check(self._fn("get_params")(self._h, int(channel), C.byref(p)))
+        return p
+
+
+class RDSDecoder(_Handle):
+    """Standalone batched RDS decoding chain on the GPU (fmd_rdsdec_*): the reference's RDS_Decoding_Chain for C byte streams from
+    any source (a demodulator's RDS bytes, the scraper's _rds.bin files).  State carries over between process() calls."""
+    _prefix, _attr = "fmd_rdsdec", "d"
+
+    def __init__(self, n_channels: int, device: int = -1):
+        self._create("create", n_channels, device)
+        self.n_channels = n_channels
+        self._gcap = 0
 
     def reset(self):
         self._check(self.L.fmd_rdsdec_reset(self.d))
@@ -604,7 +708,7 @@ class RDSDecoder:
     def process_tensor(self, data, counts, stream=None) -> None:
         """data: torch uint8 [C, cap] and counts int32 [C] on the device; asynchronous on `stream` (default: torch's current stream)."""
         import torch
-        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        s = _stream_ptr(stream)
         assert data.is_contiguous() and counts.is_contiguous() and data.dtype == torch.uint8 and counts.dtype == torch.int32
         self._check(self.L.fmd_rdsdec_process_dev(self.d, C.c_void_p(data.data_ptr()), C.c_void_p(counts.data_ptr()), data.shape[1], C.c_void_p(s)))
         self._gcap = self.L.fmd_rdsdec_groups_cap(data.shape[1])
@@ -725,11 +829,7 @@ class BatchDemod:
 
     def wait_input(self, stream=None):
         """Make `stream` wait (on the device) until the newest submitted block's input buffer has been read."""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream().cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
+        stream = _stream_ptr(stream)
         self._check(self.L.fmd_wait_input(self.h, C.c_void_p(stream)))
 
     def synchronize(self):
@@ -758,21 +858,13 @@ class BatchDemod:
 
     def wait_outputs(self, stream=None):
         """Make `stream` (torch stream or raw handle; default: torch current stream) wait for the newest block's outputs."""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream().cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
+        stream = _stream_ptr(stream)
         self._check(self.L.fmd_wait_outputs(self.h, C.c_void_p(stream)))
 
     def release_outputs(self, stream=None):
         """Tell the library that everything queued on `stream` so far reads the newest block's output views: their buffers are
         not reused before that work has finished (fmd_release_outputs; device-side ordering, the host never blocks)."""
-        if stream is None:
-            import torch
-            stream = torch.cuda.current_stream().cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
+        stream = _stream_ptr(stream)
         self._check(self.L.fmd_release_outputs(self.h, C.c_void_p(stream)))
 
     # -- per-channel state snapshot / restore --
@@ -860,10 +952,7 @@ class BatchDemod:
         """Convert the newest block's audio to the reference scraper's 16-bit PCM frames into `out` (torch int16 CUDA tensor
         [C, n_audio, 2]) on `stream` (default: torch current stream), ordered behind the block's outputs."""
         import torch
-        if stream is None:
-            stream = torch.cuda.current_stream().cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
+        stream = _stream_ptr(stream)
         assert out.dtype == torch.int16 and out.is_contiguous() and out.numel() == self.n_channels * self.rates.n_audio * 2
         self._check(self.L.fmd_audio_pcm16_dev(self.h, C.c_void_p(out.data_ptr()), C.c_void_p(stream)))
         return out
@@ -943,7 +1032,7 @@ def chan_default_taps(fs_in: float, fs_out: float = 256_000.0) -> int:
     return t
 
 
-class Channelizer:
+class Channelizer(_Handle):
     """Wideband capture (cf32, u8, s8 or s16) -> [C][n_out] cf32 stations at fs_out on the GPU (fmd_chan_*); feeds BatchDemod.process directly.
 
     Accepts every pair of integer rates with fs_out / fs_in = L / M, L <= 64 and M / L <= 128 (fs_in up to 32.768 MSa/s at 256 kSa/s:
@@ -951,15 +1040,12 @@ class Channelizer:
     10 MSa/s -> 256 kSa/s with 640 taps per phase on the matrix cores (k_channelize16_mfma); the whole-band pairs with L dividing 16
     (16, 20, 20.48, 24, 30.72, 32, 32.768 MSa/s) on the matrix cores too (k_channelize_band_mfma); every other pair on the vector ALUs.
     A station's output does not depend on its row or on the number of stations."""
+    _prefix = "fmd_chan"
 
     def __init__(self, fs_in: float, center_hz, fs_out: float = 256_000.0, max_input_samples: int = 640_000, taps_per_phase: int = 0, device: int = -1):
-        self.L = load_library()
         self.centers = np.ascontiguousarray(center_hz, np.float64)
         cfg = ChanConfig(fs_in, fs_out, int(self.centers.size), self.centers.ctypes.data_as(C.POINTER(C.c_double)), taps_per_phase, max_input_samples, device)
-        self.h = C.c_void_p()
-        rc = self.L.fmd_chan_create(C.byref(cfg), C.byref(self.h))
-        if rc != FMD_OK:
-            raise FmdError(rc, self.L.fmd_chan_last_error(None).decode())
+        self._create("create", C.byref(cfg))
         l, m, t, c = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         self.L.fmd_chan_info(self.h, C.byref(l), C.byref(m), C.byref(t), C.byref(c))
         self.interp, self.decim, self.taps_per_phase, self.n_stations = l.value, m.value, t.value, c.value
@@ -984,29 +1070,13 @@ class Channelizer:
         n_out = n_in * self.interp // self.decim
         if out is None:
             out = torch.empty((self.n_stations, n_out, 2), dtype=torch.float32, device=wide.device)
-        if stream is None:
-            stream = torch.cuda.current_stream(wide.device).cuda_stream
         got = C.c_size_t(0)
-        rc = fns[wide.dtype](self.h, wide.data_ptr(), n_in, out.data_ptr(), int(out.shape[1]), C.byref(got), C.c_void_p(stream))
-        if rc != FMD_OK:
-            raise FmdError(rc, self.L.fmd_chan_last_error(self.h).decode())
+        self._check(fns[wide.dtype](self.h, wide.data_ptr(), n_in, out.data_ptr(), int(out.shape[1]), C.byref(got),
+                                    C.c_void_p(_stream_ptr(stream, wide.device))))
         return out[:, :got.value]
 
     def reset(self):
-        rc = self.L.fmd_chan_reset(self.h)
-        if rc != FMD_OK:
-            raise FmdError(rc, self.L.fmd_chan_last_error(self.h).decode())
-
-    def close(self):
-        if self.h:
-            self.L.fmd_chan_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._check(self.L.fmd_chan_reset(self.h))
 
 
 def scan_default_nfft(fs_in: float) -> int:
@@ -1060,24 +1130,17 @@ def scan_detect(psd, fs_in: float, **params) -> np.ndarray:
                      lambda: lib.fmd_scan_last_error(None).decode())
 
 
-class BandScanner:
+class BandScanner(_Handle):
     """Finds the stations of a wideband capture (fmd_scan_*): an averaged periodogram on the GPU (Hann window, N = nfft, hop N / 2, fp64
     sums in frame order: bit-identical however the capture is split into calls), then detection on an FM raster on the host.
     stations()["offset_hz"] goes straight to Channelizer(fs_in, ...)."""
+    _prefix = "fmd_scan"
 
     def __init__(self, fs_in: float, nfft: int = 0, max_input_samples: int = 2_097_152, device: int = -1):
-        self.L = load_library()
         self.fs_in = float(fs_in)
         cfg = ScanConfig(self.fs_in, int(nfft), int(max_input_samples), int(device))
-        self.h = C.c_void_p()
-        rc = self.L.fmd_scan_create(C.byref(cfg), C.byref(self.h))
-        if rc != FMD_OK:
-            raise FmdError(rc, self.L.fmd_scan_last_error(None).decode())
+        self._create("create", C.byref(cfg))
         self.nfft = int(nfft) if nfft else scan_default_nfft(fs_in)
-
-    def _check(self, rc: int):
-        if rc != FMD_OK:
-            raise FmdError(rc, self.L.fmd_scan_last_error(self.h).decode())
 
     def process(self, wide, stream=None) -> None:
         """wide: contiguous CUDA tensor [n_in, 2] of interleaved I, Q: float32, or a receiver's uint8 (v - 127), int8 or int16, read in place
@@ -1087,9 +1150,7 @@ class BandScanner:
                torch.int8: self.L.fmd_scan_process_s8_dev, torch.int16: self.L.fmd_scan_process_s16_dev}
         if not (wide.is_cuda and wide.is_contiguous() and wide.dtype in fns and wide.dim() == 2 and wide.shape[1] == 2):
             raise ValueError("wide must be a contiguous CUDA tensor [n_in, 2] of float32, uint8, int8 or int16")
-        if stream is None:
-            stream = torch.cuda.current_stream(wide.device).cuda_stream
-        self._check(fns[wide.dtype](self.h, wide.data_ptr(), int(wide.shape[0]), C.c_void_p(stream)))
+        self._check(fns[wide.dtype](self.h, wide.data_ptr(), int(wide.shape[0]), C.c_void_p(_stream_ptr(stream, wide.device))))
 
     def psd(self) -> tuple[np.ndarray, np.ndarray]:
         """(freqs_hz, psd) float64 [nfft], low to high frequency: bin i at (i - nfft / 2) fs_in / nfft.  Synchronises with the scanner."""
@@ -1113,17 +1174,6 @@ class BandScanner:
     def reset(self):
         self._check(self.L.fmd_scan_reset(self.h))
 
-    def close(self):
-        if self.h:
-            self.L.fmd_scan_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def iqcorr_solve(moments) -> IqCorrection:
     """Host-only solve step (fmd_iqcorr_solve): the six moments (IqMoments, or n, sum i, sum q, sum i^2, sum q^2, sum i q in that order)
@@ -1133,30 +1183,22 @@ def iqcorr_solve(moments) -> IqCorrection:
     c = _IqCorrectionC()
     rc = lib.fmd_iqcorr_solve(C.byref(m), C.byref(c))
     if rc != FMD_OK:
-        raise FmdError(rc, lib.fmd_iqcorr_last_error(None).decode())
+        raise _global_error(lib, "fmd_iqcorr", rc)
     return IqCorrection(c.dc_i, c.dc_q, c.w_re, c.w_im)
 
 
-class IqCorrector:
+class IqCorrector(_Handle):
     """Removes a receiver's DC offset and IQ imbalance from a wideband capture on the GPU (fmd_iqcorr_*), ahead of BandScanner and
     Channelizer.  process() adds every raw sample to fp64 moments (a fixed summation order: bit-identical however the capture is split into
     calls) and returns the samples as float32, corrected with the correction in force: identity until calibrate() or `correction` sets one."""
 
+    _prefix = "fmd_iqcorr"
     solve = staticmethod(iqcorr_solve)
 
     def __init__(self, max_input_samples: int = 2_097_152, device: int = -1):
-        self.L = load_library()
         cfg = IqcorrConfig(int(max_input_samples), int(device))
-        self.h = C.c_void_p()
-        rc = self.L.fmd_iqcorr_create(C.byref(cfg), C.byref(self.h))
-        if rc != FMD_OK:
-            self.h = C.c_void_p()
-            raise FmdError(rc, self.L.fmd_iqcorr_last_error(None).decode())
+        self._create("create", C.byref(cfg))
         self.max_input_samples = int(max_input_samples)
-
-    def _check(self, rc: int):
-        if rc != FMD_OK:
-            raise FmdError(rc, self.L.fmd_iqcorr_last_error(self.h).decode())
 
     def process(self, wide, out=None, stream=None):
         """wide: contiguous CUDA tensor [n_in, 2] of interleaved I, Q: float32, or a receiver's uint8 (v - 127), int8 or int16.  Returns the
@@ -1172,12 +1214,8 @@ class IqCorrector:
             out = torch.empty((n_in, 2), dtype=torch.float32, device=wide.device)
         if out is not False and not (out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (n_in, 2)):
             raise ValueError("out must be a contiguous CUDA float32 tensor [n_in, 2]")
-        if stream is None:
-            stream = torch.cuda.current_stream(wide.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
         self._check(fns[wide.dtype](self.h, C.c_void_p(wide.data_ptr()), n_in, None if out is False else C.c_void_p(out.data_ptr()),
-                                    C.c_void_p(stream)))
+                                    C.c_void_p(_stream_ptr(stream, wide.device))))
         return None if out is False else out
 
     def measure(self, wide, stream=None) -> None:
@@ -1214,17 +1252,6 @@ class IqCorrector:
     def reset_moments(self):
         self._check(self.L.fmd_iqcorr_reset_moments(self.h))
 
-    def close(self):
-        if self.h:
-            self.L.fmd_iqcorr_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def resampler_design(fs_in: int, fs_out: int, taps_per_phase: int = 0):
     """Host-only polyphase design of the audio resampler: (taps [T, L] float32 with taps[t, p] = h[p + t L], L, M).  Needs no GPU."""
@@ -1239,40 +1266,20 @@ def resampler_design(fs_in: int, fs_out: int, taps_per_phase: int = 0):
     return taps, L.value, M.value
 
 
-class AudioResampler:
+class AudioResampler(_Handle):
     """C stations' stereo audio from fs_in to fs_out on the GPU (fmd_resampler_*): the reference's Resampled_PCM_Player for a batch.
     method "reference" is its block-local linear interpolation, bit-identical; "polyphase" streams through an anti-aliasing filter.
     Feed it BatchDemod.audio_tensor() (or any [C, n, 2] float32 CUDA tensor whose frames are contiguous)."""
 
+    _prefix, _attr = "fmd_resampler", "r"
     design = staticmethod(resampler_design)
 
     def __init__(self, n_channels: int, fs_out: int, fs_in: int = 32000, method: str = "polyphase", taps_per_phase: int = 0,
                  max_input_frames: int = 1 << 16, device: int = -1):
-        self.L = load_library()
         m = {"reference": FMD_RESAMPLE_REFERENCE, "polyphase": FMD_RESAMPLE_POLYPHASE}[method]
         cfg = ResamplerConfig(n_channels, int(fs_in), int(fs_out), m, int(taps_per_phase), int(max_input_frames), device)
-        self.r = C.c_void_p()
-        rc = self.L.fmd_resampler_create(C.byref(cfg), C.byref(self.r))
-        if rc != FMD_OK:
-            self.r = None
-            raise FmdError(rc, self.L.fmd_resampler_last_error(None).decode() or self.L.fmd_status_string(rc).decode())
+        self._create("create", C.byref(cfg))
         self.n_channels, self.fs_in, self.fs_out, self.method = n_channels, int(fs_in), int(fs_out), method
-
-    def close(self):
-        if getattr(self, "r", None):
-            self.L.fmd_resampler_destroy(self.r)
-            self.r = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int):
-        if rc < 0:
-            raise FmdError(rc, (self.L.fmd_resampler_last_error(self.r) or b"").decode() or self.L.fmd_status_string(rc).decode())
-        return rc
 
     def output_frames(self, n_in: int) -> int:
         """frames per channel the next call with n_in input frames emits"""
@@ -1291,23 +1298,14 @@ class AudioResampler:
 
     def _run(self, fn, x, n_in, dtype, out, stream):
         import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
-                and x.stride(2) == 1 and x.stride(1) == 2):
-            raise ValueError("x must be a CUDA float32 tensor [C, n, 2] with contiguous frames")
-        n_in = int(x.shape[1]) if n_in is None else int(n_in)
+        px, in_stride, n_in = _batch_input(x, self.n_channels, n_in, ("float32",), "frames")
         want = self.output_frames(n_in)
         if out is None:
             out = torch.empty((self.n_channels, max(want, 1), 2), dtype=dtype, device=x.device)
         assert out.dtype == dtype and out.dim() == 3 and out.stride(2) == 1 and out.stride(1) == 2 and out.shape[1] >= want
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
         got = C.c_longlong(0)
-        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
         out_stride = out.stride(0) // 2 if out.shape[0] > 1 else out.shape[1]
-        self._check(fn(self.r, C.c_void_p(x.data_ptr()), in_stride, n_in, C.c_void_p(out.data_ptr()), out_stride, C.byref(got),
-                       C.c_void_p(stream)))
+        self._check(fn(self.r, px, in_stride, n_in, C.c_void_p(out.data_ptr()), out_stride, C.byref(got), C.c_void_p(_stream_ptr(stream, x.device))))
         return out[:, :got.value]
 
     def process(self, x, n_in: int | None = None, out=None, stream=None):
@@ -1322,14 +1320,14 @@ class AudioResampler:
         return self._run(self.L.fmd_resampler_process_pcm16_dev, x, n_in, torch.int16, out, stream)
 
 
-class AudioMixer:
+class AudioMixer(_Handle):
     """B output buses on the GPU (fmd_mixer_*), each one reference AudioMixer: bus b plays
     clamp(sum over its delivering sources, in order, of fmaf(x, gain_b / log10f(10 k), acc)), bit-identical to the reference's build.
     buses: a list of B lists of station rows in registration (CreateManagedBuffer) order; a row may appear in many buses.
     Feed it the same [C, n, 2] float32 CUDA tensors as AudioResampler (BatchDemod.audio_tensor() or a resampler's output)."""
+    _prefix, _attr = "fmd_mixer", "m"
 
     def __init__(self, n_channels: int, buses, gains=None, device: int = -1):
-        self.L = load_library()
         buses = [list(map(int, b)) for b in buses]
         offs = np.zeros(len(buses) + 1, np.int32)
         offs[1:] = np.cumsum([len(b) for b in buses])
@@ -1338,28 +1336,8 @@ class AudioMixer:
         if g is not None and g.shape != (len(buses),):
             raise ValueError("gains must hold one value per bus")
         cfg = MixerConfig(int(n_channels), len(buses), offs.ctypes.data, src.ctypes.data, None if g is None else g.ctypes.data, device)
-        self.m = C.c_void_p()
-        rc = self.L.fmd_mixer_create(C.byref(cfg), C.byref(self.m))
-        if rc != FMD_OK:
-            self.m = None
-            raise FmdError(rc, self.L.fmd_mixer_last_error(None).decode() or self.L.fmd_status_string(rc).decode())
+        self._create("create", C.byref(cfg))
         self.n_channels, self.n_buses = int(n_channels), len(buses)
-
-    def close(self):
-        if getattr(self, "m", None):
-            self.L.fmd_mixer_destroy(self.m)
-            self.m = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int):
-        if rc < 0:
-            raise FmdError(rc, (self.L.fmd_mixer_last_error(self.m) or b"").decode() or self.L.fmd_status_string(rc).decode())
-        return rc
 
     def set_sources(self, bus: int, sources):
         """replace a bus's sources (registration order); applies from the next process call"""
@@ -1381,29 +1359,15 @@ class AudioMixer:
         read, default all); active: None (every station delivered) or a [C] uint8 / bool CUDA tensor; out: [B, >= n, 2] float32.
         Returns [B, n, 2] float32, asynchronous on `stream` (default: torch's current stream)."""
         import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
-                and x.stride(2) == 1 and x.stride(1) == 2):
-            raise ValueError("x must be a CUDA float32 tensor [C, n, 2] with contiguous frames")
-        n = int(x.shape[1]) if n is None else int(n)
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32",), "frames")
         if out is None:
             out = torch.empty((self.n_buses, max(n, 1), 2), dtype=torch.float32, device=x.device)
         if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and out.shape[0] == self.n_buses and out.stride(2) == 1
                 and out.stride(1) == 2):
             raise ValueError("out must be a CUDA float32 tensor [B, n, 2] with contiguous frames")
-        if active is not None:
-            if active.dtype == torch.bool:
-                active = active.view(torch.uint8)
-            if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (self.n_channels,) and active.is_contiguous()):
-                raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
         out_stride = out.stride(0) // 2 if out.shape[0] > 1 else out.shape[1]
-        self._check(self.L.fmd_mixer_process_f32_dev(self.m, C.c_void_p(x.data_ptr()), in_stride, n,
-                                                     None if active is None else C.c_void_p(active.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                     out_stride, C.c_void_p(stream)))
+        self._check(self.L.fmd_mixer_process_f32_dev(self.m, px, in_stride, n, _active_ptr(active, self.n_channels), C.c_void_p(out.data_ptr()),
+                                                     out_stride, C.c_void_p(_stream_ptr(stream, x.device))))
         return out[:, :n]
 
 
@@ -1413,7 +1377,7 @@ def meter_design(fs: int) -> MeterDesign:
     d = MeterDesign()
     rc = L.fmd_meter_design(int(fs), C.byref(d))
     if rc != FMD_OK:
-        raise FmdError(rc, L.fmd_meter_last_error(None).decode() or L.fmd_status_string(rc).decode())
+        raise _global_error(L, "fmd_meter", rc)
     return d
 
 
@@ -1431,30 +1395,18 @@ def meter_integrated(hist, design: MeterDesign) -> float:
     out = C.c_double(0.0)
     rc = L.fmd_meter_integrated(h.ctypes.data_as(C.c_void_p), C.byref(design), C.byref(out))
     if rc != FMD_OK:
-        raise FmdError(rc, L.fmd_meter_last_error(None).decode() or L.fmd_status_string(rc).decode())
-    return out.value
-
-
-def _meter_window(fn, record) -> float:
-    L = load_library()
-    r = np.ascontiguousarray(record, METER_STATUS_DTYPE).reshape(-1)
-    if r.size != 1:
-        raise ValueError("one status record at a time")
-    out = C.c_double(0.0)
-    rc = getattr(L, fn)(r.ctypes.data_as(C.c_void_p), C.byref(out))
-    if rc != FMD_OK:
-        raise FmdError(rc, L.fmd_meter_last_error(None).decode() or L.fmd_status_string(rc).decode())
+        raise _global_error(L, "fmd_meter", rc)
     return out.value
 
 
 def meter_momentary(record) -> float:
     """fmd_meter_momentary of one METER_STATUS_DTYPE record: the last 400 ms, in LUFS (FMD_ERR_STATE before 4 sub-blocks)"""
-    return _meter_window("fmd_meter_momentary", record)
+    return _record_read("fmd_meter", "momentary", record, METER_STATUS_DTYPE)
 
 
 def meter_short_term(record) -> float:
     """fmd_meter_short_term of one METER_STATUS_DTYPE record: the last 3 s, in LUFS (FMD_ERR_STATE before 30 sub-blocks)"""
-    return _meter_window("fmd_meter_short_term", record)
+    return _record_read("fmd_meter", "short_term", record, METER_STATUS_DTYPE)
 
 
 def meter_tp_design(fs: int) -> MeterTpDesign:
@@ -1463,7 +1415,7 @@ def meter_tp_design(fs: int) -> MeterTpDesign:
     d = MeterTpDesign()
     rc = L.fmd_meter_tp_design(int(fs), C.byref(d))
     if rc != FMD_OK:
-        raise FmdError(rc, L.fmd_meter_last_error(None).decode() or L.fmd_status_string(rc).decode())
+        raise _global_error(L, "fmd_meter", rc)
     return d
 
 
@@ -1485,88 +1437,36 @@ def meter_range(hist, design: MeterDesign):
     lra, low, high = C.c_double(0.0), C.c_double(0.0), C.c_double(0.0)
     rc = L.fmd_meter_range(h.ctypes.data_as(C.c_void_p), C.byref(design), C.byref(lra), C.byref(low), C.byref(high))
     if rc != FMD_OK:
-        raise FmdError(rc, L.fmd_meter_last_error(None).decode() or L.fmd_status_string(rc).decode())
+        raise _global_error(L, "fmd_meter", rc)
     return lra.value, low.value, high.value
 
 
-class LoudnessMeter:
+class LoudnessMeter(_Monitor):
     """ITU-R BS.1770 loudness and sample peak of C stations' audio on the GPU (fmd_meter_*).  Feed it the same [C, n, 2] float32 CUDA
     tensors as AudioResampler and AudioMixer (BatchDemod.audio_tensor() at 32 kHz, or a resampler's output at fs); it changes nothing in
     them.  status() returns METER_STATUS_DTYPE records, histogram() the gating blocks' [C, 1000] counts; momentary / short_term /
     integrated turn them into LUFS on the host.  features = METER_TRUE_PEAK | METER_RANGE adds the maximum true-peak level
     (r128_status(), true_peak_dbtp()) and the loudness range (range_histogram(), loudness_range())."""
+    _prefix, _attr, _status_dtype = "fmd_meter", "m", METER_STATUS_DTYPE
 
     def __init__(self, n_channels: int, fs: int, max_input_frames: int = 1 << 16, device: int = -1, features: int = 0):
-        self.L = load_library()
         cfg = MeterConfig(int(n_channels), int(fs), int(max_input_frames), device)
-        self.m = C.c_void_p()
-        rc = self.L.fmd_meter_create_ex(C.byref(cfg), int(features), C.byref(self.m))
-        if rc != FMD_OK:
-            self.m = None
-            raise FmdError(rc, self.L.fmd_meter_last_error(None).decode() or self.L.fmd_status_string(rc).decode())
+        self._create("create_ex", C.byref(cfg), int(features))
         self.n_channels, self.fs, self.features = int(n_channels), int(fs), int(features)
         self.design = meter_design(fs)
-
-    def close(self):
-        if getattr(self, "m", None):
-            self.L.fmd_meter_destroy(self.m)
-            self.m = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int):
-        if rc < 0:
-            raise FmdError(rc, (self.L.fmd_meter_last_error(self.m) or b"").decode() or self.L.fmd_status_string(rc).decode())
-        return rc
 
     def process(self, x, n: int | None = None, active=None, stream=None):
         """meters the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
         uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole).  Asynchronous on `stream` (default: torch's current)."""
-        import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
-                and x.stride(2) == 1 and x.stride(1) == 2):
-            raise ValueError("x must be a CUDA float32 tensor [C, n, 2] with contiguous frames")
-        n = int(x.shape[1]) if n is None else int(n)
-        if active is not None:
-            if active.dtype == torch.bool:
-                active = active.view(torch.uint8)
-            if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (self.n_channels,) and active.is_contiguous()):
-                raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
-        self._check(self.L.fmd_meter_process_f32_dev(self.m, C.c_void_p(x.data_ptr()), in_stride, n,
-                                                     None if active is None else C.c_void_p(active.data_ptr()), C.c_void_p(stream)))
-
-    def reset(self, channel: int = -1):
-        self._check(self.L.fmd_meter_reset(self.m, int(channel)))
-
-    def reset_peaks(self, channel: int = -1):
-        self._check(self.L.fmd_meter_reset_peaks(self.m, int(channel)))
-
-    def status(self) -> np.ndarray:
-        """[C] METER_STATUS_DTYPE records; waits for the meter's work"""
-        out = np.zeros(self.n_channels, METER_STATUS_DTYPE)
-        self._check(self.L.fmd_meter_get_status(self.m, out.ctypes.data_as(C.c_void_p)))
-        return out
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32",), "frames")
+        self._check(self.L.fmd_meter_process_f32_dev(self.m, px, in_stride, n, _active_ptr(active, self.n_channels),
+                                                     C.c_void_p(_stream_ptr(stream, x.device))))
 
     def histogram(self) -> np.ndarray:
         """[C, 1000] uint32 counts of gating blocks per 0.1 LU bin from -70 LUFS; waits for the meter's work"""
         out = np.zeros((self.n_channels, METER_BINS), np.uint32)
         self._check(self.L.fmd_meter_get_histogram(self.m, out.ctypes.data_as(C.c_void_p)))
         return out
-
-    def status_dev_ptr(self) -> int:
-        """fmd_meter_status_dev: the address of the device's own [C] records, valid until the next process call"""
-        p = C.c_void_p()
-        self._check(self.L.fmd_meter_status_dev(self.m, C.byref(p)))
-        return p.value
 
     def integrated(self, hist=None) -> np.ndarray:
         """[C] float64 LUFS: the gated programme loudness since reset (-inf where no gating block passed -70 LUFS)"""
@@ -1612,10 +1512,6 @@ class LoudnessMeter:
         return meter_dbtp(self.r128_status()["tp_hold"])
 
 
-def _modmon_raise(L, rc):
-    raise FmdError(rc, L.fmd_modmon_last_error(None).decode() or L.fmd_status_string(rc).decode())
-
-
 def modmon_design(fs: int) -> ModmonDesign:
     """fmd_modmon_design (host only, no GPU needed): the interval length M, the MPX low-pass's 33 taps, the pilot table and its gain,
     and the histogram's edges"""
@@ -1623,42 +1519,30 @@ def modmon_design(fs: int) -> ModmonDesign:
     d = ModmonDesign()
     rc = L.fmd_modmon_design(int(fs), C.byref(d))
     if rc != FMD_OK:
-        _modmon_raise(L, rc)
+        raise _global_error(L, "fmd_modmon", rc)
     return d
-
-
-def _modmon_record(fn, record, design: ModmonDesign, *args) -> float:
-    L = load_library()
-    r = np.ascontiguousarray(record, MODMON_STATUS_DTYPE).reshape(-1)
-    if r.size != 1:
-        raise ValueError("one status record at a time")
-    out = C.c_double(0.0)
-    rc = getattr(L, fn)(r.ctypes.data_as(C.c_void_p), C.byref(design), *args, C.byref(out))
-    if rc != FMD_OK:
-        _modmon_raise(L, rc)
-    return out.value
 
 
 def modmon_deviation_hz(record, design: ModmonDesign) -> float:
     """fmd_modmon_deviation_hz of one MODMON_STATUS_DTYPE record: half the peak-to-peak swing of the newest 50 ms interval, in Hz
     (FMD_ERR_STATE before the first interval)"""
-    return _modmon_record("fmd_modmon_deviation_hz", record, design)
+    return _record_read("fmd_modmon", "deviation_hz", record, MODMON_STATUS_DTYPE, C.byref(design))
 
 
 def modmon_offset_hz(record, design: ModmonDesign) -> float:
     """fmd_modmon_offset_hz: the carrier's frequency offset over the newest interval, in Hz"""
-    return _modmon_record("fmd_modmon_offset_hz", record, design)
+    return _record_read("fmd_modmon", "offset_hz", record, MODMON_STATUS_DTYPE, C.byref(design))
 
 
 def modmon_pilot_hz(record, design: ModmonDesign) -> float:
     """fmd_modmon_pilot_hz: the 19 kHz pilot's deviation over the newest interval, in Hz"""
-    return _modmon_record("fmd_modmon_pilot_hz", record, design)
+    return _record_read("fmd_modmon", "pilot_hz", record, MODMON_STATUS_DTYPE, C.byref(design))
 
 
 def modmon_mpx_power_dbr(record, design: ModmonDesign, window_s: int = 60) -> float:
     """fmd_modmon_mpx_power_dbr: ITU-R BS.412 multiplex power over the newest window_s completed seconds, in dBr (FMD_ERR_STATE while
     fewer are complete)"""
-    return _modmon_record("fmd_modmon_mpx_power_dbr", record, design, C.c_int(int(window_s)))
+    return _record_read("fmd_modmon", "mpx_power_dbr", record, MODMON_STATUS_DTYPE, C.byref(design), int(window_s))
 
 
 def _modmon_hist(hist):
@@ -1676,7 +1560,7 @@ def modmon_exceedance(hist, over: int, limit_hz: int = 75000):
     frac, cnt = C.c_double(0.0), C.c_ulonglong(0)
     rc = L.fmd_modmon_exceedance(h.ctypes.data_as(C.c_void_p), int(over), int(limit_hz), C.byref(frac), C.byref(cnt))
     if rc != FMD_OK:
-        _modmon_raise(L, rc)
+        raise _global_error(L, "fmd_modmon", rc)
     return frac.value, cnt.value
 
 
@@ -1687,93 +1571,37 @@ def modmon_percentile(hist, over: int, q: float) -> float:
     out = C.c_double(0.0)
     rc = L.fmd_modmon_percentile(h.ctypes.data_as(C.c_void_p), int(over), float(q), C.byref(out))
     if rc != FMD_OK:
-        _modmon_raise(L, rc)
+        raise _global_error(L, "fmd_modmon", rc)
     return out.value
 
 
-class ModulationMonitor:
+class ModulationMonitor(_Monitor):
     """Peak deviation (ITU-R SM.1268), multiplex power (ITU-R BS.412), carrier offset and pilot deviation of C stations' baseband on the
     GPU (fmd_modmon_*).  Feed it the [C, n, 2] float32 or uint8 CUDA tensors the demodulator takes (a channeliser's output); it changes
     nothing in them.  status() returns MODMON_STATUS_DTYPE records, histogram() the interval peaks' [C, 300] counts; the modmon_*
     functions turn them into Hz and dBr on the host."""
+    _prefix, _attr, _status_dtype = "fmd_modmon", "m", MODMON_STATUS_DTYPE
 
     def __init__(self, n_channels: int, fs: int, max_input_samples: int = 1 << 20, device: int = -1):
-        self.L = load_library()
         cfg = ModmonConfig(int(n_channels), int(fs), int(max_input_samples), device)
-        self.m = C.c_void_p()
-        rc = self.L.fmd_modmon_create(C.byref(cfg), C.byref(self.m))
-        if rc != FMD_OK:
-            self.m = None
-            _modmon_raise(self.L, rc)
+        self._create("create", C.byref(cfg))
         self.n_channels, self.fs = int(n_channels), int(fs)
         self.design = modmon_design(fs)
-
-    def close(self):
-        if getattr(self, "m", None):
-            self.L.fmd_modmon_destroy(self.m)
-            self.m = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int):
-        if rc < 0:
-            raise FmdError(rc, (self.L.fmd_modmon_last_error(self.m) or b"").decode() or self.L.fmd_status_string(rc).decode())
-        return rc
 
     def process(self, x, n: int | None = None, active=None, stream=None):
         """monitors the first n samples (default all) of x: [C, >= n, 2] float32 or uint8 on the device, contiguous samples; active: None
         or a [C] uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole).  Asynchronous on `stream` (default: torch's
         current)."""
         import torch
-        if not (x.is_cuda and x.dtype in (torch.float32, torch.uint8) and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
-                and x.stride(2) == 1 and x.stride(1) == 2):
-            raise ValueError("x must be a CUDA float32 or uint8 tensor [C, n, 2] with contiguous samples")
-        n = int(x.shape[1]) if n is None else int(n)
-        if active is not None:
-            if active.dtype == torch.bool:
-                active = active.view(torch.uint8)
-            if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (self.n_channels,) and active.is_contiguous()):
-                raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32", "uint8"), "samples")
         fn = self.L.fmd_modmon_process_cf32_dev if x.dtype == torch.float32 else self.L.fmd_modmon_process_u8_dev
-        self._check(fn(self.m, C.c_void_p(x.data_ptr()), in_stride, n, None if active is None else C.c_void_p(active.data_ptr()),
-                       C.c_void_p(stream)))
-
-    def reset(self, channel: int = -1):
-        self._check(self.L.fmd_modmon_reset(self.m, int(channel)))
-
-    def reset_peaks(self, channel: int = -1):
-        self._check(self.L.fmd_modmon_reset_peaks(self.m, int(channel)))
-
-    def status(self) -> np.ndarray:
-        """[C] MODMON_STATUS_DTYPE records; waits for the monitor's work"""
-        out = np.zeros(self.n_channels, MODMON_STATUS_DTYPE)
-        self._check(self.L.fmd_modmon_get_status(self.m, out.ctypes.data_as(C.c_void_p)))
-        return out
+        self._check(fn(self.m, px, in_stride, n, _active_ptr(active, self.n_channels), C.c_void_p(_stream_ptr(stream, x.device))))
 
     def histogram(self) -> np.ndarray:
         """[C, 300] uint32 counts of 50 ms intervals per 500 Hz bin of peak deviation; waits for the monitor's work"""
         out = np.zeros((self.n_channels, MODMON_BINS), np.uint32)
         self._check(self.L.fmd_modmon_get_histogram(self.m, out.ctypes.data_as(C.c_void_p)))
         return out
-
-    def status_dev_ptr(self) -> int:
-        """fmd_modmon_status_dev: the address of the device's own [C] records, valid until the next process call"""
-        p = C.c_void_p()
-        self._check(self.L.fmd_modmon_status_dev(self.m, C.byref(p)))
-        return p.value
-
-
-def _squelch_raise(L, rc):
-    raise FmdError(rc, L.fmd_squelch_last_error(None).decode() or L.fmd_status_string(rc).decode())
 
 
 def squelch_default_params() -> SquelchParams:
@@ -1788,141 +1616,46 @@ def squelch_threshold(db: float) -> float:
     return load_library().fmd_squelch_threshold(float(db))
 
 
-def _squelch_record(record):
-    r = np.ascontiguousarray(record, SQUELCH_STATUS_DTYPE).reshape(-1)
-    if r.size != 1:
-        raise ValueError("one status record at a time")
-    return r
-
-
 def squelch_level_db(record, fs: int) -> float:
     """fmd_squelch_level_db of one SQUELCH_STATUS_DTYPE record: the newest interval's mean power in dB of the input's own units
     (FMD_ERR_STATE before the first interval)"""
-    L, r, out = load_library(), _squelch_record(record), C.c_double(0.0)
-    rc = L.fmd_squelch_level_db(r.ctypes.data_as(C.c_void_p), int(fs), C.byref(out))
-    if rc != FMD_OK:
-        _squelch_raise(L, rc)
-    return out.value
+    return _record_read("fmd_squelch", "level_db", record, SQUELCH_STATUS_DTYPE, int(fs))
 
 
 def squelch_cnr_db(record, fs: int, window: int = 1) -> float:
     """fmd_squelch_cnr_db: the envelope-constancy carrier-to-noise ratio over the newest `window` (1 ... 20) intervals in dB, -inf where no
     carrier shows and +inf where no noise does (FMD_ERR_STATE while fewer intervals are complete)"""
-    L, r, out = load_library(), _squelch_record(record), C.c_double(0.0)
-    rc = L.fmd_squelch_cnr_db(r.ctypes.data_as(C.c_void_p), int(fs), int(window), C.byref(out))
-    if rc != FMD_OK:
-        _squelch_raise(L, rc)
-    return out.value
+    return _record_read("fmd_squelch", "cnr_db", record, SQUELCH_STATUS_DTYPE, int(fs), int(window))
 
 
 def squelch_powers(record, fs: int, window: int = 1):
     """fmd_squelch_powers: (carrier, noise) power per sample over the newest `window` intervals, in the input's own units squared"""
-    L, r, a, b = load_library(), _squelch_record(record), C.c_double(0.0), C.c_double(0.0)
-    rc = L.fmd_squelch_powers(r.ctypes.data_as(C.c_void_p), int(fs), int(window), C.byref(a), C.byref(b))
-    if rc != FMD_OK:
-        _squelch_raise(L, rc)
-    return a.value, b.value
+    return _record_read("fmd_squelch", "powers", record, SQUELCH_STATUS_DTYPE, int(fs), int(window), outs=2)
 
 
-class Squelch:
+class Squelch(_Gated):
     """Carrier squelch of C stations' baseband on the GPU (fmd_squelch_*): per station and 50 ms interval the power moments behind an
     envelope-constancy CNR, a hysteresis gate, and the [C] uint8 mask that AudioMixer.process(active=...), LoudnessMeter.process and
     ModulationMonitor.process take as it is.  Feed it the [C, n, 2] float32 or uint8 CUDA tensors the demodulator takes (a channeliser's
     output); it changes nothing in them.  status() returns SQUELCH_STATUS_DTYPE records; the squelch_* functions turn them into dB."""
+    _prefix, _attr, _status_dtype, _params_type = "fmd_squelch", "q", SQUELCH_STATUS_DTYPE, SquelchParams
 
     def __init__(self, n_channels: int, fs: int, max_input_samples: int = 1 << 20, device: int = -1):
-        self.L = load_library()
         cfg = SquelchConfig(int(n_channels), int(fs), int(max_input_samples), device)
-        self.q = C.c_void_p()
-        rc = self.L.fmd_squelch_create(C.byref(cfg), C.byref(self.q))
-        if rc != FMD_OK:
-            self.q = None
-            _squelch_raise(self.L, rc)
+        self._create("create", C.byref(cfg))
         self.n_channels, self.fs = int(n_channels), int(fs)
-
-    def close(self):
-        if getattr(self, "q", None):
-            self.L.fmd_squelch_destroy(self.q)
-            self.q = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int):
-        if rc < 0:
-            raise FmdError(rc, (self.L.fmd_squelch_last_error(self.q) or b"").decode() or self.L.fmd_status_string(rc).decode())
-        return rc
 
     def process(self, x, n: int | None = None, active=None, mask=None, stream=None):
         """takes the first n samples (default all) of x: [C, >= n, 2] float32 or uint8 on the device, contiguous samples; active: None or a
         [C] uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole and keeps its mask byte); mask: the [C] uint8 CUDA tensor
         to write, None = a new one.  Returns the mask tensor.  Asynchronous on `stream` (default: torch's current)."""
         import torch
-        if not (x.is_cuda and x.dtype in (torch.float32, torch.uint8) and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
-                and x.stride(2) == 1 and x.stride(1) == 2):
-            raise ValueError("x must be a CUDA float32 or uint8 tensor [C, n, 2] with contiguous samples")
-        n = int(x.shape[1]) if n is None else int(n)
-        if active is not None:
-            if active.dtype == torch.bool:
-                active = active.view(torch.uint8)
-            if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (self.n_channels,) and active.is_contiguous()):
-                raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        if mask is None:
-            # zeroed on the stream the call then writes it on (0 is the default stream, on which torch works unless told otherwise)
-            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=x.device) if stream else torch.cuda.default_stream(x.device)):
-                mask = torch.zeros(self.n_channels, dtype=torch.uint8, device=x.device)
-        elif not (mask.is_cuda and mask.dtype == torch.uint8 and mask.shape == (self.n_channels,) and mask.is_contiguous()):
-            raise ValueError("mask must be a contiguous [C] uint8 CUDA tensor")
-        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32", "uint8"), "samples")
+        pa, stream = _active_ptr(active, self.n_channels), _stream_ptr(stream, x.device)
+        mask, pm = _byte_out(mask, "mask", self.n_channels, x.device, stream)
         fn = self.L.fmd_squelch_process_cf32_dev if x.dtype == torch.float32 else self.L.fmd_squelch_process_u8_dev
-        self._check(fn(self.q, C.c_void_p(x.data_ptr()), in_stride, n, None if active is None else C.c_void_p(active.data_ptr()),
-                       C.c_void_p(mask.data_ptr()), C.c_void_p(stream)))
+        self._check(fn(self.q, px, in_stride, n, pa, pm, C.c_void_p(stream)))
         return mask
-
-    def set_params(self, channel: int = -1, **fields):
-        """fmd_squelch_set_params: the named fields of SquelchParams for station `channel` (-1 = every station, each keeping its other
-        fields); ordered behind the squelch's earlier work, they apply from the next interval that ends"""
-        for c in (range(self.n_channels) if channel < 0 else (int(channel),)):
-            p = self.params(c)
-            for k, v in fields.items():
-                if k not in dict(SquelchParams._fields_):
-                    raise TypeError(f"SquelchParams has no field {k}")
-                setattr(p, k, v)
-            self._check(self.L.fmd_squelch_set_params(self.q, c, C.byref(p)))
-
-    def params(self, channel: int) -> SquelchParams:
-        p = SquelchParams()
-        self._check(self.L.fmd_squelch_get_params(self.q, int(channel), C.byref(p)))
-        return p
-
-    def reset(self, channel: int = -1):
-        self._check(self.L.fmd_squelch_reset(self.q, int(channel)))
-
-    def reset_peaks(self, channel: int = -1):
-        self._check(self.L.fmd_squelch_reset_peaks(self.q, int(channel)))
-
-    def status(self) -> np.ndarray:
-        """[C] SQUELCH_STATUS_DTYPE records; waits for the squelch's work"""
-        out = np.zeros(self.n_channels, SQUELCH_STATUS_DTYPE)
-        self._check(self.L.fmd_squelch_get_status(self.q, out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def status_dev_ptr(self) -> int:
-        """fmd_squelch_status_dev: the address of the device's own [C] records, valid until the next process call"""
-        p = C.c_void_p()
-        self._check(self.L.fmd_squelch_status_dev(self.q, C.byref(p)))
-        return p.value
-
-
-def _audmon_raise(L, rc):
-    raise FmdError(rc, L.fmd_audmon_last_error(None).decode() or L.fmd_status_string(rc).decode())
 
 
 def audmon_default_params() -> AudmonParams:
@@ -1933,145 +1666,54 @@ def audmon_default_params() -> AudmonParams:
     return p
 
 
-def _audmon_record(record):
-    r = np.ascontiguousarray(record, AUDMON_STATUS_DTYPE).reshape(-1)
-    if r.size != 1:
-        raise ValueError("one status record at a time")
-    return r
-
-
-def _audmon_read(fn: str, record, fs: int, *args) -> float:
-    L, r, out = load_library(), _audmon_record(record), C.c_double(0.0)
-    rc = getattr(L, fn)(r.ctypes.data_as(C.c_void_p), int(fs), *[int(a) for a in args], C.byref(out))
-    if rc != FMD_OK:
-        _audmon_raise(L, rc)
-    return out.value
-
-
 def audmon_level_db(record, fs: int, rail: int = 2, window: int = 1) -> float:
     """fmd_audmon_level_db of one AUDMON_STATUS_DTYPE record: the mean power of rail 0 (L), 1 (R) or 2 (both) over the newest `window`
     (1 ... 30) intervals in dB of full scale 1.0, -inf for silence (FMD_ERR_STATE while fewer intervals are complete)"""
-    return _audmon_read("fmd_audmon_level_db", record, fs, rail, window)
+    return _record_read("fmd_audmon", "level_db", record, AUDMON_STATUS_DTYPE, int(fs), int(rail), int(window))
 
 
 def audmon_balance_db(record, fs: int, window: int = 1) -> float:
     """fmd_audmon_balance_db: L over R in dB (NaN for 0 / 0)"""
-    return _audmon_read("fmd_audmon_balance_db", record, fs, window)
+    return _record_read("fmd_audmon", "balance_db", record, AUDMON_STATUS_DTYPE, int(fs), int(window))
 
 
 def audmon_correlation(record, fs: int, window: int = 1) -> float:
     """fmd_audmon_correlation: sum L R / sqrt(sum L^2 sum R^2), -1 ... 1 (NaN for 0 / 0)"""
-    return _audmon_read("fmd_audmon_correlation", record, fs, window)
+    return _record_read("fmd_audmon", "correlation", record, AUDMON_STATUS_DTYPE, int(fs), int(window))
 
 
 def audmon_side_mid_db(record, fs: int, window: int = 1) -> float:
     """fmd_audmon_side_mid_db: sum (L - R)^2 over sum (L + R)^2 in dB, -inf for R == L (NaN for 0 / 0)"""
-    return _audmon_read("fmd_audmon_side_mid_db", record, fs, window)
+    return _record_read("fmd_audmon", "side_mid_db", record, AUDMON_STATUS_DTYPE, int(fs), int(window))
 
 
-class AudioMonitor:
+class AudioMonitor(_Gated):
     """Audio fault monitor of C stations' audio on the GPU (fmd_audmon_*): per station and 100 ms interval the sums of L^2, R^2 and L R
     and the rail peaks, five hysteresis detectors (AUDMON_SILENCE, _LEFT_LOST, _RIGHT_LOST, _ANTIPHASE, _MONO), and two [C] uint8 tensors:
     the flags and the ok bytes, which AudioMixer.process(active=...) and LoudnessMeter.process take as they are.  Feed it the same
     [C, n, 2] float32 CUDA tensors as AudioResampler, AudioMixer and LoudnessMeter (BatchDemod.audio_tensor() at 32 kHz, or a resampler's
     output at fs); it changes nothing in them.  status() returns AUDMON_STATUS_DTYPE records; the audmon_* functions turn them into dB."""
+    _prefix, _attr, _status_dtype, _params_type = "fmd_audmon", "a", AUDMON_STATUS_DTYPE, AudmonParams
 
     def __init__(self, n_channels: int, fs: int, max_input_frames: int = 1 << 16, device: int = -1):
-        self.L = load_library()
         cfg = AudmonConfig(int(n_channels), int(fs), int(max_input_frames), device)
-        self.a = C.c_void_p()
-        rc = self.L.fmd_audmon_create(C.byref(cfg), C.byref(self.a))
-        if rc != FMD_OK:
-            self.a = None
-            _audmon_raise(self.L, rc)
+        self._create("create", C.byref(cfg))
         self.n_channels, self.fs = int(n_channels), int(fs)
-
-    def close(self):
-        if getattr(self, "a", None):
-            self.L.fmd_audmon_destroy(self.a)
-            self.a = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _check(self, rc: int):
-        if rc < 0:
-            raise FmdError(rc, (self.L.fmd_audmon_last_error(self.a) or b"").decode() or self.L.fmd_status_string(rc).decode())
-        return rc
 
     def process(self, x, n: int | None = None, active=None, flags=None, ok=None, stream=None):
         """takes the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
         uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole and keeps its two bytes); flags, ok: the [C] uint8 CUDA
         tensors to write, None = a new one, False = not written.  Returns (flags, ok), None for one not written.  Asynchronous on
         `stream` (default: torch's current)."""
-        import torch
-        if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 3 and x.shape[0] == self.n_channels and x.shape[2] == 2
-                and x.stride(2) == 1 and x.stride(1) == 2):
-            raise ValueError("x must be a CUDA float32 tensor [C, n, 2] with contiguous frames")
-        n = int(x.shape[1]) if n is None else int(n)
-        if active is not None:
-            if active.dtype == torch.bool:
-                active = active.view(torch.uint8)
-            if not (active.is_cuda and active.dtype == torch.uint8 and active.shape == (self.n_channels,) and active.is_contiguous()):
-                raise ValueError("active must be a contiguous [C] uint8 or bool CUDA tensor")
-        if stream is None:
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-        elif hasattr(stream, "cuda_stream"):
-            stream = stream.cuda_stream
-        outs = []
-        for name, t in (("flags", flags), ("ok", ok)):
-            if t is None:
-                # zeroed on the stream the call then writes it on (0 is the default stream, on which torch works unless told otherwise)
-                with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=x.device) if stream else torch.cuda.default_stream(x.device)):
-                    t = torch.zeros(self.n_channels, dtype=torch.uint8, device=x.device)
-            elif t is False:
-                t = None
-            elif not (t.is_cuda and t.dtype == torch.uint8 and t.shape == (self.n_channels,) and t.is_contiguous()):
-                raise ValueError(f"{name} must be a contiguous [C] uint8 CUDA tensor")
-            outs.append(t)
-        in_stride = x.stride(0) // 2 if x.shape[0] > 1 else x.shape[1]     # (a batch of one may carry any stride on its first axis)
-        self._check(self.L.fmd_audmon_process_f32_dev(self.a, C.c_void_p(x.data_ptr()), in_stride, n,
-                                                      None if active is None else C.c_void_p(active.data_ptr()),
-                                                      None if outs[0] is None else C.c_void_p(outs[0].data_ptr()),
-                                                      None if outs[1] is None else C.c_void_p(outs[1].data_ptr()), C.c_void_p(stream)))
-        return outs[0], outs[1]
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32",), "frames")
+        pa, stream = _active_ptr(active, self.n_channels), _stream_ptr(stream, x.device)
+        flags, pf = _byte_out(flags, "flags", self.n_channels, x.device, stream)
+        ok, po = _byte_out(ok, "ok", self.n_channels, x.device, stream)
+        self._check(self.L.fmd_audmon_process_f32_dev(self.a, px, in_stride, n, pa, pf, po, C.c_void_p(stream)))
+        return flags, ok
 
-    def set_params(self, channel: int = -1, **fields):
-        """fmd_audmon_set_params: the named fields of AudmonParams for station `channel` (-1 = every station, each keeping its other
-        fields); raise_intervals and clear_intervals take five values or one for all five.  Ordered behind the monitor's earlier work,
-        they apply from the next interval that ends"""
-        for c in (range(self.n_channels) if channel < 0 else (int(channel),)):
-            p = self.params(c)
-            for k, v in fields.items():
-                if k not in dict(AudmonParams._fields_):
-                    raise TypeError(f"AudmonParams has no field {k}")
-                if k in ("raise_intervals", "clear_intervals"):
-                    v = (C.c_int * 5)(*([int(v)] * 5 if np.isscalar(v) else [int(a) for a in v]))
-                setattr(p, k, v)
-            self._check(self.L.fmd_audmon_set_params(self.a, c, C.byref(p)))
-
-    def params(self, channel: int) -> AudmonParams:
-        p = AudmonParams()
-        self._check(self.L.fmd_audmon_get_params(self.a, int(channel), C.byref(p)))
-        return p
-
-    def reset(self, channel: int = -1):
-        self._check(self.L.fmd_audmon_reset(self.a, int(channel)))
-
-    def reset_peaks(self, channel: int = -1):
-        self._check(self.L.fmd_audmon_reset_peaks(self.a, int(channel)))
-
-    def status(self) -> np.ndarray:
-        """[C] AUDMON_STATUS_DTYPE records; waits for the monitor's work"""
-        out = np.zeros(self.n_channels, AUDMON_STATUS_DTYPE)
-        self._check(self.L.fmd_audmon_get_status(self.a, out.ctypes.data_as(C.c_void_p)))
-        return out
-
-    def status_dev_ptr(self) -> int:
-        """fmd_audmon_status_dev: the address of the device's own [C] records, valid until the next process call"""
-        p = C.c_void_p()
-        self._check(self.L.fmd_audmon_status_dev(self.a, C.byref(p)))
-        return p.value
+    def _field(self, name: str, value):
+        """raise_intervals and clear_intervals take five values or one for all five"""
+        if name in ("raise_intervals", "clear_intervals"):
+            return (C.c_int * 5)(*([int(value)] * 5 if np.isscalar(value) else [int(a) for a in value]))
+        return value

@@ -16,14 +16,13 @@
 // Denormals: fp64 and fp32 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstddef>
 #include <cstdint>
-#include <cstdio>
 #include <string>
 #include <vector>
 
 #include "fmd_audmon_design.h"
+#include "fmd_side.h"
 #include "fmdemod.h"
 
 using fmd::AudmonGate;
@@ -237,33 +236,24 @@ __global__ __launch_bounds__(kT) void k_audmon_set(int c0, int cn, AudmonGate g,
 }  // namespace
 
 struct fmd_audmon_s {
-    int device = 0, C = 0, fs = 0, M = 0;
+    int C = 0, fs = 0, M = 0;
     long long max_in = 0;
     std::vector<fmd_audmon_params> params;   // [C], as set
     fmd_audmon_status* d_status = nullptr;   // [C]
     AudmonGate* d_gate = nullptr;            // [C]
     double* d_part = nullptr;                // [C][3][64]
     float* d_carry = nullptr;                // [C][2]
-    hipEvent_t done = nullptr;               // end of the previous call's work
-    bool have_done = false;
+    fmd::CallOrder order;                    // behind the previous call's work, for callers that change streams between calls
     std::string err;
 };
 
-static int am_fail(fmd_audmon a, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    if (a) a->err = buf; else fmd::audmon_global_error() = buf;
-    return code;
-}
-
-static bool am_quiesce(fmd_audmon a) {
-    return hipSetDevice(a->device) == hipSuccess && (!a->have_done || hipEventSynchronize(a->done) == hipSuccess);
-}
+template <typename... A>
+static int am_fail(fmd_audmon a, int code, const char* fmt, A... args) { return fmd::fail(a ? a->err : fmd::audmon_global_error(), code, fmt, args...); }
 
 static int am_reset(fmd_audmon a, int channel, int peaks) {
     if (!a) return FMD_ERR_ARG;
     if (channel < -1 || channel >= a->C) return am_fail(a, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, a->C);
-    if (!am_quiesce(a)) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
+    if (!a->order.quiesce()) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
     const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? a->C : 1;
     hipLaunchKernelGGL(k_audmon_reset, dim3((unsigned)cn), dim3(kT), 0, nullptr, c0, peaks, a->d_status, a->d_part, a->d_carry);
     if (hipGetLastError() != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "k_audmon_reset launch failed");
@@ -283,17 +273,16 @@ int fmd_audmon_create(const fmd_audmon_config* cfg, fmd_audmon* out) {
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return am_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
     fmd_audmon a = new fmd_audmon_s();
-    a->device = dev; a->C = cfg->n_channels; a->fs = cfg->fs; a->M = M; a->max_in = cfg->max_input_frames;
+    a->C = cfg->n_channels; a->fs = cfg->fs; a->M = M; a->max_in = cfg->max_input_frames;
     fmd_audmon_params p{};
     fmd_audmon_default_params(&p);
     a->params.assign((size_t)a->C, p);
     const size_t C = (size_t)a->C;
-    bool ok = hipSetDevice(dev) == hipSuccess;
+    bool ok = a->order.init(dev);
     ok = ok && hipMalloc(&a->d_status, sizeof(fmd_audmon_status) * C) == hipSuccess;
     ok = ok && hipMalloc(&a->d_gate, sizeof(AudmonGate) * C) == hipSuccess;
     ok = ok && hipMalloc(&a->d_part, sizeof(double) * kPartD * C) == hipSuccess;
     ok = ok && hipMalloc(&a->d_carry, sizeof(float) * 2 * C) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&a->done, hipEventDisableTiming) == hipSuccess;
     // (the reset first: set_params reads the record's flags)
     if (!ok || fmd_audmon_reset(a, -1) != FMD_OK || fmd_audmon_set_params(a, -1, &p) != FMD_OK) {
         fmd_audmon_destroy(a);
@@ -305,10 +294,9 @@ int fmd_audmon_create(const fmd_audmon_config* cfg, fmd_audmon* out) {
 
 int fmd_audmon_destroy(fmd_audmon a) {
     if (!a) return FMD_ERR_ARG;
-    (void)am_quiesce(a);
+    (void)a->order.quiesce();
     for (void* p : {(void*)a->d_status, (void*)a->d_gate, (void*)a->d_part, (void*)a->d_carry})
         if (p) (void)hipFree(p);
-    if (a->done) (void)hipEventDestroy(a->done);
     delete a;
     return FMD_OK;
 }
@@ -322,7 +310,7 @@ int fmd_audmon_set_params(fmd_audmon a, int channel, const fmd_audmon_params* p)
     if (channel < -1 || channel >= a->C) return am_fail(a, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, a->C);
     AudmonGate g;
     if (fmd::audmon_gate(p, a->M, &g, &a->err) != FMD_OK) return FMD_ERR_ARG;
-    if (!am_quiesce(a)) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
+    if (!a->order.quiesce()) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
     const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? a->C : 1;
     hipLaunchKernelGGL(k_audmon_set, dim3((unsigned)((cn + kT - 1) / kT)), dim3(kT), 0, nullptr, c0, cn, g, a->d_gate, a->d_status);
     if (hipGetLastError() != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "k_audmon_set launch failed");
@@ -346,20 +334,18 @@ int fmd_audmon_process_f32_dev(fmd_audmon a, const float* d_in, long long in_str
         return am_fail(a, FMD_ERR_ARG, "n %lld outside [0, in_stride %lld] or above max_input_frames %lld", n, in_stride, a->max_in);
     if (n == 0 && !d_flags && !d_ok) return FMD_OK;                          // nothing of any station changes and there is no byte to write
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(a->device) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "hipSetDevice failed");
     // every station's state carries over from call to call: a caller that switches streams is ordered behind the previous call
-    if (a->have_done && hipStreamWaitEvent(s, a->done, 0) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "stream wait failed");
+    if (const char* e = a->order.begin(s)) return am_fail(a, FMD_ERR_DEVICE, "%s", e);
     hipLaunchKernelGGL(k_audmon, dim3((unsigned)a->C), dim3(kT), 0, s, reinterpret_cast<const float2*>(d_in), in_stride, n, d_active, a->M, a->d_gate,
                        a->d_status, a->d_part, a->d_carry, d_flags, d_ok);
     if (hipGetLastError() != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "k_audmon launch failed");
-    if (hipEventRecord(a->done, s) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "event record failed");
-    a->have_done = true;
+    if (const char* e = a->order.end(s)) return am_fail(a, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 
 int fmd_audmon_get_status(fmd_audmon a, fmd_audmon_status* out) {
     if (!a || !out) return am_fail(a, FMD_ERR_ARG, "null monitor or output");
-    if (!am_quiesce(a)) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
+    if (!a->order.quiesce()) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemcpy(out, a->d_status, sizeof(fmd_audmon_status) * (size_t)a->C, hipMemcpyDeviceToHost) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "copy failed");
     return FMD_OK;
 }

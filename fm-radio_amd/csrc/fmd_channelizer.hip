@@ -30,8 +30,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
@@ -41,6 +39,7 @@
 
 #include "fmdemod.h"
 #include "fmd_iq.h"
+#include "fmd_side.h"
 
 namespace {
 
@@ -452,7 +451,6 @@ thread_local std::string g_chan_error;
 }  // namespace
 
 struct fmd_channelizer_s {
-    int device = 0;
     int L = 0, M = 0, T = 0, C = 0;
     double fs_in = 0, fs_out = 0;
     size_t max_in = 0;
@@ -460,8 +458,7 @@ struct fmd_channelizer_s {
     unsigned long long o_abs = 0;     // absolute index of the next output sample
     float2* win[2] = {nullptr, nullptr};   // [T - 1] history samples each, ping-pong: a launch reads one and writes the next call's into the other
     int cur = 0;                      // window the next call stages into (its first T-1 samples hold the history)
-    hipEvent_t done = nullptr;        // end of the previous call's work, for callers that change streams between calls
-    bool have_done = false;
+    fmd::CallOrder order;             // behind the previous call's work, for callers that change streams between calls
     float* taps = nullptr;            // [T][L]
     float* atab = nullptr;            // k_channelize16_mfma's operand A, per wavefront, K-step and lane; null: that form does not apply
     float* hrev = nullptr;            // k_channelize_band_mfma's prototype, [L][T] with each phase reversed; null: that form does not apply
@@ -473,12 +470,8 @@ struct fmd_channelizer_s {
     std::string err;
 };
 
-static int chan_fail(fmd_channelizer h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    if (h) h->err = buf; else g_chan_error = buf;
-    return code;
-}
+template <typename... A>
+static int chan_fail(fmd_channelizer h, int code, const char* fmt, A... args) { return fmd::fail(h ? h->err : g_chan_error, code, fmt, args...); }
 
 // k_channelize_band_mfma's tile for this configuration: the most groups (8, 4, 2) whose rails and prototype fit kBandLds; G = 0: none does
 static BandPlan band_plan(int L, int M, int T) {
@@ -578,7 +571,7 @@ int fmd_chan_create(const fmd_chan_config* cfg, fmd_channelizer* out) {
         if ((long long)tile * M / L + T + 2 > kMaxWindow) return chan_fail(nullptr, FMD_ERR_ARG, "decimation %d/%d with %d taps per phase needs a staging window over %d samples", M, L, T, kMaxWindow);
     }
     fmd_channelizer h = new fmd_channelizer_s();
-    h->device = dev; h->L = L; h->M = M; h->T = T; h->C = cfg->n_stations; h->fs_in = cfg->fs_in; h->fs_out = cfg->fs_out;
+    h->L = L; h->M = M; h->T = T; h->C = cfg->n_stations; h->fs_in = cfg->fs_in; h->fs_out = cfg->fs_out;
     h->legacy = legacy; h->tile = tile; h->band = bp;
     h->max_in = (size_t)cfg->max_input_samples;
     h->h_taps.resize((size_t)T * L);
@@ -590,9 +583,8 @@ int fmd_chan_create(const fmd_chan_config* cfg, fmd_channelizer* out) {
         fr -= std::floor(fr);                                       // [0, 1) turns per sample
         inc[k] = (unsigned long long)std::llround(std::ldexp(fr, 63)) << 1;   // fr * 2^64, even
     }
-    bool ok = hipSetDevice(dev) == hipSuccess;
+    bool ok = h->order.init(dev);
     for (int i = 0; i < 2; i++) ok = ok && hipMalloc(&h->win[i], sizeof(float2) * (size_t)T) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&h->done, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipMalloc(&h->taps, sizeof(float) * h->h_taps.size()) == hipSuccess;
     ok = ok && hipMalloc(&h->inc, sizeof(unsigned long long) * h->C) == hipSuccess;
     for (int i = 0; i < 2; i++) ok = ok && hipMemset(h->win[i], 0, sizeof(float2) * (size_t)T) == hipSuccess;
@@ -627,9 +619,8 @@ int fmd_chan_create(const fmd_chan_config* cfg, fmd_channelizer* out) {
 
 int fmd_chan_destroy(fmd_channelizer h) {
     if (!h) return FMD_ERR_ARG;
-    (void)hipSetDevice(h->device);
+    (void)hipSetDevice(h->order.device());
     for (int i = 0; i < 2; i++) if (h->win[i]) (void)hipFree(h->win[i]);
-    if (h->done) (void)hipEventDestroy(h->done);
     if (h->taps) (void)hipFree(h->taps);
     if (h->atab) (void)hipFree(h->atab);
     if (h->hrev) (void)hipFree(h->hrev);
@@ -655,10 +646,10 @@ int fmd_chan_get_taps(fmd_channelizer h, float* taps, size_t cap_floats) {
 
 int fmd_chan_reset(fmd_channelizer h) {
     if (!h) return FMD_ERR_ARG;
-    if (hipSetDevice(h->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "synchronise failed");
+    if (hipSetDevice(h->order.device()) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "synchronise failed");
     for (int i = 0; i < 2; i++)
         if (hipMemset(h->win[i], 0, sizeof(float2) * (size_t)h->T) != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "memset failed");
-    h->n_abs = 0; h->o_abs = 0; h->cur = 0; h->have_done = false;
+    h->n_abs = 0; h->o_abs = 0; h->cur = 0; h->order.forget();
     return FMD_OK;
 }
 
@@ -673,10 +664,9 @@ static int chan_process(fmd_channelizer h, const void* d_wide, size_t n_in, floa
     const size_t no = n_in * (size_t)h->L / (size_t)h->M;
     if (no > out_capacity_per_station) return chan_fail(h, FMD_ERR_SIZE, "output capacity %zu < %zu", out_capacity_per_station, no);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(h->device) != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "hipSetDevice failed");
-    const int T = h->T;
     // the windows carry state from call to call: a caller that switches streams is ordered behind the previous call's work
-    if (h->have_done && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "stream wait failed");
+    if (const char* e = h->order.begin(s)) return chan_fail(h, FMD_ERR_DEVICE, "%s", e);
+    const int T = h->T;
     // window = [T-1 history samples][this block], read in place; its first sample has absolute input index n_abs - (T-1)
     const ChanWin<S> win{h->win[h->cur], static_cast<const typename Iq<S>::raw*>(d_wide), h->win[h->cur ^ 1]};
     ChanDims d{h->L, h->M, T, h->C, (long long)no, (long long)out_capacity_per_station, h->o_abs, h->n_abs - (unsigned long long)(T - 1), (long long)n_in, h->tile};
@@ -709,8 +699,7 @@ static int chan_process(fmd_channelizer h, const void* d_wide, size_t n_in, floa
     if (hipGetLastError() != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "k_channelize launch failed");
     // (the last T-1 samples of [history ++ block] are the next call's history: the launch's first workgroup has written them into the
     //  OTHER history buffer, however short the block is — n_in = 625 < T - 1 = 639 is a legal call)
-    if (hipEventRecord(h->done, s) != hipSuccess) return chan_fail(h, FMD_ERR_DEVICE, "event record failed");
-    h->have_done = true;
+    if (const char* e = h->order.end(s)) return chan_fail(h, FMD_ERR_DEVICE, "%s", e);
     h->cur ^= 1;
     h->n_abs += n_in; h->o_abs += no;
     *n_out = no;

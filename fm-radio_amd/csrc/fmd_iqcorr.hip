@@ -17,13 +17,12 @@
 //     run the five chains).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <string>
 
 #include "fmd_iq.h"
 #include "fmd_iqcorr_design.h"
+#include "fmd_side.h"
 #include "fmdemod.h"
 
 using fmd::Iq;
@@ -169,7 +168,6 @@ template <typename S> bool set_lds() {
 }  // namespace
 
 struct fmd_iqcorr_s {
-    int device = 0;
     long long max_in = 0;
     unsigned long long n_abs = 0;      // samples since create / reset: the absolute index of the next one
     fmd_iq_correction corr{0.f, 0.f, 0.f, 0.f};
@@ -177,21 +175,12 @@ struct fmd_iqcorr_s {
     double* open[2] = {nullptr, nullptr};   // [5][256] each, ping-pong: a launch reads the open chunk's partials from one and writes the
     int cur = 0;                       // next call's into the other; open[cur] is valid while n_abs is no multiple of 4096
     double* sums = nullptr;            // [max_in / 4096 + 2][5] scratch: the chunk sums of one call
-    hipEvent_t done = nullptr;         // end of the previous call's work, for callers that change streams between calls
-    bool have_done = false;
+    fmd::CallOrder order;              // behind the previous call's work, for callers that change streams between calls
     std::string err;
 };
 
-static int iq_fail(fmd_iqcorr h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    if (h) h->err = buf; else fmd::iqcorr_global_error() = buf;
-    return code;
-}
-
-static bool iq_quiesce(fmd_iqcorr h) {
-    return hipSetDevice(h->device) == hipSuccess && (!h->have_done || hipEventSynchronize(h->done) == hipSuccess);
-}
+template <typename... A>
+static int iq_fail(fmd_iqcorr h, int code, const char* fmt, A... args) { return fmd::fail(h ? h->err : fmd::iqcorr_global_error(), code, fmt, args...); }
 
 template <typename S>
 static int iq_process(fmd_iqcorr h, const void* d_in, long long n_in, float* d_out, void* stream) {
@@ -203,9 +192,8 @@ static int iq_process(fmd_iqcorr h, const void* d_in, long long n_in, float* d_o
     const uintptr_t pi = reinterpret_cast<uintptr_t>(d_in), po = reinterpret_cast<uintptr_t>(d_out);
     if (pi % sizeof(raw_t) != 0 || po % sizeof(float2) != 0) return iq_fail(h, FMD_ERR_ARG, "d_in is not aligned to an I / Q pair or d_out not to 8 bytes");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(h->device) != hipSuccess) return iq_fail(h, FMD_ERR_DEVICE, "hipSetDevice failed");
     // the totals, the open chunk and the scratch row carry over from call to call: a caller that switches streams is ordered behind the previous call
-    if (h->have_done && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) return iq_fail(h, FMD_ERR_DEVICE, "stream wait failed");
+    if (const char* e = h->order.begin(s)) return iq_fail(h, FMD_ERR_DEVICE, "%s", e);
     const unsigned long long a = h->n_abs, end = a + (unsigned long long)n_in;
     const long long c0 = (long long)(a / kIqChunk), c1 = (long long)((end - 1) / kIqChunk);
     const int touched = (int)(c1 - c0 + 1), closed = (int)((long long)(end / kIqChunk) - c0);
@@ -219,8 +207,7 @@ static int iq_process(fmd_iqcorr h, const void* d_in, long long n_in, float* d_o
         hipLaunchKernelGGL(k_iqcorr_fold, dim3(1), dim3(kT), 0, s, h->sums, closed, h->total);
         if (hipGetLastError() != hipSuccess) return iq_fail(h, FMD_ERR_DEVICE, "k_iqcorr_fold launch failed");
     }
-    if (hipEventRecord(h->done, s) != hipSuccess) return iq_fail(h, FMD_ERR_DEVICE, "event record failed");
-    h->have_done = true;
+    if (const char* e = h->order.end(s)) return iq_fail(h, FMD_ERR_DEVICE, "%s", e);
     h->cur ^= 1;
     h->n_abs = end;
     return FMD_OK;
@@ -236,13 +223,12 @@ int fmd_iqcorr_create(const fmd_iqcorr_config* cfg, fmd_iqcorr* out) {
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return iq_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
     fmd_iqcorr h = new fmd_iqcorr_s();
-    h->device = dev; h->max_in = cfg->max_input_samples;
+    h->max_in = cfg->max_input_samples;
     const size_t rows = (size_t)(h->max_in / kIqChunk) + 2;
-    bool ok = hipSetDevice(dev) == hipSuccess;
+    bool ok = h->order.init(dev);
     ok = ok && hipMalloc(&h->total, sizeof(double) * kIqMoments) == hipSuccess;
     for (int i = 0; i < 2; i++) ok = ok && hipMalloc(&h->open[i], sizeof(double) * kIqMoments * kIqLanes) == hipSuccess;
     ok = ok && hipMalloc(&h->sums, sizeof(double) * kIqMoments * rows) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&h->done, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipMemset(h->total, 0, sizeof(double) * kIqMoments) == hipSuccess;
     ok = ok && set_lds<float2>() && set_lds<uint8_t>() && set_lds<int8_t>() && set_lds<int16_t>();
     if (!ok) { fmd_iqcorr_destroy(h); return iq_fail(nullptr, FMD_ERR_DEVICE, "device allocation failed"); }
@@ -252,18 +238,17 @@ int fmd_iqcorr_create(const fmd_iqcorr_config* cfg, fmd_iqcorr* out) {
 
 int fmd_iqcorr_destroy(fmd_iqcorr h) {
     if (!h) return FMD_ERR_ARG;
-    (void)iq_quiesce(h);
+    (void)h->order.quiesce();
     if (h->total) (void)hipFree(h->total);
     for (int i = 0; i < 2; i++) if (h->open[i]) (void)hipFree(h->open[i]);
     if (h->sums) (void)hipFree(h->sums);
-    if (h->done) (void)hipEventDestroy(h->done);
     delete h;
     return FMD_OK;
 }
 
 int fmd_iqcorr_reset_moments(fmd_iqcorr h) {
     if (!h) return FMD_ERR_ARG;
-    if (!iq_quiesce(h)) return iq_fail(h, FMD_ERR_DEVICE, "synchronise failed");
+    if (!h->order.quiesce()) return iq_fail(h, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemset(h->total, 0, sizeof(double) * kIqMoments) != hipSuccess) return iq_fail(h, FMD_ERR_DEVICE, "memset failed");
     h->n_abs = 0;
     return FMD_OK;
@@ -291,7 +276,7 @@ int fmd_iqcorr_process_s16_dev(fmd_iqcorr h, const int16_t* d_in, long long n_in
 
 int fmd_iqcorr_get_moments(fmd_iqcorr h, fmd_iq_moments* out) {
     if (!h || !out) return iq_fail(h, FMD_ERR_ARG, "null corrector or output");
-    if (!iq_quiesce(h)) return iq_fail(h, FMD_ERR_DEVICE, "synchronise failed");
+    if (!h->order.quiesce()) return iq_fail(h, FMD_ERR_DEVICE, "synchronise failed");
     double t[kIqMoments];
     if (hipMemcpy(t, h->total, sizeof(t), hipMemcpyDeviceToHost) != hipSuccess) return iq_fail(h, FMD_ERR_DEVICE, "copy failed");
     if (h->n_abs % kIqChunk != 0) {            // the open chunk: its tree on a copy, the device's partials stay as they are

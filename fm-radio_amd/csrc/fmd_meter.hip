@@ -20,13 +20,12 @@
 // Denormals: fp64 and fp32 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstddef>
 #include <cstdint>
-#include <cstdio>
 #include <string>
 
 #include "fmd_meter_design.h"
+#include "fmd_side.h"
 #include "fmdemod.h"
 
 using fmd::kMeterBins;
@@ -338,7 +337,7 @@ __global__ __launch_bounds__(kTpT) void k_meter_tp(const float* __restrict__ in,
 }  // namespace
 
 struct fmd_meter_s {
-    int device = 0, C = 0, fs = 0;
+    int C = 0, fs = 0;
     long long max_in = 0;
     fmd_meter_design_t design{};
     MeterCoef coef{};
@@ -352,21 +351,12 @@ struct fmd_meter_s {
     fmd_meter_r128_status* d_r128 = nullptr;   // [C], with either feature
     float* d_tphist = nullptr;              // [C][2][11], with FMD_METER_TRUE_PEAK
     unsigned* d_range = nullptr;            // [C][1000], with FMD_METER_RANGE
-    hipEvent_t done = nullptr;              // end of the previous call's work
-    bool have_done = false;
+    fmd::CallOrder order;                   // behind the previous call's work, for callers that change streams between calls
     std::string err;
 };
 
-static int mt_fail(fmd_meter m, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    if (m) m->err = buf; else fmd::meter_global_error() = buf;
-    return code;
-}
-
-static bool mt_quiesce(fmd_meter m) {
-    return hipSetDevice(m->device) == hipSuccess && (!m->have_done || hipEventSynchronize(m->done) == hipSuccess);
-}
+template <typename... A>
+static int mt_fail(fmd_meter m, int code, const char* fmt, A... args) { return fmd::fail(m ? m->err : fmd::meter_global_error(), code, fmt, args...); }
 
 extern "C" {
 
@@ -385,7 +375,7 @@ int fmd_meter_create_ex(const fmd_meter_config* cfg, unsigned features, fmd_mete
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return mt_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
     fmd_meter m = new fmd_meter_s();
-    m->device = dev; m->C = cfg->n_channels; m->fs = cfg->fs; m->max_in = cfg->max_input_frames;
+    m->C = cfg->n_channels; m->fs = cfg->fs; m->max_in = cfg->max_input_frames;
     m->design = d;
     m->features = features;
     m->tp = tp;
@@ -394,7 +384,7 @@ int fmd_meter_create_ex(const fmd_meter_config* cfg, unsigned features, fmd_mete
     m->coef = MeterCoef{d.pre_b[0], d.pre_b[1], d.pre_b[2], -d.pre_a[1], -d.pre_a[2], d.rlb_b[0], d.rlb_b[1], d.rlb_b[2], -d.rlb_a[1], -d.rlb_a[2],
                         (double)d.frames_per_subblock, d.frames_per_subblock};
     const size_t C = (size_t)m->C;
-    bool ok = hipSetDevice(dev) == hipSuccess;
+    bool ok = m->order.init(dev);
     ok = ok && hipMalloc(&m->d_status, sizeof(fmd_meter_status) * C) == hipSuccess;
     ok = ok && hipMalloc(&m->d_carry, sizeof(double) * 2 * kCarry * C) == hipSuccess;
     ok = ok && hipMalloc(&m->d_hist, sizeof(unsigned) * kMeterBins * C) == hipSuccess;
@@ -402,7 +392,6 @@ int fmd_meter_create_ex(const fmd_meter_config* cfg, unsigned features, fmd_mete
     if (features) ok = ok && hipMalloc(&m->d_r128, sizeof(fmd_meter_r128_status) * C) == hipSuccess;
     if (features & FMD_METER_TRUE_PEAK) ok = ok && hipMalloc(&m->d_tphist, sizeof(float) * 2 * kTpH * C) == hipSuccess;
     if (features & FMD_METER_RANGE) ok = ok && hipMalloc(&m->d_range, sizeof(unsigned) * kMeterBins * C) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&m->done, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipMemcpy(m->d_edge, d.edge, sizeof(double) * (kMeterBins + 1), hipMemcpyHostToDevice) == hipSuccess;
     if (!ok || fmd_meter_reset(m, -1) != FMD_OK) { fmd_meter_destroy(m); return mt_fail(nullptr, FMD_ERR_DEVICE, "device allocation failed"); }
     *out = m;
@@ -411,10 +400,9 @@ int fmd_meter_create_ex(const fmd_meter_config* cfg, unsigned features, fmd_mete
 
 int fmd_meter_destroy(fmd_meter m) {
     if (!m) return FMD_ERR_ARG;
-    (void)mt_quiesce(m);
+    (void)m->order.quiesce();
     for (void* p : {(void*)m->d_status, (void*)m->d_carry, (void*)m->d_hist, (void*)m->d_edge, (void*)m->d_r128, (void*)m->d_tphist, (void*)m->d_range})
         if (p) (void)hipFree(p);
-    if (m->done) (void)hipEventDestroy(m->done);
     delete m;
     return FMD_OK;
 }
@@ -422,7 +410,7 @@ int fmd_meter_destroy(fmd_meter m) {
 int fmd_meter_reset(fmd_meter m, int channel) {
     if (!m) return FMD_ERR_ARG;
     if (channel < -1 || channel >= m->C) return mt_fail(m, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, m->C);
-    if (!mt_quiesce(m)) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (!m->order.quiesce()) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
     const size_t c0 = channel < 0 ? 0 : (size_t)channel, cn = channel < 0 ? (size_t)m->C : 1;
     if (hipMemset(m->d_status + c0, 0, sizeof(fmd_meter_status) * cn) != hipSuccess ||
         hipMemset(m->d_carry + c0 * 2 * kCarry, 0, sizeof(double) * 2 * kCarry * cn) != hipSuccess ||
@@ -438,7 +426,7 @@ int fmd_meter_reset(fmd_meter m, int channel) {
 int fmd_meter_reset_peaks(fmd_meter m, int channel) {
     if (!m) return FMD_ERR_ARG;
     if (channel < -1 || channel >= m->C) return mt_fail(m, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, m->C);
-    if (!mt_quiesce(m)) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (!m->order.quiesce()) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
     const size_t c0 = channel < 0 ? 0 : (size_t)channel, cn = channel < 0 ? (size_t)m->C : 1;
     char* p = reinterpret_cast<char*>(m->d_status + c0) + offsetof(fmd_meter_status, peak_call);
     if (hipMemset2D(p, sizeof(fmd_meter_status), 0, 4 * sizeof(float), cn) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "memset failed");
@@ -455,9 +443,8 @@ int fmd_meter_process_f32_dev(fmd_meter m, const float* d_in, long long in_strid
     if (n < 0 || n > in_stride || n > m->max_in)
         return mt_fail(m, FMD_ERR_ARG, "n %lld outside [0, in_stride %lld] or above max_input_frames %lld", n, in_stride, m->max_in);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(m->device) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "hipSetDevice failed");
     // every station's state carries over from call to call: a caller that switches streams is ordered behind the previous call
-    if (m->have_done && hipStreamWaitEvent(s, m->done, 0) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "stream wait failed");
+    if (const char* e = m->order.begin(s)) return mt_fail(m, FMD_ERR_DEVICE, "%s", e);
     const dim3 grid((unsigned)((m->C + kCh - 1) / kCh));
     if (m->features & FMD_METER_RANGE)
         hipLaunchKernelGGL(k_meter<true>, grid, dim3(kT), 0, s, d_in, in_stride, n, d_active, m->C, m->coef, m->d_edge, m->d_status, m->d_carry,
@@ -473,21 +460,20 @@ int fmd_meter_process_f32_dev(fmd_meter m, const float* d_in, long long in_strid
         else hipLaunchKernelGGL(k_meter_tp<1>, tgrid, dim3(kTpT), 0, s, d_in, in_stride, n, d_active, m->tp_taps, m->d_r128, m->d_tphist);
         if (hipGetLastError() != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "k_meter_tp launch failed");
     }
-    if (hipEventRecord(m->done, s) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "event record failed");
-    m->have_done = true;
+    if (const char* e = m->order.end(s)) return mt_fail(m, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 
 int fmd_meter_get_status(fmd_meter m, fmd_meter_status* out) {
     if (!m || !out) return mt_fail(m, FMD_ERR_ARG, "null meter or output");
-    if (!mt_quiesce(m)) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (!m->order.quiesce()) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemcpy(out, m->d_status, sizeof(fmd_meter_status) * (size_t)m->C, hipMemcpyDeviceToHost) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "copy failed");
     return FMD_OK;
 }
 
 int fmd_meter_get_histogram(fmd_meter m, unsigned* hist) {
     if (!m || !hist) return mt_fail(m, FMD_ERR_ARG, "null meter or output");
-    if (!mt_quiesce(m)) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (!m->order.quiesce()) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemcpy(hist, m->d_hist, sizeof(unsigned) * kMeterBins * (size_t)m->C, hipMemcpyDeviceToHost) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "copy failed");
     return FMD_OK;
 }
@@ -507,7 +493,7 @@ int fmd_meter_features(fmd_meter m, unsigned* features) {
 int fmd_meter_get_r128_status(fmd_meter m, fmd_meter_r128_status* out) {
     if (!m || !out) return mt_fail(m, FMD_ERR_ARG, "null meter or output");
     if (!m->features) return mt_fail(m, FMD_ERR_STATE, "the meter was created without FMD_METER_TRUE_PEAK or FMD_METER_RANGE");
-    if (!mt_quiesce(m)) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (!m->order.quiesce()) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemcpy(out, m->d_r128, sizeof(fmd_meter_r128_status) * (size_t)m->C, hipMemcpyDeviceToHost) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "copy failed");
     return FMD_OK;
 }
@@ -522,7 +508,7 @@ int fmd_meter_r128_status_dev(fmd_meter m, const fmd_meter_r128_status** d_out) 
 int fmd_meter_get_range_histogram(fmd_meter m, unsigned* hist) {
     if (!m || !hist) return mt_fail(m, FMD_ERR_ARG, "null meter or output");
     if (!(m->features & FMD_METER_RANGE)) return mt_fail(m, FMD_ERR_STATE, "the meter was created without FMD_METER_RANGE");
-    if (!mt_quiesce(m)) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (!m->order.quiesce()) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemcpy(hist, m->d_range, sizeof(unsigned) * kMeterBins * (size_t)m->C, hipMemcpyDeviceToHost) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "copy failed");
     return FMD_OK;
 }

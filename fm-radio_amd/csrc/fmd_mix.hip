@@ -19,14 +19,13 @@
 //                 LDS.  The bus's delivering sources are first compacted, in order, into an LDS list.
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstdint>
-#include <cstdio>
 #include <string>
 #include <vector>
 
 #include "fmdemod.h"
 #include "fmd_mix_design.h"
+#include "fmd_side.h"
 
 namespace {
 
@@ -219,7 +218,7 @@ thread_local std::string g_mix_error;
 }  // namespace
 
 struct fmd_mixer_s {
-    int device = 0, C = 0, B = 0;
+    int C = 0, B = 0;
     std::vector<std::vector<int>> sources;     // per bus, registration order
     std::vector<float> gains;
     // device tables, rebuilt from the host state before the next call after a change
@@ -231,21 +230,12 @@ struct fmd_mixer_s {
     // host-destination calls
     float* scratch = nullptr;
     size_t scratch_values = 0;
-    hipEvent_t done = nullptr;                 // end of the previous call's work
-    bool have_done = false;
+    fmd::CallOrder order;                      // behind the previous call's work, for callers that change streams between calls
     std::string err;
 };
 
-static int mx_fail(fmd_mixer m, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    if (m) m->err = buf; else g_mix_error = buf;
-    return code;
-}
-
-static bool mx_quiesce(fmd_mixer m) {
-    return hipSetDevice(m->device) == hipSuccess && (!m->have_done || hipEventSynchronize(m->done) == hipSuccess);
-}
+template <typename... A>
+static int mx_fail(fmd_mixer m, int code, const char* fmt, A... args) { return fmd::fail(m ? m->err : g_mix_error, code, fmt, args...); }
 
 static void mx_free(fmd_mixer m) {
     for (void* p : {(void*)m->d_rows, (void*)m->d_offs, (void*)m->d_small, (void*)m->d_large, (void*)m->d_scales})
@@ -297,13 +287,12 @@ static int mx_process(fmd_mixer m, const float* d_in, long long in_stride, long 
     if (!m) return FMD_ERR_ARG;
     if (!d_in || !d_out) return mx_fail(m, FMD_ERR_ARG, "null input or output");
     if (n < 0 || n > in_stride || out_stride < n) return mx_fail(m, FMD_ERR_ARG, "n %lld outside [0, in_stride %lld] or out_stride %lld < n", n, in_stride, out_stride);
-    if (hipSetDevice(m->device) != hipSuccess) return mx_fail(m, FMD_ERR_DEVICE, "hipSetDevice failed");
+    if (const char* e = m->order.begin(s)) return mx_fail(m, FMD_ERR_DEVICE, "%s", e);
     if (m->dirty) {
-        if (!mx_quiesce(m)) return mx_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+        if (!m->order.quiesce()) return mx_fail(m, FMD_ERR_DEVICE, "synchronise failed");
         const int rc = mx_upload(m, s);
         if (rc != FMD_OK) return rc;
     }
-    if (m->have_done && hipStreamWaitEvent(s, m->done, 0) != hipSuccess) return mx_fail(m, FMD_ERR_DEVICE, "stream wait failed");
     if (n > 0) {
         if (!m->h_small.empty()) {
             const bool pairs = in_stride % 2 == 0 && out_stride % 2 == 0 && reinterpret_cast<uintptr_t>(d_in) % 16 == 0 &&
@@ -325,8 +314,7 @@ static int mx_process(fmd_mixer m, const float* d_in, long long in_stride, long 
         }
         if (hipGetLastError() != hipSuccess) return mx_fail(m, FMD_ERR_DEVICE, "mixer launch failed");
     }
-    if (hipEventRecord(m->done, s) != hipSuccess) return mx_fail(m, FMD_ERR_DEVICE, "event record failed");
-    m->have_done = true;
+    if (const char* e = m->order.end(s)) return mx_fail(m, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 
@@ -344,14 +332,14 @@ int fmd_mixer_create(const fmd_mixer_config* cfg, fmd_mixer* out) {
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return mx_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
     fmd_mixer m = new fmd_mixer_s();
-    m->device = dev; m->C = cfg->n_channels; m->B = cfg->n_buses;
+    m->C = cfg->n_channels; m->B = cfg->n_buses;
     m->sources.resize(m->B);
     m->gains.assign(m->B, 1.0f);
     for (int b = 0; b < m->B; b++) {
         m->sources[b].assign(cfg->bus_sources + cfg->bus_offsets[b], cfg->bus_sources + cfg->bus_offsets[b + 1]);
         if (cfg->gains) m->gains[b] = cfg->gains[b];
     }
-    if (hipSetDevice(dev) != hipSuccess || hipEventCreateWithFlags(&m->done, hipEventDisableTiming) != hipSuccess) {
+    if (!m->order.init(dev)) {
         fmd_mixer_destroy(m);
         return mx_fail(nullptr, FMD_ERR_DEVICE, "device setup failed");
     }
@@ -361,10 +349,9 @@ int fmd_mixer_create(const fmd_mixer_config* cfg, fmd_mixer* out) {
 
 int fmd_mixer_destroy(fmd_mixer m) {
     if (!m) return FMD_ERR_ARG;
-    (void)mx_quiesce(m);
+    (void)m->order.quiesce();
     mx_free(m);
     if (m->scratch) (void)hipFree(m->scratch);
-    if (m->done) (void)hipEventDestroy(m->done);
     delete m;
     return FMD_OK;
 }
@@ -405,7 +392,7 @@ int fmd_mixer_process_f32_host(fmd_mixer m, const float* d_in, long long in_stri
     if (n < 0 || n > in_stride || out_stride < n) return mx_fail(m, FMD_ERR_ARG, "n %lld outside [0, in_stride %lld] or out_stride %lld < n", n, in_stride, out_stride);
     const size_t need = (size_t)m->B * (size_t)(n > 0 ? n : 1) * 2;
     if (need > m->scratch_values) {
-        if (!mx_quiesce(m)) return mx_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+        if (!m->order.quiesce()) return mx_fail(m, FMD_ERR_DEVICE, "synchronise failed");
         if (m->scratch) (void)hipFree(m->scratch);
         m->scratch = nullptr; m->scratch_values = 0;
         if (hipMalloc(&m->scratch, sizeof(float) * need) != hipSuccess) return mx_fail(m, FMD_ERR_DEVICE, "scratch allocation failed");

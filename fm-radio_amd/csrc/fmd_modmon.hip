@@ -18,15 +18,14 @@
 // Denormals: fp64 and fp32 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstddef>
 #include <cstdint>
-#include <cstdio>
 #include <string>
 
 #include "fmd_iq.h"
 #include "fmd_math.h"
 #include "fmd_modmon_design.h"
+#include "fmd_side.h"
 #include "fmdemod.h"
 
 using fmd::kModmonBins;
@@ -259,7 +258,7 @@ __global__ __launch_bounds__(kT) void k_modmon_reset(int c0, int peaks, fmd_modm
 }  // namespace
 
 struct fmd_modmon_s {
-    int device = 0, C = 0, fs = 0;
+    int C = 0, fs = 0;
     long long max_in = 0;
     fmd_modmon_design_t design{};
     MmTaps taps{};
@@ -268,26 +267,17 @@ struct fmd_modmon_s {
     float* d_carry = nullptr;               // [C][36]
     unsigned* d_hist = nullptr;             // [C][300]
     double* d_pilot = nullptr;              // [2][384]
-    hipEvent_t done = nullptr;              // end of the previous call's work
-    bool have_done = false;
+    fmd::CallOrder order;                   // behind the previous call's work, for callers that change streams between calls
     std::string err;
 };
 
-static int mm_fail(fmd_modmon m, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    if (m) m->err = buf; else fmd::modmon_global_error() = buf;
-    return code;
-}
-
-static bool mm_quiesce(fmd_modmon m) {
-    return hipSetDevice(m->device) == hipSuccess && (!m->have_done || hipEventSynchronize(m->done) == hipSuccess);
-}
+template <typename... A>
+static int mm_fail(fmd_modmon m, int code, const char* fmt, A... args) { return fmd::fail(m ? m->err : fmd::modmon_global_error(), code, fmt, args...); }
 
 static int mm_reset(fmd_modmon m, int channel, int peaks) {
     if (!m) return FMD_ERR_ARG;
     if (channel < -1 || channel >= m->C) return mm_fail(m, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, m->C);
-    if (!mm_quiesce(m)) return mm_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (!m->order.quiesce()) return mm_fail(m, FMD_ERR_DEVICE, "synchronise failed");
     const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? m->C : 1;
     hipLaunchKernelGGL(k_modmon_reset, dim3((unsigned)cn), dim3(kT), 0, nullptr, c0, peaks, m->d_status, m->d_part, m->d_carry, m->d_hist);
     if (hipGetLastError() != hipSuccess) return mm_fail(m, FMD_ERR_DEVICE, "k_modmon_reset launch failed");
@@ -303,14 +293,12 @@ static int mm_process(fmd_modmon m, const void* d_in, size_t align, long long in
         return mm_fail(m, FMD_ERR_ARG, "n %lld outside [0, in_stride %lld] or above max_input_samples %lld", n, in_stride, m->max_in);
     if (n == 0) return FMD_OK;                                               // nothing of any station changes
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(m->device) != hipSuccess) return mm_fail(m, FMD_ERR_DEVICE, "hipSetDevice failed");
     // every station's state carries over from call to call: a caller that switches streams is ordered behind the previous call
-    if (m->have_done && hipStreamWaitEvent(s, m->done, 0) != hipSuccess) return mm_fail(m, FMD_ERR_DEVICE, "stream wait failed");
+    if (const char* e = m->order.begin(s)) return mm_fail(m, FMD_ERR_DEVICE, "%s", e);
     hipLaunchKernelGGL(k_modmon<S>, dim3((unsigned)m->C), dim3(kT), 0, s, static_cast<const typename fmd::Iq<S>::raw*>(d_in), in_stride, n, d_active,
                        m->taps, m->design.hz_per_rad, m->design.M, m->design.P, m->d_pilot, m->d_status, m->d_part, m->d_carry, m->d_hist);
     if (hipGetLastError() != hipSuccess) return mm_fail(m, FMD_ERR_DEVICE, "k_modmon launch failed");
-    if (hipEventRecord(m->done, s) != hipSuccess) return mm_fail(m, FMD_ERR_DEVICE, "event record failed");
-    m->have_done = true;
+    if (const char* e = m->order.end(s)) return mm_fail(m, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 
@@ -326,17 +314,16 @@ int fmd_modmon_create(const fmd_modmon_config* cfg, fmd_modmon* out) {
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return mm_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
     fmd_modmon m = new fmd_modmon_s();
-    m->device = dev; m->C = cfg->n_channels; m->fs = cfg->fs; m->max_in = cfg->max_input_samples;
+    m->C = cfg->n_channels; m->fs = cfg->fs; m->max_in = cfg->max_input_samples;
     m->design = d;
     for (int t = 0; t < kModmonTaps; t++) m->taps.h[t] = d.h[t];
     const size_t C = (size_t)m->C;
-    bool ok = hipSetDevice(dev) == hipSuccess;
+    bool ok = m->order.init(dev);
     ok = ok && hipMalloc(&m->d_status, sizeof(fmd_modmon_status) * C) == hipSuccess;
     ok = ok && hipMalloc(&m->d_part, sizeof(double) * kCarryD * C) == hipSuccess;
     ok = ok && hipMalloc(&m->d_carry, sizeof(float) * kCarryF * C) == hipSuccess;
     ok = ok && hipMalloc(&m->d_hist, sizeof(unsigned) * kModmonBins * C) == hipSuccess;
     ok = ok && hipMalloc(&m->d_pilot, sizeof(double) * 2 * kModmonMaxP) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&m->done, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipMemcpy(m->d_pilot, d.pilot_cos, sizeof(double) * kModmonMaxP, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(m->d_pilot + kModmonMaxP, d.pilot_sin, sizeof(double) * kModmonMaxP, hipMemcpyHostToDevice) == hipSuccess;
     if (!ok || fmd_modmon_reset(m, -1) != FMD_OK) { fmd_modmon_destroy(m); return mm_fail(nullptr, FMD_ERR_DEVICE, "device allocation failed"); }
@@ -346,10 +333,9 @@ int fmd_modmon_create(const fmd_modmon_config* cfg, fmd_modmon* out) {
 
 int fmd_modmon_destroy(fmd_modmon m) {
     if (!m) return FMD_ERR_ARG;
-    (void)mm_quiesce(m);
+    (void)m->order.quiesce();
     for (void* p : {(void*)m->d_status, (void*)m->d_part, (void*)m->d_carry, (void*)m->d_hist, (void*)m->d_pilot})
         if (p) (void)hipFree(p);
-    if (m->done) (void)hipEventDestroy(m->done);
     delete m;
     return FMD_OK;
 }
@@ -368,14 +354,14 @@ int fmd_modmon_process_u8_dev(fmd_modmon m, const uint8_t* d_in, long long in_st
 
 int fmd_modmon_get_status(fmd_modmon m, fmd_modmon_status* out) {
     if (!m || !out) return mm_fail(m, FMD_ERR_ARG, "null monitor or output");
-    if (!mm_quiesce(m)) return mm_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (!m->order.quiesce()) return mm_fail(m, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemcpy(out, m->d_status, sizeof(fmd_modmon_status) * (size_t)m->C, hipMemcpyDeviceToHost) != hipSuccess) return mm_fail(m, FMD_ERR_DEVICE, "copy failed");
     return FMD_OK;
 }
 
 int fmd_modmon_get_histogram(fmd_modmon m, unsigned* hist) {
     if (!m || !hist) return mm_fail(m, FMD_ERR_ARG, "null monitor or output");
-    if (!mm_quiesce(m)) return mm_fail(m, FMD_ERR_DEVICE, "synchronise failed");
+    if (!m->order.quiesce()) return mm_fail(m, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemcpy(hist, m->d_hist, sizeof(unsigned) * kModmonBins * (size_t)m->C, hipMemcpyDeviceToHost) != hipSuccess) return mm_fail(m, FMD_ERR_DEVICE, "copy failed");
     return FMD_OK;
 }

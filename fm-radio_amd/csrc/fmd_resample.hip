@@ -13,8 +13,6 @@
 // Outputs are written with non-temporal stores (nothing reads them back on the GPU before the consumer does).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <map>
 #include <string>
@@ -22,6 +20,7 @@
 
 #include "fmdemod.h"
 #include "fmd_resample_design.h"
+#include "fmd_side.h"
 
 namespace {
 
@@ -139,7 +138,6 @@ thread_local std::string g_rs_error;
 }  // namespace
 
 struct fmd_resampler_s {
-    int device = 0;
     int C = 0, fs_in = 0, fs_out = 0, method = 0, T = 0, T_cfg = 0;   // T_cfg: the configuration's taps_per_phase (0 = default)
     long long max_in = 0;
     // polyphase
@@ -154,22 +152,12 @@ struct fmd_resampler_s {
     // host-destination calls
     float2* scratch = nullptr;
     size_t scratch_frames = 0;
-    hipEvent_t done = nullptr;                 // end of the previous call's work, for callers that change streams between calls
-    bool have_done = false;
+    fmd::CallOrder order;                      // behind the previous call's work, for callers that change streams between calls
     std::string err;
 };
 
-static int rs_fail(fmd_resampler r, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    if (r) r->err = buf; else g_rs_error = buf;
-    return code;
-}
-
-// the earlier calls' work is finished (before the host frees or rewrites what they read)
-static bool rs_quiesce(fmd_resampler r) {
-    return hipSetDevice(r->device) == hipSuccess && (!r->have_done || hipEventSynchronize(r->done) == hipSuccess);
-}
+template <typename... A>
+static int rs_fail(fmd_resampler r, int code, const char* fmt, A... args) { return fmd::fail(r ? r->err : g_rs_error, code, fmt, args...); }
 
 static void rs_free_tables(fmd_resampler r) {
     for (auto& kv : r->tables) if (kv.second.dev) (void)hipFree(kv.second.dev);
@@ -233,10 +221,10 @@ static int rs_process(fmd_resampler r, const float* d_in, long long in_stride, l
             if (!fmd::resample_ref_table((int)n_in, (int)no, &t.host))
                 return rs_fail(r, FMD_ERR_ARG, "the reference's index leaves the %lld-frame input before its %lld outputs are made (its span indexing would abort)", n_in, no);
             if (r->tables.size() >= kMaxTables) {
-                if (!rs_quiesce(r)) return rs_fail(r, FMD_ERR_DEVICE, "synchronise failed");
+                if (!r->order.quiesce()) return rs_fail(r, FMD_ERR_DEVICE, "synchronise failed");
                 rs_free_tables(r);
             }
-            if (hipSetDevice(r->device) != hipSuccess || hipMalloc(&t.dev, sizeof(int4) * (size_t)no) != hipSuccess ||
+            if (hipSetDevice(r->order.device()) != hipSuccess || hipMalloc(&t.dev, sizeof(int4) * (size_t)no) != hipSuccess ||
                 hipMemcpy(t.dev, t.host.data(), sizeof(int4) * (size_t)no, hipMemcpyHostToDevice) != hipSuccess) {
                 if (t.dev) (void)hipFree(t.dev);
                 return rs_fail(r, FMD_ERR_DEVICE, "index table upload failed");
@@ -245,8 +233,7 @@ static int rs_process(fmd_resampler r, const float* d_in, long long in_stride, l
         }
         tab = &it->second;
     }
-    if (hipSetDevice(r->device) != hipSuccess) return rs_fail(r, FMD_ERR_DEVICE, "hipSetDevice failed");
-    if (r->have_done && hipStreamWaitEvent(s, r->done, 0) != hipSuccess) return rs_fail(r, FMD_ERR_DEVICE, "stream wait failed");
+    if (const char* e = r->order.begin(s)) return rs_fail(r, FMD_ERR_DEVICE, "%s", e);
     const unsigned gy = (unsigned)((r->C + kStations - 1) / kStations);
     const float2* in = reinterpret_cast<const float2*>(d_in);
     bool launched = false;
@@ -270,8 +257,7 @@ static int rs_process(fmd_resampler r, const float* d_in, long long in_stride, l
         r->cur ^= 1;
     }
     if (launched && hipGetLastError() != hipSuccess) return rs_fail(r, FMD_ERR_DEVICE, "resampler launch failed");
-    if (hipEventRecord(r->done, s) != hipSuccess) return rs_fail(r, FMD_ERR_DEVICE, "event record failed");
-    r->have_done = true;
+    if (const char* e = r->order.end(s)) return rs_fail(r, FMD_ERR_DEVICE, "%s", e);
     if (r->method == FMD_RESAMPLE_POLYPHASE) { r->n_abs += n_in; r->o_abs += no; }
     *n_out = no;
     return FMD_OK;
@@ -300,9 +286,9 @@ int fmd_resampler_create(const fmd_resampler_config* cfg, fmd_resampler* out) {
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return rs_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
     fmd_resampler r = new fmd_resampler_s();
-    r->device = dev; r->C = cfg->n_channels; r->fs_in = cfg->fs_in; r->fs_out = cfg->fs_out; r->method = cfg->method; r->T_cfg = cfg->taps_per_phase;
+    r->C = cfg->n_channels; r->fs_in = cfg->fs_in; r->fs_out = cfg->fs_out; r->method = cfg->method; r->T_cfg = cfg->taps_per_phase;
     r->max_in = cfg->max_input_frames;
-    bool ok = hipSetDevice(dev) == hipSuccess && hipEventCreateWithFlags(&r->done, hipEventDisableTiming) == hipSuccess;
+    bool ok = r->order.init(dev);
     if (ok && r->method == FMD_RESAMPLE_POLYPHASE) {
         {
             const int rc = rs_setup_poly(r);
@@ -316,12 +302,11 @@ int fmd_resampler_create(const fmd_resampler_config* cfg, fmd_resampler* out) {
 
 int fmd_resampler_destroy(fmd_resampler r) {
     if (!r) return FMD_ERR_ARG;
-    (void)rs_quiesce(r);
+    (void)r->order.quiesce();
     rs_free_tables(r);
     for (int i = 0; i < 2; i++) if (r->hist[i]) (void)hipFree(r->hist[i]);
     if (r->taps) (void)hipFree(r->taps);
     if (r->scratch) (void)hipFree(r->scratch);
-    if (r->done) (void)hipEventDestroy(r->done);
     delete r;
     return FMD_OK;
 }
@@ -329,7 +314,7 @@ int fmd_resampler_destroy(fmd_resampler r) {
 int fmd_resampler_reset(fmd_resampler r, int channel) {
     if (!r || channel < -1 || channel >= r->C) return FMD_ERR_ARG;
     if (r->method != FMD_RESAMPLE_POLYPHASE) return FMD_OK;
-    if (!rs_quiesce(r)) return rs_fail(r, FMD_ERR_DEVICE, "synchronise failed");
+    if (!r->order.quiesce()) return rs_fail(r, FMD_ERR_DEVICE, "synchronise failed");
     const size_t row = sizeof(float2) * (size_t)(r->T - 1);
     if (channel < 0) {
         for (int i = 0; i < 2; i++)
@@ -346,7 +331,7 @@ int fmd_resampler_set_input_rate(fmd_resampler r, int fs_in) {
     if (fs_in == r->fs_in) return 0;
     if (r->method == FMD_RESAMPLE_POLYPHASE && fmd_resampler_design(fs_in, r->fs_out, r->T_cfg, nullptr, nullptr, nullptr) != FMD_OK)
         return rs_fail(r, FMD_ERR_ARG, "unsupported polyphase rates %d -> %d", fs_in, r->fs_out);
-    if (!rs_quiesce(r)) return rs_fail(r, FMD_ERR_DEVICE, "synchronise failed");
+    if (!r->order.quiesce()) return rs_fail(r, FMD_ERR_DEVICE, "synchronise failed");
     rs_free_tables(r);
     r->fs_in = fs_in;
     if (r->method == FMD_RESAMPLE_POLYPHASE) {
@@ -380,7 +365,7 @@ int fmd_resampler_process_f32_host(fmd_resampler r, const float* d_in, long long
     if (no > out_stride) return rs_fail(r, FMD_ERR_SIZE, "out_stride %lld < %lld output frames", out_stride, no);
     const size_t need = (size_t)r->C * (size_t)(no > 0 ? no : 1);
     if (need > r->scratch_frames) {
-        if (!rs_quiesce(r)) return rs_fail(r, FMD_ERR_DEVICE, "synchronise failed");
+        if (!r->order.quiesce()) return rs_fail(r, FMD_ERR_DEVICE, "synchronise failed");
         if (r->scratch) (void)hipFree(r->scratch);
         r->scratch = nullptr; r->scratch_frames = 0;
         if (hipMalloc(&r->scratch, sizeof(float2) * need) != hipSuccess) return rs_fail(r, FMD_ERR_DEVICE, "scratch allocation failed");

@@ -18,13 +18,12 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstdio>
 #include <string>
 #include <vector>
 
 #include "fmd_iq.h"
 #include "fmd_scan_design.h"
+#include "fmd_side.h"
 #include "fmdemod.h"
 
 using fmd::Iq;
@@ -203,7 +202,6 @@ static int threads_for(int logn) { return (1 << logn) / 8 < 512 ? (1 << logn) / 
 }  // namespace
 
 struct fmd_scanner_s {
-    int device = 0;
     int N = 0, logn = 0;
     double fs_in = 0;
     double sum_w2 = 0;                 // sum of the fp32 window values squared, in double
@@ -218,17 +216,12 @@ struct fmd_scanner_s {
     float2* tw = nullptr;              // [N] e^{-j 2 pi m / N}
     float* power = nullptr;            // [max_frames][N] scratch: the call's frame powers, fft-shifted
     double* acc = nullptr;             // [N] S, fft-shifted
-    hipEvent_t done = nullptr;         // end of the previous call's work, for callers that change streams between calls
-    bool have_done = false;
+    fmd::CallOrder order;              // behind the previous call's work, for callers that change streams between calls
     std::string err;
 };
 
-static int scan_fail(fmd_scanner h, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    if (h) h->err = buf; else fmd::scan_global_error() = buf;
-    return code;
-}
+template <typename... A>
+static int scan_fail(fmd_scanner h, int code, const char* fmt, A... args) { return fmd::fail(h ? h->err : fmd::scan_global_error(), code, fmt, args...); }
 
 template <typename S> static bool set_lds(int logn) {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(frames_kernel<S>(logn)), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -240,9 +233,8 @@ static int scan_process(fmd_scanner h, const void* d_wide, size_t n_in, void* st
     if (!h || !d_wide) return scan_fail(h, FMD_ERR_ARG, "null scanner or input");
     if (n_in == 0 || n_in > h->max_in) return scan_fail(h, FMD_ERR_SIZE, "n_in %zu outside (0, %zu]", n_in, h->max_in);
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(h->device) != hipSuccess) return scan_fail(h, FMD_ERR_DEVICE, "hipSetDevice failed");
     // the history and the scratch rows carry over from call to call: a caller that switches streams is ordered behind the previous call
-    if (h->have_done && hipStreamWaitEvent(s, h->done, 0) != hipSuccess) return scan_fail(h, FMD_ERR_DEVICE, "stream wait failed");
+    if (const char* e = h->order.begin(s)) return scan_fail(h, FMD_ERR_DEVICE, "%s", e);
     const int N = h->N, H = N / 2;
     const long long W = (long long)h->h_len + (long long)n_in;
     const int frames = W >= N ? (int)((W - N) / H + 1) : 0;
@@ -255,8 +247,7 @@ static int scan_process(fmd_scanner h, const void* d_wide, size_t n_in, void* st
         hipLaunchKernelGGL(k_scan_accumulate, dim3((unsigned)(N / 64)), dim3(64), 0, s, h->power, frames, N, h->acc);
         if (hipGetLastError() != hipSuccess) return scan_fail(h, FMD_ERR_DEVICE, "k_scan_accumulate launch failed");
     }
-    if (hipEventRecord(h->done, s) != hipSuccess) return scan_fail(h, FMD_ERR_DEVICE, "event record failed");
-    h->have_done = true;
+    if (const char* e = h->order.end(s)) return scan_fail(h, FMD_ERR_DEVICE, "%s", e);
     h->cur ^= 1;
     h->n_abs += n_in;
     h->n_frames += frames;
@@ -277,7 +268,7 @@ int fmd_scan_create(const fmd_scan_config* cfg, fmd_scanner* out) {
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return scan_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
     fmd_scanner h = new fmd_scanner_s();
-    h->device = dev; h->N = N; h->fs_in = cfg->fs_in; h->max_in = (size_t)cfg->max_input_samples;
+    h->N = N; h->fs_in = cfg->fs_in; h->max_in = (size_t)cfg->max_input_samples;
     while ((1 << h->logn) < N) h->logn++;
     const long long wmax = (long long)(N - 1) + cfg->max_input_samples;
     h->max_frames = wmax >= N ? (int)((wmax - N) / (N / 2) + 1) : 0;
@@ -289,13 +280,12 @@ int fmd_scan_create(const fmd_scan_config* cfg, fmd_scanner* out) {
         const double a = -2.0 * M_PI * (double)n / (double)N;
         tw[n] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
-    bool ok = hipSetDevice(dev) == hipSuccess;
+    bool ok = h->order.init(dev);
     for (int i = 0; i < 2; i++) ok = ok && hipMalloc(&h->hist[i], sizeof(float2) * (size_t)(N - 1)) == hipSuccess;
     ok = ok && hipMalloc(&h->window, sizeof(float) * N) == hipSuccess;
     ok = ok && hipMalloc(&h->tw, sizeof(float2) * N) == hipSuccess;
     ok = ok && hipMalloc(&h->power, sizeof(float) * (size_t)N * (size_t)(h->max_frames > 0 ? h->max_frames : 1)) == hipSuccess;
     ok = ok && hipMalloc(&h->acc, sizeof(double) * N) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&h->done, hipEventDisableTiming) == hipSuccess;
     ok = ok && hipMemcpy(h->window, win.data(), sizeof(float) * N, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemcpy(h->tw, tw.data(), sizeof(float2) * N, hipMemcpyHostToDevice) == hipSuccess;
     ok = ok && hipMemset(h->acc, 0, sizeof(double) * N) == hipSuccess;
@@ -307,22 +297,19 @@ int fmd_scan_create(const fmd_scan_config* cfg, fmd_scanner* out) {
 
 int fmd_scan_destroy(fmd_scanner h) {
     if (!h) return FMD_ERR_ARG;
-    (void)hipSetDevice(h->device);
-    if (h->have_done) (void)hipEventSynchronize(h->done);
+    (void)h->order.quiesce();
     for (int i = 0; i < 2; i++) if (h->hist[i]) (void)hipFree(h->hist[i]);
     if (h->window) (void)hipFree(h->window);
     if (h->tw) (void)hipFree(h->tw);
     if (h->power) (void)hipFree(h->power);
     if (h->acc) (void)hipFree(h->acc);
-    if (h->done) (void)hipEventDestroy(h->done);
     delete h;
     return FMD_OK;
 }
 
 int fmd_scan_reset(fmd_scanner h) {
     if (!h) return FMD_ERR_ARG;
-    if (hipSetDevice(h->device) != hipSuccess) return scan_fail(h, FMD_ERR_DEVICE, "hipSetDevice failed");
-    if (h->have_done && hipEventSynchronize(h->done) != hipSuccess) return scan_fail(h, FMD_ERR_DEVICE, "synchronise failed");
+    if (!h->order.quiesce()) return scan_fail(h, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemset(h->acc, 0, sizeof(double) * h->N) != hipSuccess) return scan_fail(h, FMD_ERR_DEVICE, "memset failed");
     h->n_abs = 0; h->n_frames = 0; h->h_len = 0; h->cur = 0;
     return FMD_OK;
@@ -344,8 +331,7 @@ int fmd_scan_process_s16_dev(fmd_scanner h, const int16_t* d_wide, size_t n_in, 
 int fmd_scan_get_psd(fmd_scanner h, double* psd, int cap, long long* n_frames) {
     if (!h || !psd) return scan_fail(h, FMD_ERR_ARG, "null scanner or output");
     if (cap < h->N) return scan_fail(h, FMD_ERR_SIZE, "capacity %d < nfft %d", cap, h->N);
-    if (hipSetDevice(h->device) != hipSuccess) return scan_fail(h, FMD_ERR_DEVICE, "hipSetDevice failed");
-    if (h->have_done && hipEventSynchronize(h->done) != hipSuccess) return scan_fail(h, FMD_ERR_DEVICE, "synchronise failed");
+    if (!h->order.quiesce()) return scan_fail(h, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemcpy(psd, h->acc, sizeof(double) * h->N, hipMemcpyDeviceToHost) != hipSuccess) return scan_fail(h, FMD_ERR_DEVICE, "copy failed");
     if (h->n_frames > 0) {
         const double scale = (double)h->n_frames * h->fs_in * h->sum_w2;

@@ -16,14 +16,13 @@
 // Denormals: fp64 and fp32 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
 #include <hip/hip_runtime.h>
 
-#include <cstdarg>
 #include <cstddef>
 #include <cstdint>
-#include <cstdio>
 #include <string>
 #include <vector>
 
 #include "fmd_iq.h"
+#include "fmd_side.h"
 #include "fmd_squelch_design.h"
 #include "fmdemod.h"
 
@@ -230,33 +229,24 @@ __global__ __launch_bounds__(kT) void k_squelch_set(int c0, int cn, SquelchGate 
 }  // namespace
 
 struct fmd_squelch_s {
-    int device = 0, C = 0, fs = 0, M = 0;
+    int C = 0, fs = 0, M = 0;
     long long max_in = 0;
     std::vector<fmd_squelch_params> params;  // [C], as set
     fmd_squelch_status* d_status = nullptr;  // [C]
     SquelchGate* d_gate = nullptr;           // [C]
     double* d_part = nullptr;                // [C][2][256]
     float* d_carry = nullptr;                // [C]
-    hipEvent_t done = nullptr;               // end of the previous call's work
-    bool have_done = false;
+    fmd::CallOrder order;                    // behind the previous call's work
     std::string err;
 };
 
-static int sq_fail(fmd_squelch q, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof(buf), fmt, ap); va_end(ap);
-    if (q) q->err = buf; else fmd::squelch_global_error() = buf;
-    return code;
-}
-
-static bool sq_quiesce(fmd_squelch q) {
-    return hipSetDevice(q->device) == hipSuccess && (!q->have_done || hipEventSynchronize(q->done) == hipSuccess);
-}
+template <typename... A>
+static int sq_fail(fmd_squelch q, int code, const char* fmt, A... args) { return fmd::fail(q ? q->err : fmd::squelch_global_error(), code, fmt, args...); }
 
 static int sq_reset(fmd_squelch q, int channel, int peaks) {
     if (!q) return FMD_ERR_ARG;
     if (channel < -1 || channel >= q->C) return sq_fail(q, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, q->C);
-    if (!sq_quiesce(q)) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
+    if (!q->order.quiesce()) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
     const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? q->C : 1;
     hipLaunchKernelGGL(k_squelch_reset, dim3((unsigned)cn), dim3(kT), 0, nullptr, c0, peaks, q->d_gate, q->d_status, q->d_part, q->d_carry);
     if (hipGetLastError() != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "k_squelch_reset launch failed");
@@ -272,14 +262,11 @@ static int sq_process(fmd_squelch q, const void* d_in, size_t align, long long i
         return sq_fail(q, FMD_ERR_ARG, "n %lld outside [0, in_stride %lld] or above max_input_samples %lld", n, in_stride, q->max_in);
     if (n == 0 && !d_mask) return FMD_OK;                                    // nothing of any station changes and there is no mask to write
     hipStream_t s = static_cast<hipStream_t>(stream);
-    if (hipSetDevice(q->device) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "hipSetDevice failed");
-    // every station's state carries over from call to call: a caller that switches streams is ordered behind the previous call
-    if (q->have_done && hipStreamWaitEvent(s, q->done, 0) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "stream wait failed");
+    if (const char* e = q->order.begin(s)) return sq_fail(q, FMD_ERR_DEVICE, "%s", e);   // every station's state carries over from call to call
     hipLaunchKernelGGL(k_squelch<S>, dim3((unsigned)q->C), dim3(kT), 0, s, static_cast<const typename fmd::Iq<S>::raw*>(d_in), in_stride, n, d_active, q->M,
                        q->d_gate, q->d_status, q->d_part, q->d_carry, d_mask);
     if (hipGetLastError() != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "k_squelch launch failed");
-    if (hipEventRecord(q->done, s) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "event record failed");
-    q->have_done = true;
+    if (const char* e = q->order.end(s)) return sq_fail(q, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 
@@ -295,17 +282,16 @@ int fmd_squelch_create(const fmd_squelch_config* cfg, fmd_squelch* out) {
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return sq_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
     fmd_squelch q = new fmd_squelch_s();
-    q->device = dev; q->C = cfg->n_channels; q->fs = cfg->fs; q->M = M; q->max_in = cfg->max_input_samples;
+    q->C = cfg->n_channels; q->fs = cfg->fs; q->M = M; q->max_in = cfg->max_input_samples;
     fmd_squelch_params p{};
     fmd_squelch_default_params(&p);
     q->params.assign((size_t)q->C, p);
     const size_t C = (size_t)q->C;
-    bool ok = hipSetDevice(dev) == hipSuccess;
+    bool ok = q->order.init(dev);
     ok = ok && hipMalloc(&q->d_status, sizeof(fmd_squelch_status) * C) == hipSuccess;
     ok = ok && hipMalloc(&q->d_gate, sizeof(SquelchGate) * C) == hipSuccess;
     ok = ok && hipMalloc(&q->d_part, sizeof(double) * kPartD * C) == hipSuccess;
     ok = ok && hipMalloc(&q->d_carry, sizeof(float) * C) == hipSuccess;
-    ok = ok && hipEventCreateWithFlags(&q->done, hipEventDisableTiming) == hipSuccess;
     if (!ok || fmd_squelch_set_params(q, -1, &p) != FMD_OK || fmd_squelch_reset(q, -1) != FMD_OK) {
         fmd_squelch_destroy(q);
         return sq_fail(nullptr, FMD_ERR_DEVICE, "device allocation failed");
@@ -316,10 +302,9 @@ int fmd_squelch_create(const fmd_squelch_config* cfg, fmd_squelch* out) {
 
 int fmd_squelch_destroy(fmd_squelch q) {
     if (!q) return FMD_ERR_ARG;
-    (void)sq_quiesce(q);
+    (void)q->order.quiesce();
     for (void* p : {(void*)q->d_status, (void*)q->d_gate, (void*)q->d_part, (void*)q->d_carry})
         if (p) (void)hipFree(p);
-    if (q->done) (void)hipEventDestroy(q->done);
     delete q;
     return FMD_OK;
 }
@@ -333,7 +318,7 @@ int fmd_squelch_set_params(fmd_squelch q, int channel, const fmd_squelch_params*
     if (channel < -1 || channel >= q->C) return sq_fail(q, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, q->C);
     SquelchGate g;
     if (fmd::squelch_gate(p, q->M, &g, &q->err) != FMD_OK) return FMD_ERR_ARG;
-    if (!sq_quiesce(q)) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
+    if (!q->order.quiesce()) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
     const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? q->C : 1;
     hipLaunchKernelGGL(k_squelch_set, dim3((unsigned)((cn + kT - 1) / kT)), dim3(kT), 0, nullptr, c0, cn, g, q->d_gate, q->d_status);
     if (hipGetLastError() != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "k_squelch_set launch failed");
@@ -359,7 +344,7 @@ int fmd_squelch_process_u8_dev(fmd_squelch q, const uint8_t* d_in, long long in_
 
 int fmd_squelch_get_status(fmd_squelch q, fmd_squelch_status* out) {
     if (!q || !out) return sq_fail(q, FMD_ERR_ARG, "null squelch or output");
-    if (!sq_quiesce(q)) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
+    if (!q->order.quiesce()) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
     if (hipMemcpy(out, q->d_status, sizeof(fmd_squelch_status) * (size_t)q->C, hipMemcpyDeviceToHost) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "copy failed");
     return FMD_OK;
 }

@@ -85,6 +85,53 @@ def test_no_gpu_means_loud_failure(pkg):
     assert e.value.status == -4  # FMD_ERR_NO_DEVICE
 
 
+_SIDE_CLASSES = [   # (class, handle attribute, a valid configuration, a bad one and create's message for it)
+    ("Channelizer", "h", (10e6, [0.0]), None, None),       # (checks for a device before its arguments)
+    ("BandScanner", "h", (10_240_000.0,), (10_240_000.0, 100), "nfft 100 is not a power of two in 256 ... 16384"),
+    ("IqCorrector", "h", (), (0,), "max_input_samples 0 outside (0, 2^32]"),
+    ("AudioResampler", "r", (2, 48000), (0, 48000), "bad resampler configuration"),
+    ("AudioMixer", "m", (2, [[0, 1]]), (2, [[0, 5]]), "a bus source lies outside [0, 2)"),
+    ("LoudnessMeter", "m", (2, 48000), (0, 48000), "n_channels 0 is not positive or max_input_frames 65536 outside (0, 2^30]"),
+    ("AudioMonitor", "a", (2, 48000), (0, 48000), "n_channels 0 is not positive or max_input_frames 65536 outside (0, 2^30]"),
+    ("ModulationMonitor", "m", (2, 256000), (0, 256000), "n_channels 0 is not positive or max_input_samples 1048576 outside (0, 2^30]"),
+    ("Squelch", "q", (2, 256000), (0, 256000), "n_channels 0 is not positive or max_input_samples 1048576 outside (0, 2^30]"),
+    ("RDSDecoder", "d", (2,), None, None),
+]
+
+
+def test_side_objects_share_create_and_close(pkg):
+    """The create-or-raise and close path of the nine side classes and RDSDecoder, without a device: status and create's own text in the
+    FmdError, no handle left behind, and close() safe to repeat."""
+    import gc
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("GPU present")
+    def run():
+        for name, attr, good, bad, msg in _SIDE_CLASSES:
+            cls = getattr(pkg.capi, name)
+            for args, status, text in ((good, -4, None), (bad, -1, msg)):
+                if args is None:
+                    continue
+                obj = cls.__new__(cls)
+                with pytest.raises(pkg.FmdError) as e:
+                    obj.__init__(*args)
+                assert e.value.status == status, (name, str(e.value))
+                if text is None:
+                    assert "no gfx950 device" in str(e.value), (name, str(e.value))
+                else:
+                    assert str(e.value) == f"fmdemod status {status}: {text}", (name, str(e.value))
+                assert getattr(obj, attr) is None, name
+                obj.close()
+                obj.close()
+                del obj
+                gc.collect()
+
+    # the library's create messages are per thread: a thread of its own sees none left by the tests before this one
+    from concurrent.futures import ThreadPoolExecutor
+    with ThreadPoolExecutor(1) as pool:
+        pool.submit(run).result()
+
+
 def test_bad_configs_rejected(pkg):
     lib = pkg.load_library()
     h = C.c_void_p()

@@ -94,7 +94,8 @@ def test_kernel_matches_float64_definition_and_streams(pkg):
         st = streams[i & 1]
         with torch.cuda.stream(st):
             big = bigs[i & 1]
-            got = ch.process(xt[i * 625:(i + 1) * 625].contiguous(), out=big, stream=st.cuda_stream)
+            # (the stream as its raw pointer and as the torch.cuda.Stream itself, each form on both streams)
+            got = ch.process(xt[i * 625:(i + 1) * 625].contiguous(), out=big, stream=st if i & 2 else st.cuda_stream)
             assert tuple(got.shape) == (6, 16, 2)
             outs.append(got.clone())
             assert float(big[:, 16:].min()) == 7.0       # nothing written beyond n_out in any row

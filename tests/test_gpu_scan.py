@@ -84,7 +84,7 @@ def test_ragged_calls_and_streams_are_bit_identical(pkg, fs_in, nfft):
     streams = [torch.cuda.Stream(), torch.cuda.Stream()]
     for i, (a, b) in enumerate(zip(cuts[:-1], cuts[1:])):
         st = streams[i & 1]
-        rag.process(xt[a:b], stream=st.cuda_stream)
+        rag.process(xt[a:b], stream=st if i & 2 else st.cuda_stream)   # (the raw pointer and the torch.cuda.Stream itself, each on both streams)
     _, got = rag.psd()
     assert rag.n_frames == one.n_frames == (n - N) // (N // 2) + 1
     assert np.array_equal(_bits(got), _bits(want))
