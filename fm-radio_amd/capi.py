@@ -215,6 +215,23 @@ AUDMON_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("intervals", "<u8"), ("inter
 AUDMON_SILENCE, AUDMON_LEFT_LOST, AUDMON_RIGHT_LOST, AUDMON_ANTIPHASE, AUDMON_MONO = 1, 2, 4, 8, 16
 
 
+class TonedetConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
+
+
+class TonedetParams(C.Structure):
+    """include/fmdemod.h fmd_tonedet_params"""
+    _fields_ = [("freq_hz", C.c_int * 8), ("share_db", C.c_double * 8), ("floor_db", C.c_double), ("raise_intervals", C.c_int * 8),
+                ("clear_intervals", C.c_int * 8), ("alarm_mask", C.c_uint)]
+
+
+# include/fmdemod.h fmd_tonedet_status (2344 bytes)
+TONEDET_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("intervals", "<u8"), ("intervals_flagged", "<u8", (8,)), ("ring_mm", "<f8", (30,)),
+                                 ("ring_pw", "<f8", (8, 30)), ("run", "<u4", (8,)), ("transitions", "<u4", (8,)), ("nonfinite", "<u4"),
+                                 ("freq_hz", "<i4", (8,)), ("flags", "u1"), ("ok", "u1"), ("reserved", "u1", (2,))])
+TONEDET_SLOTS = 8
+
+
 class PlanInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("effective_channels", "pilot_power_rows", "pll_k_adaptive", "pll_chained", "pll_waves", "lmr_inline", "lazy_capable",
                                        "front_lds_pad", "front_big_tile", "extract_auto_pair", "pll_kernel")]
@@ -421,14 +438,23 @@ def load_library():
     L.fmd_audmon_set_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(AudmonParams)]
     L.fmd_audmon_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(AudmonParams)]
     L.fmd_audmon_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fmd_tonedet_default_params.argtypes = [C.POINTER(TonedetParams)]
+    L.fmd_tonedet_default_params.restype = None
+    L.fmd_tonedet_share_db.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.fmd_tonedet_level_db.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double)]
+    L.fmd_tonedet_create.argtypes = [C.POINTER(TonedetConfig), C.POINTER(C.c_void_p)]
+    L.fmd_tonedet_set_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(TonedetParams)]
+    L.fmd_tonedet_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(TonedetParams)]
+    L.fmd_tonedet_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # what every side object declares alike
-    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "rdsdec"):
+    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "rdsdec"):
         getattr(L, f"fmd_{pre}_destroy").argtypes = [C.c_void_p]
         getattr(L, f"fmd_{pre}_last_error").restype = C.c_char_p
         getattr(L, f"fmd_{pre}_last_error").argtypes = [C.c_void_p]
-    for pre in ("meter", "modmon", "squelch", "audmon"):
+    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet"):
         getattr(L, f"fmd_{pre}_reset").argtypes = [C.c_void_p, C.c_int]
-        getattr(L, f"fmd_{pre}_reset_peaks").argtypes = [C.c_void_p, C.c_int]
+        if pre != "tonedet":                                      # (the tone detector holds no peaks)
+            getattr(L, f"fmd_{pre}_reset_peaks").argtypes = [C.c_void_p, C.c_int]
         getattr(L, f"fmd_{pre}_get_status").argtypes = [C.c_void_p, C.c_void_p]
         getattr(L, f"fmd_{pre}_status_dev").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
     L.fmd_last_error.restype = C.c_char_p
@@ -631,7 +657,7 @@ class _Handle:
 
 
 class _Monitor(_Handle):
-    """The four per-station monitors (meter, modmon, squelch, audmon): [C] status records of `_status_dtype` that reset the same way."""
+    """The five per-station monitors (meter, modmon, squelch, audmon, tonedet): [C] status records of `_status_dtype` that reset the same way."""
     _status_dtype = None
 
     def reset(self, channel: int = -1):
@@ -656,7 +682,7 @@ class _Monitor(_Handle):
 
 
 class _Gated(_Monitor):
-    """The monitors with per-station parameters (squelch, audmon): a ctypes structure `_params_type` read and set by field name."""
+    """The monitors with per-station parameters (squelch, audmon, tonedet): a ctypes structure `_params_type` read and set by field name."""
     _params_type = None
 
     def _field(self, name: str, value):
@@ -1716,4 +1742,61 @@ class AudioMonitor(_Gated):
         """raise_intervals and clear_intervals take five values or one for all five"""
         if name in ("raise_intervals", "clear_intervals"):
             return (C.c_int * 5)(*([int(value)] * 5 if np.isscalar(value) else [int(a) for a in value]))
+        return value
+
+
+def tonedet_default_params() -> TonedetParams:
+    """fmd_tonedet_default_params: slots at 1000, 440, 400, 853, 960 and 1050 Hz and two unused; a tone present within 3 dB of the mid
+    signal's power (6 dB for the EAS pair, which shares it); a floor of -50 dB; 20 intervals to raise and 5 to clear; alarm_mask 0 (a tone
+    is an indication until the user makes it an alarm)"""
+    p = TonedetParams()
+    load_library().fmd_tonedet_default_params(C.byref(p))
+    return p
+
+
+def tonedet_share_db(record, fs: int, slot: int, window: int = 1) -> float:
+    """fmd_tonedet_share_db of one TONEDET_STATUS_DTYPE record: the power of slot `slot`'s tone over the mid signal's power over the newest
+    `window` (1 ... 30) intervals in dB, 0 for a pure sine at the slot's frequency (FMD_ERR_STATE while fewer intervals are complete)"""
+    return _record_read("fmd_tonedet", "share_db", record, TONEDET_STATUS_DTYPE, int(fs), int(slot), int(window))
+
+
+def tonedet_level_db(record, fs: int, slot: int, window: int = 1) -> float:
+    """fmd_tonedet_level_db: the mean square of the slot's tone in the mid signal L + R, in dB of full scale 1.0"""
+    return _record_read("fmd_tonedet", "level_db", record, TONEDET_STATUS_DTYPE, int(fs), int(slot), int(window))
+
+
+class ToneDetector(_Gated):
+    """Tone detector of C stations' audio on the GPU (fmd_tonedet_*): per station and 100 ms interval the power of the mid signal L + R at
+    up to eight integer frequencies (a Goertzel bank) against its total power, one hysteresis detector per slot, and two [C] uint8
+    tensors: the flags (bit k: slot k's tone is present) and the ok bytes, which AudioMixer.process(active=...) takes as they are.  Feed
+    it the same [C, n, 2] float32 CUDA tensors as AudioMixer, LoudnessMeter and AudioMonitor; it changes nothing in them.  status()
+    returns TONEDET_STATUS_DTYPE records; tonedet_share_db and tonedet_level_db turn them into dB."""
+    _prefix, _attr, _status_dtype, _params_type = "fmd_tonedet", "t", TONEDET_STATUS_DTYPE, TonedetParams
+
+    def __init__(self, n_channels: int, fs: int, max_input_frames: int = 1 << 16, device: int = -1):
+        cfg = TonedetConfig(int(n_channels), int(fs), int(max_input_frames), device)
+        self._create("create", C.byref(cfg))
+        self.n_channels, self.fs = int(n_channels), int(fs)
+
+    def reset_peaks(self, channel: int = -1):
+        raise AttributeError("the tone detector holds no peaks")
+
+    def process(self, x, n: int | None = None, active=None, flags=None, ok=None, stream=None):
+        """takes the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
+        uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole and keeps its two bytes); flags, ok: the [C] uint8 CUDA
+        tensors to write, None = a new one, False = not written.  Returns (flags, ok), None for one not written.  Asynchronous on
+        `stream` (default: torch's current)."""
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32",), "frames")
+        pa, stream = _active_ptr(active, self.n_channels), _stream_ptr(stream, x.device)
+        flags, pf = _byte_out(flags, "flags", self.n_channels, x.device, stream)
+        ok, po = _byte_out(ok, "ok", self.n_channels, x.device, stream)
+        self._check(self.L.fmd_tonedet_process_f32_dev(self.t, px, in_stride, n, pa, pf, po, C.c_void_p(stream)))
+        return flags, ok
+
+    def _field(self, name: str, value):
+        """freq_hz, share_db, raise_intervals and clear_intervals take eight values or one for all eight"""
+        kinds = {"freq_hz": (C.c_int, int), "raise_intervals": (C.c_int, int), "clear_intervals": (C.c_int, int), "share_db": (C.c_double, float)}
+        if name in kinds:
+            ct, py = kinds[name]
+            return (ct * 8)(*([py(value)] * 8 if np.isscalar(value) else [py(a) for a in value]))
         return value

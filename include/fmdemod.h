@@ -1180,6 +1180,118 @@ int fmd_audmon_get_status(fmd_audmon a, fmd_audmon_status* out);
 int fmd_audmon_status_dev(fmd_audmon a, const fmd_audmon_status** d_status);
 const char* fmd_audmon_last_error(fmd_audmon a);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Audio tone detector (NOT part of the reference): what is on the air when the programme has been replaced by a steady tone -- a line-up
+ * tone left on a transmitter (1 kHz, 440 Hz, 400 Hz), the two-tone EAS attention signal (853 Hz + 960 Hz), the 1050 Hz weather-radio
+ * alert.  A -12 dBFS sine is neither silent nor mono and measures as healthy loudness, so neither the fault monitor nor the loudness
+ * meter sees it.  It reads the device array [C][in_stride][2] f32 (interleaved L, R) that the mixer, the meter and the fault monitor
+ * read, changes nothing in it, measures per station and per 100 ms interval up to eight tone slots -- the power of the mid signal
+ * m = L + R at the slot's frequency (a Goertzel / single-bin DFT sum against a table) over the mid signal's total power -- runs one
+ * hysteresis detector per slot on the device with comparisons only, and writes a [C] uint8 flags byte (bit k: slot k's tone is present)
+ * and a [C] uint8 ok byte per station, which the mixer takes as d_active.
+ * Arithmetic, restated in C by tests/cpp/tonedet_ref.c; NP = 64 partials, RING = 30 intervals (three seconds), NS = 8 slots:
+ *   design      host, double, host libm; fs a multiple of 10 in 8000 ... 48000:
+ *                 M = fs / 10 (frames of a 100 ms interval)
+ *                 tc[j] = cos(2.0 * M_PI * (double)j / (double)fs), ts[j] = sin(2.0 * M_PI * (double)j / (double)fs), j = 0 ... fs - 1:
+ *                 one table per handle, uploaded once (16 bytes an entry, 768 KB at most)
+ *                 min_e = pow(10, floor_db / 10) * (double)M, and +0 for floor_db = -inf
+ *                 c_k   = pow(10, -share_db[k] / 10)
+ *   slot k      an integer frequency f_k in Hz (the resolution is 1 Hz: 853 is no multiple of 10); 0 = unused, else 1 <= f_k and
+ *               2 f_k < fs.  The phase restarts at every interval's start (the power does not depend on it).
+ *   per frame   n counted absolutely in 64 bits since the station's reset; interval g = n / M, r = n - g M.
+ *                 m = (double)L + (double)R                                      (one rounding)
+ *                 idx_k = (f_k * r) mod fs                                       (the product is below 2^31)
+ *               Partial j = (r >> 2) & 63 takes its terms in ascending r, from +0 at the interval's start:
+ *                 mm_j = fma(m, m, mm_j)
+ *                 for every used slot:  re_kj = fma(m, tc[idx_k], re_kj);  im_kj = fma(m, ts[idx_k], im_kj)
+ *               fp32 and fp64 denormals are kept.  An open interval carries its 17 x 64 partials (8.5 KB per station) to the next call.
+ *   interval end  per sum the halving tree p_j += p_{j+w} for j < w, w = 32, 16, ... 1;  S = p_0: MM, RE_k, IM_k.
+ *                 PW_k = fma(RE_k, RE_k, IM_k * IM_k);  an unused slot has PW_k = +0
+ *                 ring_mm[g % 30] = MM, ring_pw[k][g % 30] = PW_k, intervals++
+ *                 MM not finite -> nonfinite++;  usable = isfinite(MM) && MM > min_e
+ *                 present[k] = usable && isfinite(PW_k) && 2.0 * PW_k > c_k * ((double)M * MM)
+ *                 (a pure sine at f_k has 2 PW_k = M MM; an unused slot is never present; an unusable interval carries no tone)
+ *   detector k  (bit k of flags; every detector runs at every interval's end: there is no hold)
+ *               flag clear: run = present ? run + 1 : 0;  run >= raise_intervals[k] -> the flag is set, run = 0, transitions[k]++
+ *               flag set:   run = present ? 0 : run + 1;  run >= clear_intervals[k] -> the flag is cleared, run = 0, transitions[k]++
+ *               intervals_flagged[k]++ where the flag is set after the interval.
+ *   frequencies the record's freq_hz is what the open interval is measured with.  set_params' frequencies are pending: they come into
+ *               force when an interval ends (for the next one), at a reset, and at set_params itself where no interval is open
+ *               (frames == intervals * M).  The open interval finishes on the old frequencies.
+ *   bytes       flags = the eight bits;  ok = (flags & alarm_mask) == 0, with the station's alarm_mask as it is when the bytes are written
+ *               (a process call, set_params, reset).  No atomics; ordinary stores.  Nothing depends, bit for bit, on how the frames are
+ *               split into calls, on streams, on the batch or on the station's row.
+ *   read-out    host, double, pure functions over one record; fs as in the design, 0 <= slot < 8 and 1 <= window <= 30 (else
+ *               FMD_ERR_ARG); FMD_ERR_STATE while intervals < window.  Over the newest `window` intervals, oldest first, from +0:
+ *                 pw += ring_pw[slot], mm += ring_mm
+ *                 share_db  10.0 * log10(2.0 * pw / ((double)M * mm))                       the tone's share of the mid signal's power
+ *                 level_db  10.0 * log10(2.0 * pw / ((double)M * (double)M * (double)window)) the mean square of the tone's part of m
+ *               Nothing is special-cased: IEEE results are returned as they come (NaN for 0 / 0, -inf for no power in the slot).
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_tonedet_s* fmd_tonedet;
+typedef struct {
+    int       n_channels;         /* C: station rows of the input */
+    int       fs;                 /* the audio's rate: a multiple of 10 in 8000 ... 48000 */
+    long long max_input_frames;   /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_tonedet_config;
+/* defaults: {1000, 440, 400, 853, 960, 1050, 0, 0}, {3, 3, 3, 6, 6, 3, 3, 3}, -50.0, 20 for all, 5 for all, 0 (a tone is an indication
+ * until the user makes it an alarm).  Valid: every freq_hz 0 or 1 <= f and 2 f < fs; every share_db in [0, 60]; floor_db = -inf or
+ * finite; every raise_intervals and clear_intervals in 1 ... 36000 (an hour); alarm_mask with no bit above bit 7.  176 bytes */
+typedef struct {
+    int      freq_hz[8];          /* slot k's frequency in Hz, 0 = unused */
+    double   share_db[8];         /* slot k's tone is present where its power is no more than this far below the mid signal's */
+    double   floor_db;            /* an interval whose mid signal's mean square, 10 log10(MM / M), is not above this carries no tone */
+    int      raise_intervals[8];  /* intervals with the tone in a row that set slot k's flag */
+    int      clear_intervals[8];  /* intervals without it in a row that clear it */
+    unsigned alarm_mask;          /* the slots (bit k) whose flag takes the station's ok byte to 0 */
+} fmd_tonedet_params;
+/* one per station, 2344 bytes: frames at byte 0, intervals 8, intervals_flagged 16, ring_mm 80, ring_pw 320, run 2240, transitions 2272,
+ * nonfinite 2304, freq_hz 2308, flags 2340, ok 2341, reserved 2342 */
+typedef struct {
+    unsigned long long frames;               /* frames seen since reset */
+    unsigned long long intervals;            /* completed 100 ms intervals */
+    unsigned long long intervals_flagged[8]; /* ... of them with slot k's flag set after the interval */
+    double   ring_mm[30];                    /* interval g at [g % 30]: sum m^2 */
+    double   ring_pw[8][30];                 /* ... and slot k's RE^2 + IM^2 */
+    unsigned run[8];                         /* slot k's run of intervals with (flag clear) or without (flag set) its tone */
+    unsigned transitions[8];                 /* raises and clears of slot k since reset */
+    unsigned nonfinite;                      /* intervals with a non-finite MM */
+    int      freq_hz[8];                     /* the frequencies in force: what the open interval is measured with */
+    unsigned char flags;                     /* bit k: slot k's tone is present */
+    unsigned char ok;                        /* (flags & alarm_mask) == 0 */
+    unsigned char reserved[2];
+} fmd_tonedet_status;
+
+/* host-only (no GPU needed) */
+void fmd_tonedet_default_params(fmd_tonedet_params* p);
+int fmd_tonedet_share_db(const fmd_tonedet_status* s, int fs, int slot, int window, double* db);
+int fmd_tonedet_level_db(const fmd_tonedet_status* s, int fs, int slot, int window, double* db);
+
+int fmd_tonedet_create(const fmd_tonedet_config* cfg, fmd_tonedet* out);
+int fmd_tonedet_destroy(fmd_tonedet t);
+/* everything of station `channel` (-1 = every station) as after create: counters, ring, the open interval, the detectors (every flag
+ * clear, ok = 1); its parameters are kept and its frequencies come into force.  Waits for the detector's earlier work */
+int fmd_tonedet_reset(fmd_tonedet t, int channel);
+/* the parameters of station `channel` (-1 = every station): ordered behind the detector's earlier work.  Frequencies apply from the next
+ * interval that starts; every other field from the next interval that ends (alarm_mask: from the next bytes written, the record's ok
+ * at once).  FMD_ERR_ARG for values outside the ranges above, and nothing changes */
+int fmd_tonedet_set_params(fmd_tonedet t, int channel, const fmd_tonedet_params* p);
+int fmd_tonedet_get_params(fmd_tonedet t, int channel, fmd_tonedet_params* p);
+/* takes n frames of every station.  d_in [C][in_stride][2] f32 on the device, 8-byte aligned; d_active: [C] uint8 on the device,
+ * NULL = all: a station whose byte is 0 is skipped whole, and its two output bytes are left as they are.  d_flags, d_ok: [C] uint8 on
+ * the device, caller-owned, each may be NULL: behind its work on `stream` the call writes every other station's byte, also when n == 0
+ * and for a station whose detectors did not move.  n < 0, n > in_stride, n > max_input_frames or a misaligned d_in return FMD_ERR_ARG
+ * and change nothing.  Asynchronous on `stream`; consecutive calls may use different streams (the library orders them). */
+int fmd_tonedet_process_f32_dev(fmd_tonedet t, const float* d_in, long long in_stride, long long n, const uint8_t* d_active,
+                                uint8_t* d_flags, uint8_t* d_ok, void* stream);
+/* out [C]; synchronises with the detector's work */
+int fmd_tonedet_get_status(fmd_tonedet t, fmd_tonedet_status* out);
+/* the device's own [C] records, for a consumer on the device: ordered behind the detector's work on the stream of its last process
+ * call, valid until the next process call */
+int fmd_tonedet_status_dev(fmd_tonedet t, const fmd_tonedet_status** d_status);
+const char* fmd_tonedet_last_error(fmd_tonedet t);
+
 #ifdef __cplusplus
 }
 #endif
