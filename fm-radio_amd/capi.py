@@ -232,6 +232,17 @@ TONEDET_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("intervals", "<u8"), ("inte
 TONEDET_SLOTS = 8
 
 
+class AdpcmConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("block_frames", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
+
+
+# include/fmdemod.h fmd_adpcm_status (64 bytes)
+ADPCM_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("blocks", "<u8"), ("padded", "<u8"), ("clipped", "<u8", (2,)), ("nonfinite", "<u8"), ("fill", "<u4"),
+                               ("pred", "<i2", (2,)), ("index", "u1", (2,)), ("reserved", "u1", (6,))])
+ADPCM_DEFAULT_BLOCK_FRAMES = 1017
+ADPCM_WAV_HEADER_BYTES = 60
+
+
 class PlanInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("effective_channels", "pilot_power_rows", "pll_k_adaptive", "pll_chained", "pll_waves", "lmr_inline", "lazy_capable",
                                        "front_lds_pad", "front_big_tile", "extract_auto_pair", "pll_kernel")]
@@ -446,14 +457,22 @@ def load_library():
     L.fmd_tonedet_set_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(TonedetParams)]
     L.fmd_tonedet_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(TonedetParams)]
     L.fmd_tonedet_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fmd_adpcm_block_align.argtypes = [C.c_int]
+    L.fmd_adpcm_max_blocks.argtypes = [C.c_int, C.c_longlong]
+    L.fmd_adpcm_max_blocks.restype = C.c_longlong
+    L.fmd_adpcm_decode_blocks.argtypes = [C.c_void_p, C.c_int, C.c_longlong, C.c_void_p]
+    L.fmd_adpcm_wav_header.argtypes = [C.c_int, C.c_int, C.c_longlong, C.c_longlong, C.c_void_p, C.POINTER(C.c_int)]
+    L.fmd_adpcm_create.argtypes = [C.POINTER(AdpcmConfig), C.POINTER(C.c_void_p)]
+    L.fmd_adpcm_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_adpcm_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
     # what every side object declares alike
-    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "rdsdec"):
+    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "rdsdec"):
         getattr(L, f"fmd_{pre}_destroy").argtypes = [C.c_void_p]
         getattr(L, f"fmd_{pre}_last_error").restype = C.c_char_p
         getattr(L, f"fmd_{pre}_last_error").argtypes = [C.c_void_p]
-    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet"):
+    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm"):
         getattr(L, f"fmd_{pre}_reset").argtypes = [C.c_void_p, C.c_int]
-        if pre != "tonedet":                                      # (the tone detector holds no peaks)
+        if pre not in ("tonedet", "adpcm"):                       # (the tone detector and the encoder hold no peaks)
             getattr(L, f"fmd_{pre}_reset_peaks").argtypes = [C.c_void_p, C.c_int]
         getattr(L, f"fmd_{pre}_get_status").argtypes = [C.c_void_p, C.c_void_p]
         getattr(L, f"fmd_{pre}_status_dev").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -657,7 +676,8 @@ class _Handle:
 
 
 class _Monitor(_Handle):
-    """The five per-station monitors (meter, modmon, squelch, audmon, tonedet): [C] status records of `_status_dtype` that reset the same way."""
+    """The five per-station monitors (meter, modmon, squelch, audmon, tonedet) and the ADPCM encoder: [C] status records of `_status_dtype` that reset
+    the same way."""
     _status_dtype = None
 
     def reset(self, channel: int = -1):
@@ -1800,3 +1820,111 @@ class ToneDetector(_Gated):
             ct, py = kinds[name]
             return (ct * 8)(*([py(value)] * 8 if np.isscalar(value) else [py(a) for a in value]))
         return value
+
+
+def adpcm_block_align(block_frames: int = 0) -> int:
+    """fmd_adpcm_block_align (host only): bytes of a block of `block_frames` frames (0 = the default 1017: 1024 bytes)"""
+    L = load_library()
+    rc = L.fmd_adpcm_block_align(int(block_frames))
+    if rc < 0:
+        raise _global_error(L, "fmd_adpcm", rc)
+    return rc
+
+
+def adpcm_max_blocks(block_frames: int, n: int) -> int:
+    """fmd_adpcm_max_blocks (host only): the most blocks a call of n frames completes for a station, (S - 1 + n) / S"""
+    L = load_library()
+    rc = L.fmd_adpcm_max_blocks(int(block_frames), int(n))
+    if rc < 0:
+        raise _global_error(L, "fmd_adpcm", int(rc))
+    return int(rc)
+
+
+def adpcm_decode(blocks, block_frames: int = 0) -> np.ndarray:
+    """fmd_adpcm_decode_blocks (host only): whole blocks (any uint8 array or bytes of n_blocks * block_align bytes) -> [n_blocks * S, 2] int16"""
+    L = load_library()
+    align = adpcm_block_align(block_frames)
+    b = np.ascontiguousarray(np.frombuffer(blocks, np.uint8) if isinstance(blocks, (bytes, bytearray)) else blocks, np.uint8).reshape(-1)
+    if b.size % align:
+        raise ValueError(f"{b.size} bytes are no whole number of blocks of {align} bytes")
+    nb = b.size // align
+    S = (align // 8 - 1) * 8 + 1
+    pcm = np.zeros((nb * S, 2), np.int16)
+    rc = L.fmd_adpcm_decode_blocks(b.ctypes.data_as(C.c_void_p), int(block_frames), nb, pcm.ctypes.data_as(C.c_void_p))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_adpcm", rc)
+    return pcm
+
+
+def adpcm_wav_header(fs: int, block_frames: int, n_blocks: int, n_frames: int) -> bytes:
+    """fmd_adpcm_wav_header (host only): the 60 bytes in front of n_blocks blocks in a WAV file of format 0x0011 whose `fact` chunk states
+    n_frames, the true length"""
+    L = load_library()
+    out = (C.c_ubyte * ADPCM_WAV_HEADER_BYTES)()
+    n = C.c_int(0)
+    rc = L.fmd_adpcm_wav_header(int(fs), int(block_frames), int(n_blocks), int(n_frames), out, C.byref(n))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_adpcm", rc)
+    return bytes(out)[:n.value]
+
+
+class AdpcmEncoder(_Monitor):
+    """Block IMA / DVI ADPCM encoder of C stations' stereo audio on the GPU (fmd_adpcm_*): a quarter of the 16-bit PCM bytes, in blocks that
+    a WAV file of format 0x0011 holds as they are.  Feed it the same [C, n, 2] float32 CUDA tensors as AudioMixer and the monitors; it
+    changes nothing in them.  process() returns the [C, out_stride] uint8 rows with each station's completed blocks back to back and
+    the [C] int32 block counts; flush() closes the open blocks.  status() returns ADPCM_STATUS_DTYPE records; adpcm_decode and
+    adpcm_wav_header are the host's side."""
+    _prefix, _attr, _status_dtype = "fmd_adpcm", "e", ADPCM_STATUS_DTYPE
+
+    def __init__(self, n_channels: int, block_frames: int = 0, max_input_frames: int = 1 << 16, device: int = -1):
+        cfg = AdpcmConfig(int(n_channels), int(block_frames), int(max_input_frames), device)
+        self._create("create", C.byref(cfg))
+        self.n_channels = int(n_channels)
+        self.block_frames = int(block_frames) or ADPCM_DEFAULT_BLOCK_FRAMES
+        self.block_align = adpcm_block_align(self.block_frames)
+
+    def reset_peaks(self, channel: int = -1):
+        raise AttributeError("the encoder holds no peaks")
+
+    def _outputs(self, out, nblocks, need: int, device, stream):
+        """(out, its pointer, out_stride, nblocks, its pointer): out None = a new zeroed [C, need] tensor; nblocks None = new, False = not written"""
+        import torch
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device) if stream else torch.cuda.default_stream(device)):
+            if out is None:
+                out = torch.zeros((self.n_channels, max(need, 4)), dtype=torch.uint8, device=device)
+            if nblocks is None:
+                nblocks = torch.zeros(self.n_channels, dtype=torch.int32, device=device)
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == self.n_channels and out.stride(1) == 1):
+            raise ValueError("out must be a [C, out_stride] uint8 CUDA tensor with contiguous rows")
+        if out.shape[1] < need:
+            raise ValueError(f"out's rows hold {out.shape[1]} bytes; the call may write {need}")
+        if nblocks is False:
+            nblocks = None
+        elif not (nblocks.is_cuda and nblocks.dtype == torch.int32 and nblocks.shape == (self.n_channels,) and nblocks.is_contiguous()):
+            raise ValueError("nblocks must be a contiguous [C] int32 CUDA tensor")
+        stride = out.stride(0) if self.n_channels > 1 else out.shape[1]
+        return out, C.c_void_p(out.data_ptr()), stride, nblocks, None if nblocks is None else C.c_void_p(nblocks.data_ptr())
+
+    def process(self, x, n: int | None = None, active=None, out=None, nblocks=None, stream=None):
+        """takes the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
+        uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole: its row of out is kept, its count is 0); out: the
+        [C, out_stride] uint8 CUDA tensor to write, out_stride a multiple of 4 and at least adpcm_max_blocks(S, n) * block_align, None =
+        a new zeroed one of exactly that; nblocks: the [C] int32 CUDA tensor to write, None = a new one, False = not written.  Returns
+        (out, nblocks).  Asynchronous on `stream` (default: torch's current)."""
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32",), "frames")
+        pa, stream = _active_ptr(active, self.n_channels), _stream_ptr(stream, x.device)
+        need = (self.block_frames - 1 + max(n, 0)) // self.block_frames * self.block_align
+        out, po, stride, nblocks, pn = self._outputs(out, nblocks, need, x.device, stream)
+        self._check(self.L.fmd_adpcm_process_f32_dev(self.e, px, in_stride, n, pa, po, stride, pn, C.c_void_p(stream)))
+        return out, nblocks
+
+    def flush(self, channel: int = -1, out=None, nblocks=None, stream=None, device=None):
+        """fmd_adpcm_flush: closes the open block of station `channel` (-1 = of every station) with repeats of its last frame: 0 or 1
+        block at out[c] and its number in nblocks[c]; the other stations' rows and counts are kept.  out, nblocks as in process (None =
+        new, zeroed).  Returns (out, nblocks)."""
+        import torch
+        device = device if device is not None else (out.device if out is not None and out is not False else torch.device("cuda", torch.cuda.current_device()))
+        stream = _stream_ptr(stream, device)
+        out, po, stride, nblocks, pn = self._outputs(out, nblocks, self.block_align, device, stream)
+        self._check(self.L.fmd_adpcm_flush(self.e, int(channel), po, stride, pn, C.c_void_p(stream)))
+        return out, nblocks

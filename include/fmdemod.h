@@ -1292,6 +1292,101 @@ int fmd_tonedet_get_status(fmd_tonedet t, fmd_tonedet_status* out);
 int fmd_tonedet_status_dev(fmd_tonedet t, const fmd_tonedet_status** d_status);
 const char* fmd_tonedet_last_error(fmd_tonedet t);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * ADPCM audio encoder (NOT part of the reference): station recordings at a quarter of the 16-bit PCM bytes, as block IMA / DVI ADPCM, the
+ * WAV format tag 0x0011 that ordinary players and tools open.  The first side object that is a sink: it reads the device array
+ * [C][in_stride][2] f32 (interleaved L, R) that the mixer and the monitors read, changes nothing in it, and writes every station's
+ * completed blocks to a caller-owned device array: 32 KB/s per station at 32 kHz, where 16-bit PCM is 128 KB/s.  Stereo only.
+ * Arithmetic, restated in C by tests/cpp/adpcm_ref.c; all integer behind one fp32 multiply:
+ *   sample      t = x * (32767.0f * 0.95f)                      one fp32 multiply, round to nearest: the scraper's scale (fmd_audio_pcm16_dev)
+ *               t NaN or +-inf:  q = 0, the station's nonfinite++ (per sample)
+ *               otherwise        v = (int)t, truncated toward zero;  v > 32767 -> q = 32767, v < -32768 -> q = -32768, each with the
+ *                                rail's clipped++;  else q = v.  For every in-range sample q is fmd_audio_pcm16_dev's value.
+ *   step        the IMA / DVI reference quantiser over (pred, index) per rail, with the 89-entry step table and the index table
+ *               {-1, -1, -1, -1, 2, 4, 6, 8}:
+ *                 step = table[index];  diff = q - pred;  code = 8 where diff < 0, and diff = -diff then;  vpdiff = step >> 3
+ *                 diff >= step      -> code |= 4, diff -= step,      vpdiff += step
+ *                 diff >= step >> 1 -> code |= 2, diff -= step >> 1, vpdiff += step >> 1
+ *                 diff >= step >> 2 -> code |= 1,                    vpdiff += step >> 2
+ *                 pred = pred -+ vpdiff by the sign, clamped to int16;  index += index table[code & 7], clamped to 0 ... 88
+ *               (what Python's audioop.lin2adpcm(..., 2, (pred, index)) computes.)
+ *   block       S = block_frames frames, S = 1 (mod 8), 9 <= S <= 8185, default 1017;  block_align = 8 * ((S - 1) / 8 + 1) bytes
+ *               (1024 for the default, 31.8 ms at 32 kHz).
+ *                 bytes 0-1  q(L) of the block's first frame, int16 little-endian;  byte 2  L's index as it stands (0 after a reset,
+ *                 else what the previous block's last frame left: the index is carried from block to block);  byte 3  0
+ *                 bytes 4-7  the same for R
+ *               At the block's first frame each rail's pred is set to the header sample itself and no code is emitted.  Then per further
+ *               eight frames four bytes of L codes and four bytes of R codes, the earlier frame in the low nibble.
+ *   streaming   frames are counted per station since its reset.  The open block's bytes, its fill count, each rail's pred and index
+ *               live in the encoder and carry to the next call.  A call of n frames completes (fill + n) / S blocks for the station,
+ *               writes them back to back at d_out + c * out_stride and their number to d_nblocks[c]; bytes of d_out behind them are left
+ *               as they are.  Stations may stand at different places in their blocks.  Nothing depends, bit for bit, on how the frames
+ *               are split into calls, on streams, on the batch or on the station's row.  Ordinary stores, no atomics.
+ *   flush       closes the station's open block: repeats of the last real frame's (q(L), q(R)) are encoded until the block is full,
+ *               the block is written at d_out + c * out_stride and 1 to d_nblocks[c];  padded += S - fill, blocks++, fill = 0, pred and
+ *               index carried on.  With fill == 0 nothing of the station changes and d_nblocks[c] = 0.
+ *   decoder     per block and rail from the header's (pred, index):  vpdiff = step >> 3, + step, + step >> 1, + step >> 2 by the code's
+ *               bits 2, 1, 0;  pred and index move as in the encoder.  (audioop.adpcm2lin.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_adpcm_s* fmd_adpcm;
+typedef struct {
+    int       n_channels;         /* C: station rows of the input */
+    int       block_frames;       /* S: frames of a block, 1 (mod 8) in 9 ... 8185; 0 = 1017 */
+    long long max_input_frames;   /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_adpcm_config;
+/* one per station, 64 bytes: frames at byte 0, blocks 8, padded 16, clipped 24, nonfinite 40, fill 48, pred 52, index 56, reserved 58 */
+typedef struct {
+    unsigned long long frames;        /* frames taken since reset */
+    unsigned long long blocks;        /* blocks completed since reset, the flushed ones among them */
+    unsigned long long padded;        /* frames that flushes repeated to fill their blocks: frames + padded = blocks * S + fill */
+    unsigned long long clipped[2];    /* samples of L, R clamped to the 16-bit range */
+    unsigned long long nonfinite;     /* samples (of either rail) that were NaN or +-inf after the scale: encoded as 0 */
+    unsigned           fill;          /* frames in the open block, 0 ... S - 1 */
+    short              pred[2];       /* each rail's predictor */
+    unsigned char      index[2];      /* each rail's step index, 0 ... 88 */
+    unsigned char      reserved[6];
+} fmd_adpcm_status;
+#define FMD_ADPCM_WAV_HEADER_BYTES 60
+
+/* host-only (no GPU needed); block_frames as in the configuration (0 = 1017), FMD_ERR_ARG for any other value that is no valid S */
+/* bytes of a block */
+int fmd_adpcm_block_align(int block_frames);
+/* (S - 1 + n) / S: the most blocks a process call of n frames completes for a station, whatever its fill */
+long long fmd_adpcm_max_blocks(int block_frames, long long n);
+/* the matching decoder: blocks [n_blocks][block_align] -> pcm_out [n_blocks * S][2] int16, interleaved.  FMD_ERR_ARG, with nothing
+ * written, where a header's index byte is above 88 */
+int fmd_adpcm_decode_blocks(const uint8_t* blocks, int block_frames, long long n_blocks, int16_t* pcm_out);
+/* the FMD_ADPCM_WAV_HEADER_BYTES bytes in front of n_blocks blocks in a RIFF / WAVE file, *len = their number: a `fmt ` chunk of 20
+ * bytes (tag 0x0011, 2 channels, fs, nAvgBytesPerSec = fs * block_align / S in integers, nBlockAlign, wBitsPerSample = 4, cbSize = 2,
+ * wSamplesPerBlock = S), a `fact` chunk with n_frames, the true length (frames - what flushes padded), and the `data` chunk's header.
+ * FMD_ERR_ARG for fs outside 1 ... 1000000 or n_frames outside [0, n_blocks * S]; FMD_ERR_SIZE where the file would pass 4 GiB */
+int fmd_adpcm_wav_header(int fs, int block_frames, long long n_blocks, long long n_frames, uint8_t* out, int* len);
+
+int fmd_adpcm_create(const fmd_adpcm_config* cfg, fmd_adpcm* out);
+int fmd_adpcm_destroy(fmd_adpcm e);
+/* station `channel` (-1 = every station) as after create: counters 0, no open block, pred and index 0.  Waits for the encoder's
+ * earlier work */
+int fmd_adpcm_reset(fmd_adpcm e, int channel);
+/* takes n frames of every station.  d_in [C][in_stride][2] f32 on the device, 8-byte aligned; d_active: [C] uint8 on the device,
+ * NULL = all: a station whose byte is 0 is skipped whole, its row of d_out is left as it is and d_nblocks[c] = 0.  d_out: caller-owned
+ * bytes on the device, 4-byte aligned, station c's completed blocks from d_out + c * out_stride on; out_stride in bytes, a multiple of
+ * 4 and at least fmd_adpcm_max_blocks(S, n) * block_align.  d_nblocks: [C] int32 on the device, may be NULL.  n < 0, n > in_stride,
+ * n > max_input_frames, a misaligned or null d_in or d_out or an out_stride that is too small or no multiple of 4 return FMD_ERR_ARG and
+ * change nothing.  Asynchronous on `stream`; consecutive calls may use different streams (the library orders them). */
+int fmd_adpcm_process_f32_dev(fmd_adpcm e, const float* d_in, long long in_stride, long long n, const uint8_t* d_active, uint8_t* d_out,
+                              long long out_stride, int* d_nblocks, void* stream);
+/* closes the open block of station `channel` (-1 = of every station) as `flush` above says: 0 or 1 block at d_out + c * out_stride and
+ * its number in d_nblocks[c] (may be NULL); other stations' rows and counts are left as they are.  d_out 4-byte aligned, out_stride a
+ * multiple of 4 and at least block_align, else FMD_ERR_ARG.  Asynchronous on `stream`, ordered like a process call */
+int fmd_adpcm_flush(fmd_adpcm e, int channel, uint8_t* d_out, long long out_stride, int* d_nblocks, void* stream);
+/* out [C]; synchronises with the encoder's work */
+int fmd_adpcm_get_status(fmd_adpcm e, fmd_adpcm_status* out);
+/* the device's own [C] records, for a consumer on the device: ordered behind the encoder's work on the stream of its last call, valid
+ * until the next call */
+int fmd_adpcm_status_dev(fmd_adpcm e, const fmd_adpcm_status** d_status);
+const char* fmd_adpcm_last_error(fmd_adpcm e);
+
 #ifdef __cplusplus
 }
 #endif
