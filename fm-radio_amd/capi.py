@@ -243,6 +243,40 @@ ADPCM_DEFAULT_BLOCK_FRAMES = 1017
 ADPCM_WAV_HEADER_BYTES = 60
 
 
+class SameConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
+
+
+class SameParams(C.Structure):
+    """include/fmdemod.h fmd_same_params"""
+    _fields_ = [("pull", C.c_int), ("hold_ticks", C.c_uint), ("alarm_mask", C.c_uint), ("reserved", C.c_uint)]
+
+
+class SameEncodeConfig(C.Structure):
+    """include/fmdemod.h fmd_same_encode_config"""
+    _fields_ = [("fs", C.c_int), ("repeats", C.c_int), ("gap_frames", C.c_longlong), ("clock_ratio", C.c_double), ("amplitude", C.c_double),
+                ("mark_db", C.c_double)]
+
+
+class SameHeader(C.Structure):
+    """include/fmdemod.h fmd_same_header"""
+    _fields_ = [("kind", C.c_int), ("valid", C.c_uint), ("org", C.c_char * 4), ("event", C.c_char * 4), ("n_locations", C.c_int),
+                ("locations", (C.c_char * 8) * 31), ("duration_min", C.c_int), ("day", C.c_int), ("hour", C.c_int), ("minute", C.c_int),
+                ("callsign", C.c_char * 12)]
+
+
+# include/fmdemod.h fmd_same_message (280 bytes) and fmd_same_status (2856 bytes)
+SAME_MESSAGE_DTYPE = np.dtype([("sync_tick", "<u8"), ("len", "<u2"), ("kind", "u1"), ("reserved", "u1"), ("bytes", "u1", (268,))])
+SAME_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("ticks", "<u8"), ("bits", "<u8"), ("syncs", "<u8"), ("accepted", "<u8"), ("rejected", "<u8"),
+                              ("sync_tick", "<u8"), ("last_accept_tick", "<u8"), ("open", "<f8", (4,)), ("hist", "<f8", (7, 4)), ("ph", "<u4"),
+                              ("sh", "<u4"), ("nbit", "<u4"), ("msg_len", "<u4"), ("run", "<u4"), ("synced", "u1"), ("prev_s", "u1"), ("flags", "u1"),
+                              ("ok", "u1"), ("msg", "u1", (268,)), ("reserved", "u1", (4,)), ("ring", SAME_MESSAGE_DTYPE, (8,))])
+SAME_SYNCED, SAME_ALERT_OPEN = 1, 2
+SAME_KIND_HEADER, SAME_KIND_EOM = 1, 2
+SAME_VALID_ORG, SAME_VALID_EVENT, SAME_VALID_LOCATIONS, SAME_VALID_DURATION, SAME_VALID_TIME, SAME_VALID_CALLSIGN = 1, 2, 4, 8, 16, 32
+SAME_RING = 8
+
+
 class PlanInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("effective_channels", "pilot_power_rows", "pll_k_adaptive", "pll_chained", "pll_waves", "lmr_inline", "lazy_capable",
                                        "front_lds_pad", "front_big_tile", "extract_auto_pair", "pll_kernel")]
@@ -465,14 +499,24 @@ def load_library():
     L.fmd_adpcm_create.argtypes = [C.POINTER(AdpcmConfig), C.POINTER(C.c_void_p)]
     L.fmd_adpcm_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
     L.fmd_adpcm_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_same_default_params.argtypes = [C.POINTER(SameParams)]
+    L.fmd_same_default_params.restype = None
+    L.fmd_same_encode.argtypes = [C.POINTER(SameEncodeConfig), C.c_char_p, C.c_int, C.c_void_p, C.c_longlong]
+    L.fmd_same_encode.restype = C.c_longlong
+    L.fmd_same_parse.argtypes = [C.c_char_p, C.c_int, C.POINTER(SameHeader)]
+    L.fmd_same_vote.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.fmd_same_create.argtypes = [C.POINTER(SameConfig), C.POINTER(C.c_void_p)]
+    L.fmd_same_set_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SameParams)]
+    L.fmd_same_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SameParams)]
+    L.fmd_same_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # what every side object declares alike
-    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "rdsdec"):
+    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "rdsdec"):
         getattr(L, f"fmd_{pre}_destroy").argtypes = [C.c_void_p]
         getattr(L, f"fmd_{pre}_last_error").restype = C.c_char_p
         getattr(L, f"fmd_{pre}_last_error").argtypes = [C.c_void_p]
-    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm"):
+    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same"):
         getattr(L, f"fmd_{pre}_reset").argtypes = [C.c_void_p, C.c_int]
-        if pre not in ("tonedet", "adpcm"):                       # (the tone detector and the encoder hold no peaks)
+        if pre not in ("tonedet", "adpcm", "same"):               # (the tone detector, the encoder and the SAME decoder hold no peaks)
             getattr(L, f"fmd_{pre}_reset_peaks").argtypes = [C.c_void_p, C.c_int]
         getattr(L, f"fmd_{pre}_get_status").argtypes = [C.c_void_p, C.c_void_p]
         getattr(L, f"fmd_{pre}_status_dev").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -676,7 +720,7 @@ class _Handle:
 
 
 class _Monitor(_Handle):
-    """The five per-station monitors (meter, modmon, squelch, audmon, tonedet) and the ADPCM encoder: [C] status records of `_status_dtype` that reset
+    """The five per-station monitors (meter, modmon, squelch, audmon, tonedet), the ADPCM encoder and the SAME decoder: [C] status records of `_status_dtype` that reset
     the same way."""
     _status_dtype = None
 
@@ -702,7 +746,7 @@ class _Monitor(_Handle):
 
 
 class _Gated(_Monitor):
-    """The monitors with per-station parameters (squelch, audmon, tonedet): a ctypes structure `_params_type` read and set by field name."""
+    """The objects with per-station parameters (squelch, audmon, tonedet, same): a ctypes structure `_params_type` read and set by field name."""
     _params_type = None
 
     def _field(self, name: str, value):
@@ -1820,6 +1864,112 @@ class ToneDetector(_Gated):
             ct, py = kinds[name]
             return (ct * 8)(*([py(value)] * 8 if np.isscalar(value) else [py(a) for a in value]))
         return value
+
+
+def same_default_params() -> SameParams:
+    """fmd_same_default_params: pull 16, hold_ticks 750000 (180 s), alarm_mask 0"""
+    p = SameParams()
+    load_library().fmd_same_default_params(C.byref(p))
+    return p
+
+
+def same_encode(text, fs: int, clock_ratio: float = 1.0, amplitude: float = 0.25, repeats: int = 3, gap_frames: int = -1, mark_db: float = 0.0) -> np.ndarray:
+    """fmd_same_encode (host only): `text` (bytes or str, 1 ... 268 bytes) as [n, 2] float32 audio at fs: `repeats` bursts of 16 bytes 0xAB
+    and the text at 520.83 bit/s times clock_ratio, each followed by gap_frames of silence (negative: one second)"""
+    L = load_library()
+    text = text.encode("ascii") if isinstance(text, str) else bytes(text)
+    cfg = SameEncodeConfig(int(fs), int(repeats), int(gap_frames), float(clock_ratio), float(amplitude), float(mark_db))
+    n = L.fmd_same_encode(C.byref(cfg), text, len(text), None, 0)
+    if n < 0:
+        raise _global_error(L, "fmd_same", int(n))
+    out = np.zeros((n, 2), np.float32)
+    rc = L.fmd_same_encode(C.byref(cfg), text, len(text), out.ctypes.data_as(C.c_void_p), n)
+    if rc != n:
+        raise _global_error(L, "fmd_same", int(rc))
+    return out
+
+
+def same_parse(message) -> dict:
+    """fmd_same_parse (host only): one message's bytes -> {"kind", "valid", "org", "event", "locations", "duration_min", "day", "hour",
+    "minute", "callsign"}; a field whose SAME_VALID_* bit is clear is empty or 0"""
+    L = load_library()
+    b = bytes(message)
+    h = SameHeader()
+    rc = L.fmd_same_parse(b, len(b), C.byref(h))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_same", rc)
+    return {"kind": h.kind, "valid": h.valid, "org": h.org.decode(), "event": h.event.decode(),
+            "locations": [h.locations[i].value.decode() for i in range(h.n_locations)], "duration_min": h.duration_min, "day": h.day, "hour": h.hour,
+            "minute": h.minute, "callsign": h.callsign.decode()}
+
+
+def same_vote(messages) -> tuple:
+    """fmd_same_vote (host only): one to three (sync_tick, kind, bytes) messages of one transmission -> ((sync_tick, kind, bytes) voted byte
+    by byte two out of three, corrected, unresolved)"""
+    L = load_library()
+    m = np.zeros(len(messages), SAME_MESSAGE_DTYPE)
+    for i, (tick, kind, b) in enumerate(messages):
+        if len(b) > 268:
+            raise ValueError("a message has more than 268 bytes")
+        m[i]["sync_tick"], m[i]["len"], m[i]["kind"] = tick, len(b), kind
+        m[i]["bytes"][:len(b)] = np.frombuffer(bytes(b), np.uint8)
+    out = np.zeros(1, SAME_MESSAGE_DTYPE)
+    fixed, unresolved = C.c_int(0), C.c_int(0)
+    rc = L.fmd_same_vote(m.ctypes.data_as(C.c_void_p), len(messages), out.ctypes.data_as(C.c_void_p), C.byref(fixed), C.byref(unresolved))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_same", rc)
+    r = out[0]
+    return (int(r["sync_tick"]), int(r["kind"]), bytes(r["bytes"][:int(r["len"])])), fixed.value, unresolved.value
+
+
+class SameDecoder(_Gated):
+    """EAS SAME decoder of C stations' audio on the GPU (fmd_same_*): per station the 520.83 bit/s AFSK bursts in front of and behind an
+    alert, decoded to `ZCZC-...` headers and `NNNN` end-of-message marks, and two [C] uint8 tensors: the flags (SAME_SYNCED,
+    SAME_ALERT_OPEN) and the ok bytes, which AudioMixer.process(active=...) takes as they are.  Feed it the same [C, n, 2] float32 CUDA
+    tensors as AudioMixer and the monitors; it changes nothing in them.  status() returns SAME_STATUS_DTYPE records; messages() the
+    messages accepted since it was last asked; same_parse and same_vote are the host's side."""
+    _prefix, _attr, _status_dtype, _params_type = "fmd_same", "d", SAME_STATUS_DTYPE, SameParams
+
+    def __init__(self, n_channels: int, fs: int, max_input_frames: int = 1 << 16, device: int = -1):
+        cfg = SameConfig(int(n_channels), int(fs), int(max_input_frames), device)
+        self._create("create", C.byref(cfg))
+        self.n_channels, self.fs = int(n_channels), int(fs)
+        self._seen = [0] * self.n_channels
+
+    def reset_peaks(self, channel: int = -1):
+        raise AttributeError("the SAME decoder holds no peaks")
+
+    def reset(self, channel: int = -1):
+        super().reset(channel)
+        for c in (range(self.n_channels) if channel < 0 else (int(channel),)):
+            self._seen[c] = 0
+
+    def process(self, x, n: int | None = None, active=None, flags=None, ok=None, stream=None):
+        """takes the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
+        uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole and keeps its two bytes); flags, ok: the [C] uint8 CUDA
+        tensors to write, None = a new one, False = not written.  Returns (flags, ok), None for one not written.  Asynchronous on
+        `stream` (default: torch's current)."""
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32",), "frames")
+        pa, stream = _active_ptr(active, self.n_channels), _stream_ptr(stream, x.device)
+        flags, pf = _byte_out(flags, "flags", self.n_channels, x.device, stream)
+        ok, po = _byte_out(ok, "ok", self.n_channels, x.device, stream)
+        self._check(self.L.fmd_same_process_f32_dev(self.d, px, in_stride, n, pa, pf, po, C.c_void_p(stream)))
+        return flags, ok
+
+    def messages(self, status=None) -> list:
+        """per station the messages accepted since the last messages() (or the reset), oldest first, as (sync_tick, kind, bytes); of more
+        than eight new ones the ring holds the newest eight.  Waits for the decoder's work unless `status` (its status() records) is given."""
+        st = self.status() if status is None else status
+        out = []
+        for c in range(self.n_channels):
+            acc = int(st[c]["accepted"])
+            new = []
+            for k in range(max(self._seen[c], acc - SAME_RING), acc):
+                r = st[c]["ring"][k % SAME_RING]
+                new.append((int(r["sync_tick"]), int(r["kind"]), bytes(r["bytes"][:int(r["len"])])))
+            self._seen[c] = acc
+            out.append(new)
+        return out
 
 
 def adpcm_block_align(block_frames: int = 0) -> int:

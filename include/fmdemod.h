@@ -1387,6 +1387,163 @@ int fmd_adpcm_get_status(fmd_adpcm e, fmd_adpcm_status* out);
 int fmd_adpcm_status_dev(fmd_adpcm e, const fmd_adpcm_status** d_status);
 const char* fmd_adpcm_last_error(fmd_adpcm e);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * EAS SAME decoder (NOT part of the reference): which alert is on the air.  The tone detector says that the 853 + 960 Hz attention
+ * signal is on a station; the machine-readable part in front of it -- three bursts of a SAME header (47 CFR 11.31), 520.83 bit/s AFSK
+ * of `ZCZC-ORG-EEE-PSSCCC...+TTTT-JJJHHMM-LLLLLLLL-`, and three `NNNN` bursts at the alert's end -- says which.  It reads the device
+ * array [C][in_stride][2] f32 (interleaved L, R) that the mixer and the monitors read, changes nothing in it, keeps one record per
+ * station with the newest eight accepted messages, and writes a [C] uint8 flags byte and a [C] uint8 ok byte per station.
+ * Arithmetic, restated in C by tests/cpp/same_ref.c:
+ *   design      host, double, host libm; fs a multiple of 10 in 8000 ... 48000:
+ *                 g = gcd(3125, 6 fs), P = 6 fs / g (at most 57600);  tc[j] = cos(2.0 * M_PI * (double)j / (double)P), ts[j] likewise sin
+ *                 mark step = (4 * 3125 / g) mod P (2083.33 Hz, four cycles a bit), space step = (3 * 3125 / g) mod P (1562.5 Hz, three)
+ *   per frame   i counted absolutely in 64 bits since the station's reset:  m = (double)L + (double)R
+ *                 the table index of frame i is (i * step) mod P per tone, moved on by an add and a conditional subtract
+ *   tick        eight a nominal bit: tick k covers frames [B(k), B(k + 1)), B(k) = ceil(k * 3 fs / 12500) -- with k = 12500 q + r,
+ *               B(k) = q * 3 fs + (r * 3 fs + 12499) / 12500 in integers.  Four sums a tick, each from +0 in ascending frame order:
+ *                 mre = fma(m, tc[im], mre); mim = fma(m, ts[im], mim); sre = fma(m, tc[is], sre); sim = fma(m, ts[is], sim)
+ *               The open tick's sums carry to the next call; fp32 and fp64 denormals are kept.
+ *   decision    at a tick's end each of the four window sums is ((((((((+0 + t[k-7]) + t[k-6]) + ...) + t[k]) over this tick and the
+ *               seven before it (ticks before the reset read +0);  E1 = fma(mre, mre, mim * mim), E0 = fma(sre, sre, sim * sim);
+ *               s = E1 > E0 (a NaN gives 0).  No normalisation, no threshold.
+ *   bit clock   integers, ph in 1 / 256 bit, run = ticks since s last changed (counted up to 255).  Where s differs from the previous
+ *               tick's s, the run that ends was nb = (run + 4) >> 3 bits long and its middle stood at ph - 16 run, which in lock is 0 for
+ *               an odd nb and 128 for an even one.  With nb >= 1 and run <= 96:  err = (ph - 16 run - (nb odd ? 0 : 128)) & 255;
+ *               err < 128 -> ph = (ph - min(pull, err)) & 255, else ph = (ph + min(pull, 256 - err)) & 255.  Then run = 0.  In every
+ *               tick run++ (up to 255), then ph += 32; at ph >= 256: ph -= 256 and s is a bit (bits++).  (A clock pulled by the
+ *               transitions themselves has a second stable state, half a bit off, once the mark tone is louder or softer than the space
+ *               tone, because rising and falling edges then move in opposite directions; a run's middle does not move: DESIGN.md §6l.)
+ *   framer      sh = (sh >> 1) | (s << 15), 16 bits.  Unsynchronised: sh == 0xABAB synchronises (syncs++, the message in progress starts
+ *               empty, sync_tick = this tick's number).  Synchronised: every eighth bit delivers b = sh >> 8.  b == 0xAB with the message
+ *               still empty is skipped; b in 0x20 ... 0x7E, 0x0D or 0x0A is appended, and the 268th byte ends the message; any other b ends
+ *               it as it stands.  An ended message whose first four bytes are ZCZC or NNNN is accepted: it goes to ring[accepted % 8]
+ *               (bytes behind its length 0), accepted++, last_accept_tick = this tick's number; any other is counted in `rejected`.
+ *               Either way the framer is unsynchronised again.
+ *   flags       bit 0 (FMD_SAME_SYNCED): synchronised at the call's end.  Bit 1 (FMD_SAME_ALERT_OPEN): set by an accepted ZCZC message,
+ *               cleared by an accepted NNNN message, and cleared at the end of tick k where k - last_accept_tick >= hold_ticks.
+ *               ok = (flags & alarm_mask) == 0.  Parameters apply from the next tick that ends; the record's ok follows alarm_mask at once.
+ *   Nothing depends, bit for bit, on how the frames are split into calls, on streams, on the batch or on the station's row.  No atomics;
+ *   ordinary stores.  (A NaN's sign and payload in the carried sums are not part of the contract.)
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_same_s* fmd_same;
+#define FMD_SAME_SYNCED        1u
+#define FMD_SAME_ALERT_OPEN    2u
+#define FMD_SAME_MAX_BYTES     268
+#define FMD_SAME_RING          8
+#define FMD_SAME_KIND_HEADER   1      /* ZCZC */
+#define FMD_SAME_KIND_EOM      2      /* NNNN */
+#define FMD_SAME_MAX_LOCATIONS 31
+typedef struct {
+    int       n_channels;         /* C: station rows of the input */
+    int       fs;                 /* the audio's rate: a multiple of 10 in 8000 ... 48000 */
+    long long max_input_frames;   /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_same_config;
+/* defaults: 16, 750000 (180 s of ticks: 12500 / 3 a second), 0.  Valid: pull in 0 ... 128; hold_ticks in 1 ... 2^31 - 1; alarm_mask
+ * with no bit above bit 1.  16 bytes */
+typedef struct {
+    int      pull;                /* the most the bit clock moves at a transition, in 1 / 256 bit */
+    unsigned hold_ticks;          /* ticks behind the last accepted message after which an open alert is closed */
+    unsigned alarm_mask;          /* the flags whose being set takes the station's ok byte to 0 */
+    unsigned reserved;            /* 0 */
+} fmd_same_params;
+/* 280 bytes: sync_tick at byte 0, len 8, kind 10, reserved 11, bytes 12 */
+typedef struct {
+    unsigned long long sync_tick;         /* the tick at whose end the framer synchronised on this message */
+    unsigned short     len;               /* bytes of the message, 4 ... 268 */
+    unsigned char      kind;              /* FMD_SAME_KIND_HEADER or FMD_SAME_KIND_EOM */
+    unsigned char      reserved;
+    unsigned char      bytes[FMD_SAME_MAX_BYTES];   /* the message from its ZCZC or NNNN on, 0 behind len */
+} fmd_same_message;
+/* one per station, 2856 bytes: frames at byte 0, ticks 8, bits 16, syncs 24, accepted 32, rejected 40, sync_tick 48, last_accept_tick 56,
+ * open 64, hist 96, ph 320, sh 324, nbit 328, msg_len 332, run 336, synced 340, prev_s 341, flags 342, ok 343, msg 344, reserved 612, ring 616 */
+typedef struct {
+    unsigned long long frames;            /* frames seen since reset */
+    unsigned long long ticks;             /* completed ticks: the open tick's number */
+    unsigned long long bits;              /* bits the clock has taken */
+    unsigned long long syncs;             /* times the framer has synchronised */
+    unsigned long long accepted;          /* messages accepted: the newest is ring[(accepted - 1) % 8] */
+    unsigned long long rejected;          /* messages that ended without ZCZC or NNNN in front */
+    unsigned long long sync_tick;         /* of the message in progress */
+    unsigned long long last_accept_tick;
+    double   open[4];                     /* the open tick's sums: mark re, mark im, space re, space im */
+    double   hist[7][4];                  /* the last seven completed ticks' sums, oldest first */
+    unsigned ph;                          /* the bit clock, 0 ... 255 */
+    unsigned sh;                          /* the framer's 16-bit register */
+    unsigned nbit;                        /* bits since the last byte, 0 ... 7 (synchronised) */
+    unsigned msg_len;                     /* bytes of the message in progress */
+    unsigned run;                         /* ticks since the decision last changed, up to 255 */
+    unsigned char synced, prev_s, flags, ok;
+    unsigned char msg[FMD_SAME_MAX_BYTES];    /* the message in progress (bytes behind msg_len are stale) */
+    unsigned char reserved[4];
+    fmd_same_message ring[FMD_SAME_RING];
+} fmd_same_status;
+/* what fmd_same_encode makes */
+typedef struct {
+    int       fs;                 /* a multiple of 10 in 8000 ... 48000 */
+    int       repeats;            /* bursts, 1 ... 16 (a transmission has three) */
+    long long gap_frames;         /* silent frames behind every burst; negative = one second */
+    double    clock_ratio;        /* the sender's clock over nominal, in [0.9, 1.1]: bit rate and both tones move with it */
+    double    amplitude;          /* of the space tone in each rail, finite and >= 0 (the mid signal carries twice that) */
+    double    mark_db;            /* the mark tone's level against the space tone's, in [-40, 40] */
+} fmd_same_encode_config;
+#define FMD_SAME_VALID_ORG       1u
+#define FMD_SAME_VALID_EVENT     2u
+#define FMD_SAME_VALID_LOCATIONS 4u
+#define FMD_SAME_VALID_DURATION  8u
+#define FMD_SAME_VALID_TIME      16u
+#define FMD_SAME_VALID_CALLSIGN  32u
+typedef struct {
+    int      kind;                /* FMD_SAME_KIND_HEADER or FMD_SAME_KIND_EOM (then every other field is 0) */
+    unsigned valid;               /* FMD_SAME_VALID_* per field */
+    char     org[4], event[4];    /* NUL-terminated */
+    int      n_locations;
+    char     locations[FMD_SAME_MAX_LOCATIONS][8];   /* PSSCCC, NUL-terminated */
+    int      duration_min;        /* +TTTT as hours and minutes, in minutes */
+    int      day, hour, minute;   /* JJJHHMM: day of the year 1 ... 366, UTC */
+    char     callsign[12];        /* LLLLLLLL, NUL-terminated */
+} fmd_same_header;
+
+/* host-only (no GPU needed) */
+void fmd_same_default_params(fmd_same_params* p);
+/* `text` (len bytes in 1 ... 268, e.g. "ZCZC-WXR-TOR-039173+0030-1051700-KCLE/NWS-") as audio: per burst 16 bytes 0xAB and the text, least
+ * significant bit first, one bit per 6 fs / (3125 clock_ratio) frames; frame i of a burst stands u = i * clock_ratio * 3125 / (6 fs) bits
+ * in, and both rails carry (float)(a * sin(2 pi cyc frac(u))), cyc = 4 and a = amplitude * 10^(mark_db / 20) in a 1 bit, cyc = 3 and
+ * a = amplitude in a 0 bit.  Returns the number of frames of the whole (bursts and gaps); writes out [frames][2] where out is not NULL
+ * and cap (in frames) suffices, else FMD_ERR_SIZE; FMD_ERR_ARG for values outside the ranges above */
+long long fmd_same_encode(const fmd_same_encode_config* cfg, const char* text, int len, float* out, long long cap);
+/* one message's bytes -> its fields.  FMD_ERR_ARG unless it starts with ZCZC or NNNN; else FMD_OK with `valid` telling which fields
+ * were well formed (a malformed field is zeroed).  Whatever stands behind the call sign's closing `-` is ignored */
+int fmd_same_parse(const unsigned char* bytes, int len, fmd_same_header* out);
+/* n = 1 ... 3 messages of one kind in ascending sync_tick, each no more than 2.5 s (10416 ticks) plus its predecessor's own length
+ * (64 ticks a byte) behind its predecessor (else FMD_ERR_STATE): byte by byte two out of three.  out: the voted message with the first
+ * one's sync_tick; *corrected: bytes at which one copy was outvoted; *unresolved: bytes without a majority, where the first copy's
+ * stands (with two copies: every byte at which they differ).  The length is voted the same way */
+int fmd_same_vote(const fmd_same_message* msgs, int n, fmd_same_message* out, int* corrected, int* unresolved);
+
+int fmd_same_create(const fmd_same_config* cfg, fmd_same* out);
+int fmd_same_destroy(fmd_same d);
+/* everything of station `channel` (-1 = every station) as after create: counters, clock, framer, sums, ring, flags clear, ok = 1; its
+ * parameters are kept.  Waits for the decoder's earlier work */
+int fmd_same_reset(fmd_same d, int channel);
+/* the parameters of station `channel` (-1 = every station): ordered behind the decoder's earlier work; they apply from the next tick
+ * that ends (the record's ok at once).  FMD_ERR_ARG for values outside the ranges above, and nothing changes */
+int fmd_same_set_params(fmd_same d, int channel, const fmd_same_params* p);
+int fmd_same_get_params(fmd_same d, int channel, fmd_same_params* p);
+/* takes n frames of every station.  d_in [C][in_stride][2] f32 on the device, 8-byte aligned; d_active: [C] uint8 on the device,
+ * NULL = all: a station whose byte is 0 is skipped whole, and its two output bytes are left as they are.  d_flags, d_ok: [C] uint8 on
+ * the device, caller-owned, each may be NULL: behind its work on `stream` the call writes every other station's byte, also when n == 0.
+ * n < 0, n > in_stride, n > max_input_frames or a misaligned d_in return FMD_ERR_ARG and change nothing.  Asynchronous on `stream`;
+ * consecutive calls may use different streams (the library orders them). */
+int fmd_same_process_f32_dev(fmd_same d, const float* d_in, long long in_stride, long long n, const uint8_t* d_active, uint8_t* d_flags,
+                             uint8_t* d_ok, void* stream);
+/* out [C]; synchronises with the decoder's work */
+int fmd_same_get_status(fmd_same d, fmd_same_status* out);
+/* the device's own [C] records, for a consumer on the device: ordered behind the decoder's work on the stream of its last process
+ * call, valid until the next process call */
+int fmd_same_status_dev(fmd_same d, const fmd_same_status** d_status);
+const char* fmd_same_last_error(fmd_same d);
+
 #ifdef __cplusplus
 }
 #endif
