@@ -1409,6 +1409,17 @@ class AudioResampler(_Handle):
         import torch
         return self._run(self.L.fmd_resampler_process_pcm16_dev, x, n_in, torch.int16, out, stream)
 
+    def process_host(self, x, out: np.ndarray, n_in: int | None = None, stream=None) -> int:
+        """process() into a host array (fmd_resampler_process_f32_host): out [C, out_stride, 2] float32, C-contiguous; the first n_out frames
+        of every row are written, nothing behind them.  Synchronises `stream`; returns n_out."""
+        px, in_stride, n_in = _batch_input(x, self.n_channels, n_in, ("float32",), "frames")
+        if not (out.dtype == np.float32 and out.ndim == 3 and out.shape[0] == self.n_channels and out.shape[2] == 2 and out.flags.c_contiguous):
+            raise ValueError("out must be a C-contiguous float32 array [C, out_stride, 2]")
+        got = C.c_longlong(0)
+        self._check(self.L.fmd_resampler_process_f32_host(self.r, px, in_stride, n_in, out.ctypes.data_as(C.c_void_p), int(out.shape[1]), C.byref(got),
+                                                          C.c_void_p(_stream_ptr(stream, x.device))))
+        return got.value
+
 
 class AudioMixer(_Handle):
     """B output buses on the GPU (fmd_mixer_*), each one reference AudioMixer: bus b plays

@@ -544,7 +544,10 @@ int fmd_resampler_output_frames(fmd_resampler r, long long n_in, long long* n_ou
  * d_out [C][out_stride][2] on the device, out_stride >= the call's *n_out.  Asynchronous on `stream`; consecutive calls may use
  * different streams (the library orders them).  A call on a new n_in (reference method) uploads that length's index table once.
  * The pcm16 form writes the scraper's frames (fm_scraper.cpp:79-82: sample * (32767 * 0.95f), truncated toward zero): exactly
- * that conversion of the f32 form's output. */
+ * that conversion of the f32 form's output.  The product t is one fp32 multiply; for |t| < 2^31 the frame holds the low 16 bits
+ * of (int32_t)t, so it wraps past +-32768 as the reference's conversion does (no saturation: clamp before the call if wanted).
+ * NaN gives 0; +inf and t >= 2^31 give -1 and -inf and t <= -2^31 give 0 (the device's float-to-int conversion saturates to
+ * 0x7fffffff / 0x80000000 and the low 16 bits are kept). */
 int fmd_resampler_process_f32_dev(fmd_resampler r, const float* d_in, long long in_stride, long long n_in,
                                   float* d_out, long long out_stride, long long* n_out, void* stream);
 int fmd_resampler_process_pcm16_dev(fmd_resampler r, const float* d_in, long long in_stride, long long n_in,
