@@ -243,6 +243,18 @@ ADPCM_DEFAULT_BLOCK_FRAMES = 1017
 ADPCM_WAV_HEADER_BYTES = 60
 
 
+class FlacConfig(C.Structure):
+    _fields_ = [("n_channels", C.c_int), ("block_frames", C.c_int), ("sample_rate", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
+
+
+# include/fmdemod.h fmd_flac_status (80 bytes)
+FLAC_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("blocks", "<u8"), ("stream_samples", "<u8"), ("stream_bytes", "<u8"), ("clipped", "<u8", (2,)), ("nonfinite", "<u8"),
+                              ("streams", "<u4"), ("frame_number", "<u4"), ("min_frame_bytes", "<u4"), ("max_frame_bytes", "<u4"), ("fill", "<u4"), ("wrapped", "<u4")])
+assert FLAC_STATUS_DTYPE.itemsize == 80
+FLAC_DEFAULT_BLOCK_FRAMES = 4096
+FLAC_STREAM_HEADER_BYTES = 42
+
+
 class SameConfig(C.Structure):
     _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
 
@@ -499,6 +511,15 @@ def load_library():
     L.fmd_adpcm_create.argtypes = [C.POINTER(AdpcmConfig), C.POINTER(C.c_void_p)]
     L.fmd_adpcm_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
     L.fmd_adpcm_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_flac_frame_bound.argtypes = [C.c_int]
+    L.fmd_flac_max_bytes.argtypes = [C.c_int, C.c_longlong]
+    L.fmd_flac_max_bytes.restype = C.c_longlong
+    L.fmd_flac_stream_header.argtypes = [C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int)]
+    L.fmd_flac_decode.argtypes = [C.c_void_p, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.POINTER(C.c_longlong)]
+    L.fmd_flac_create.argtypes = [C.POINTER(FlacConfig), C.POINTER(C.c_void_p)]
+    L.fmd_flac_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fmd_flac_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fmd_debug_flac_set_frame_number.argtypes = [C.c_void_p, C.c_int, C.c_uint]
     L.fmd_same_default_params.argtypes = [C.POINTER(SameParams)]
     L.fmd_same_default_params.restype = None
     L.fmd_same_encode.argtypes = [C.POINTER(SameEncodeConfig), C.c_char_p, C.c_int, C.c_void_p, C.c_longlong]
@@ -510,13 +531,13 @@ def load_library():
     L.fmd_same_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SameParams)]
     L.fmd_same_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # what every side object declares alike
-    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "rdsdec"):
+    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "rdsdec"):
         getattr(L, f"fmd_{pre}_destroy").argtypes = [C.c_void_p]
         getattr(L, f"fmd_{pre}_last_error").restype = C.c_char_p
         getattr(L, f"fmd_{pre}_last_error").argtypes = [C.c_void_p]
-    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same"):
+    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac"):
         getattr(L, f"fmd_{pre}_reset").argtypes = [C.c_void_p, C.c_int]
-        if pre not in ("tonedet", "adpcm", "same"):               # (the tone detector, the encoder and the SAME decoder hold no peaks)
+        if pre not in ("tonedet", "adpcm", "same", "flac"):       # (the tone detector, the encoders and the SAME decoder hold no peaks)
             getattr(L, f"fmd_{pre}_reset_peaks").argtypes = [C.c_void_p, C.c_int]
         getattr(L, f"fmd_{pre}_get_status").argtypes = [C.c_void_p, C.c_void_p]
         getattr(L, f"fmd_{pre}_status_dev").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -2089,3 +2110,123 @@ class AdpcmEncoder(_Monitor):
         out, po, stride, nblocks, pn = self._outputs(out, nblocks, self.block_align, device, stream)
         self._check(self.L.fmd_adpcm_flush(self.e, int(channel), po, stride, pn, C.c_void_p(stream)))
         return out, nblocks
+
+
+def flac_frame_bound(block_frames: int = 0) -> int:
+    """fmd_flac_frame_bound (host only): the most bytes of a FLAC frame of `block_frames` frames (0 = the default 4096)"""
+    L = load_library()
+    rc = L.fmd_flac_frame_bound(int(block_frames))
+    if rc < 0:
+        raise _global_error(L, "fmd_flac", rc)
+    return rc
+
+
+def flac_max_bytes(block_frames: int, n: int) -> int:
+    """fmd_flac_max_bytes (host only): the most bytes a call of n frames writes for a station, rounded up to 4"""
+    L = load_library()
+    rc = L.fmd_flac_max_bytes(int(block_frames), int(n))
+    if rc < 0:
+        raise _global_error(L, "fmd_flac", int(rc))
+    return int(rc)
+
+
+def flac_stream_header(fs: int, block_frames: int = 0, total_samples: int = 0, min_frame_bytes: int = 0, max_frame_bytes: int = 0) -> bytes:
+    """fmd_flac_stream_header (host only): the 42 bytes `fLaC` + STREAMINFO in front of a stream's frames in a .flac file; zeros where
+    unknown; the MD5 signature is all zero, which the format reads as not computed"""
+    L = load_library()
+    out = (C.c_ubyte * FLAC_STREAM_HEADER_BYTES)()
+    n = C.c_int()
+    rc = L.fmd_flac_stream_header(int(fs), int(block_frames), int(total_samples), int(min_frame_bytes), int(max_frame_bytes), out, C.byref(n))
+    if rc != 0:
+        raise _global_error(L, "fmd_flac", rc)
+    return bytes(out[:n.value])
+
+
+def flac_decode(data, fs: int, block_frames: int = 0) -> np.ndarray:
+    """fmd_flac_decode (host only): one stream's FLAC frames (any uint8 array or bytes, no stream header) -> [frames, 2] int16; raises
+    FmdError(FMD_ERR_ARG) for anything but a whole, intact stream of this encoder's subset"""
+    L = load_library()
+    b = np.frombuffer(bytes(data), np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, np.uint8).reshape(-1)
+    n = C.c_longlong()
+    rc = L.fmd_flac_decode(b.ctypes.data_as(C.c_void_p), b.size, int(fs), int(block_frames), None, 0, C.byref(n))
+    if rc != 0:
+        raise _global_error(L, "fmd_flac", rc)
+    pcm = np.zeros((n.value, 2), np.int16)
+    rc = L.fmd_flac_decode(b.ctypes.data_as(C.c_void_p), b.size, int(fs), int(block_frames), pcm.ctypes.data_as(C.c_void_p), n.value, C.byref(n))
+    if rc != 0:
+        raise _global_error(L, "fmd_flac", rc)
+    return pcm
+
+
+class FlacEncoder(_Monitor):
+    """FLAC encoder of C stations' stereo audio on the GPU (fmd_flac_*): per station a lossless stream that decodes to exactly the 16-bit
+    PCM fmd_audio_pcm16_dev writes.  Feed it the same [C, n, 2] float32 CUDA tensors as AudioMixer and the monitors; it changes nothing in
+    them.  process() returns the [C, out_stride] uint8 rows with each station's completed FLAC frames back to back, the [C] int32 byte
+    counts and the [C] int32 frame counts; flush() ends the streams behind a short last frame.  status() returns FLAC_STATUS_DTYPE
+    records; flac_decode and flac_stream_header are the host's side."""
+    _prefix, _attr, _status_dtype = "fmd_flac", "e", FLAC_STATUS_DTYPE
+
+    def __init__(self, n_channels: int, block_frames: int = 0, sample_rate: int = 32000, max_input_frames: int = 1 << 16, device: int = -1):
+        cfg = FlacConfig(int(n_channels), int(block_frames), int(sample_rate), int(max_input_frames), device)
+        self._create("create", C.byref(cfg))
+        self.n_channels = int(n_channels)
+        self.block_frames = int(block_frames) or FLAC_DEFAULT_BLOCK_FRAMES
+        self.sample_rate = int(sample_rate)
+        self.frame_bound = flac_frame_bound(self.block_frames)
+
+    def reset_peaks(self, channel: int = -1):
+        raise AttributeError("the encoder holds no peaks")
+
+    def _outputs(self, out, nbytes, nframes, need: int, device, stream):
+        """(out, its pointer, out_stride, nbytes, its pointer, nframes, its pointer): out None = a new zeroed [C, need] tensor; a count
+        None = new, False = not written"""
+        import torch
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device) if stream else torch.cuda.default_stream(device)):
+            if out is None:
+                out = torch.zeros((self.n_channels, max(need, 4)), dtype=torch.uint8, device=device)
+            if nbytes is None:
+                nbytes = torch.zeros(self.n_channels, dtype=torch.int32, device=device)
+            if nframes is None:
+                nframes = torch.zeros(self.n_channels, dtype=torch.int32, device=device)
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and out.shape[0] == self.n_channels and out.stride(1) == 1):
+            raise ValueError("out must be a [C, out_stride] uint8 CUDA tensor with contiguous rows")
+        if out.shape[1] < need:
+            raise ValueError(f"out's rows hold {out.shape[1]} bytes; the call may write {need}")
+        ptrs = []
+        for name, t in (("nbytes", nbytes), ("nframes", nframes)):
+            if t is False:
+                ptrs.append((None, None))
+            elif not (t.is_cuda and t.dtype == torch.int32 and t.shape == (self.n_channels,) and t.is_contiguous()):
+                raise ValueError(f"{name} must be a contiguous [C] int32 CUDA tensor")
+            else:
+                ptrs.append((t, C.c_void_p(t.data_ptr())))
+        stride = out.stride(0) if self.n_channels > 1 else out.shape[1]
+        return out, C.c_void_p(out.data_ptr()), stride, ptrs[0][0], ptrs[0][1], ptrs[1][0], ptrs[1][1]
+
+    def process(self, x, n: int | None = None, active=None, out=None, nbytes=None, nframes=None, stream=None):
+        """takes the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
+        uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole: its row of out is kept, its counts are 0); out: the
+        [C, out_stride] uint8 CUDA tensor to write, out_stride a multiple of 4 and at least flac_max_bytes(S, n), None = a new zeroed
+        one of exactly that; nbytes, nframes: the [C] int32 CUDA tensors to write, None = new ones, False = not written.  Returns
+        (out, nbytes, nframes).  Asynchronous on `stream` (default: torch's current)."""
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32",), "frames")
+        pa, stream = _active_ptr(active, self.n_channels), _stream_ptr(stream, x.device)
+        need = ((self.block_frames - 1 + max(n, 0)) // self.block_frames * self.frame_bound + 3) // 4 * 4
+        out, po, stride, nbytes, pb, nframes, pf = self._outputs(out, nbytes, nframes, need, x.device, stream)
+        self._check(self.L.fmd_flac_process_f32_dev(self.e, px, in_stride, n, pa, po, stride, pb, pf, C.c_void_p(stream)))
+        return out, nbytes, nframes
+
+    def flush(self, channel: int = -1, out=None, nbytes=None, nframes=None, stream=None, device=None):
+        """fmd_flac_flush: ends the stream of station `channel` (-1 = of every station): a short last frame of the open block's frames
+        at out[c] where there are any, its bytes in nbytes[c] and 0 or 1 in nframes[c]; the other stations' rows and counts are kept.
+        out, nbytes, nframes as in process (None = new, zeroed).  Returns (out, nbytes, nframes)."""
+        import torch
+        device = device if device is not None else (out.device if out is not None and out is not False else torch.device("cuda", torch.cuda.current_device()))
+        stream = _stream_ptr(stream, device)
+        out, po, stride, nbytes, pb, nframes, pf = self._outputs(out, nbytes, nframes, (self.frame_bound + 3) // 4 * 4, device, stream)
+        self._check(self.L.fmd_flac_flush(self.e, int(channel), po, stride, pb, pf, C.c_void_p(stream)))
+        return out, nbytes, nframes
+
+    def debug_set_frame_number(self, channel: int, value: int):
+        """fmd_debug_flac_set_frame_number (include/fmdemod_flac_debug.h): a test hook"""
+        self._check(self.L.fmd_debug_flac_set_frame_number(self.e, int(channel), int(value)))

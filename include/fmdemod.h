@@ -1391,6 +1391,117 @@ int fmd_adpcm_status_dev(fmd_adpcm e, const fmd_adpcm_status** d_status);
 const char* fmd_adpcm_last_error(fmd_adpcm e);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * FLAC audio encoder (NOT part of the reference): lossless station recordings.  16-bit PCM is 128 KB/s per station at 32 kHz and the
+ * ADPCM encoder a quarter of that but lossy; this one writes, per station, a FLAC stream (RFC 9639, streamable subset, fixed block size)
+ * that decodes to exactly the PCM fmd_audio_pcm16_dev writes, in fewer bytes.  It reads the device array [C][in_stride][2] f32
+ * (interleaved L, R) that the mixer and the monitors read, changes nothing in it, and writes every station's completed FLAC frames,
+ * byte-packed, to a caller-owned device array.  Stereo only, 16 bits, fs 8000 ... 48000 Hz.
+ * The rules, restated in C by tests/cpp/flac_ref.c; all integer behind one fp32 multiply:
+ *   sample      q exactly as the ADPCM encoder's: t = x * (32767.0f * 0.95f), one fp32 multiply;  t NaN or +-inf: q = 0, nonfinite++;
+ *               otherwise (int)t truncated toward zero and clamped to int16, each clamp counting in the rail's clipped.
+ *   block       S = block_frames, a multiple of 64 in 64 ... 4608, default 4096.  A fixed-blocksize stream: blocking-strategy bit 0,
+ *               the frame number coded.  Per station the open block's q, its fill, the stream's next frame number and the counters live
+ *               in the encoder.  Stations may stand at different places in their blocks.
+ *   candidates  of a frame of n frames: L, R (16 bits), M = (L + R) >> 1 with an arithmetic shift (16 bits), Sd = L - R (17 bits).
+ *   subframe    of a candidate X with b bits a sample: all n samples equal -> CONSTANT, 8 + b bits.  Otherwise the fixed predictors'
+ *               residuals for the orders o = 0 ... omax = min(4, n - 1):  x[i];  x[i] - x[i-1];  x[i] - 2 x[i-1] + x[i-2];
+ *               x[i] - 3 x[i-1] + 3 x[i-2] - x[i-3];  x[i] - 4 x[i-1] + 6 x[i-2] - 4 x[i-3] + x[i-4].  A_o = sum over i >= omax of
+ *               |r_o[i]| in 64 bits; the order with the smallest A_o, ties to the lower order.  Rice coding method 00, parameters
+ *               0 ... 14, no escape partitions:  u = 2 r (r >= 0), -2 r - 1 (r < 0);  a sample costs (u >> k) + 1 + k bits.  Partition
+ *               orders p = 0 ... P, P the largest p <= 6 with 2^p dividing n and (n >> p) > o;  partition 0 holds (n >> p) - o
+ *               residuals;  each partition takes the k with the fewest bits, ties to the lower k;  the order p with the smallest
+ *               2 + 4 + sum(4 + bits), ties to the lower p.  FIXED costs 8 + o b + that, and is used only where strictly smaller than
+ *               VERBATIM's 8 + n b.  No wasted-bits detection, no LPC subframes.
+ *   stereo      the totals of the channel assignments 0001 (L, R), 1000 (L, Sd), 1001 (Sd, R), 1010 (M, Sd): the smallest, ties in
+ *               that order.
+ *   frame       FF F8;  block-size code: the table's where n has one, else 0110 (8 bits of n - 1) for n <= 256, else 0111 (16 bits);
+ *               sample-rate code: the table's where fs has one, else 1101 (16 bits of Hz);  the assignment;  sample size 100, reserved
+ *               0;  the frame number, UTF-8-like, 1 - 6 bytes;  the block size's and rate's extra bytes;  CRC-8 (polynomial 0x07, init
+ *               0);  the subframes, most significant bit first;  zero bits to a byte;  CRC-16 (polynomial 0x8005, init 0, not
+ *               reflected, big-endian).  Over "123456789" the CRC-8 is 0xF4 and the CRC-16 0xFEE8.
+ *   bound       fmd_flac_frame_bound(S) = 16 + 2 (1 + 2 S) + 2 bytes: no frame exceeds it, (L, R) as two VERBATIM subframes being
+ *               always a candidate.
+ *   streaming   a call of n frames completes (fill + n) / S FLAC frames for the station, writes them back to back from
+ *               d_out + c * out_stride on, their bytes to d_nbytes[c] and their number to d_nframes[c];  bytes of d_out behind them
+ *               are left as they are.  Nothing depends, bit for bit, on how the frames are split into calls, on streams, on the batch
+ *               or on the station's row.  Ordinary stores, no global atomics, no workgroup waits on another.
+ *   flush       ends the station's stream: with fill > 0 one short frame of exactly `fill` frames (the format allows a short last
+ *               frame: nothing is padded), then frame number 0, streams++, the stream's samples, bytes, min and max frame bytes 0;
+ *               the lifetime counters stay.  With fill = 0 only the new stream.  A station whose frame number would reach 2^31 starts
+ *               a new stream by itself, behind the frame numbered 2^31 - 1, and sets `wrapped` for good; a flush whose short frame is
+ *               that frame starts one stream, not two.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_flac_s* fmd_flac;
+typedef struct {
+    int       n_channels;         /* C: station rows of the input */
+    int       block_frames;       /* S: frames of a block, a multiple of 64 in 64 ... 4608; 0 = 4096 */
+    int       sample_rate;        /* fs in Hz, 8000 ... 48000: goes into every frame's header */
+    long long max_input_frames;   /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_flac_config;
+/* one per station, 80 bytes: frames at byte 0, blocks 8, stream_samples 16, stream_bytes 24, clipped 32, nonfinite 48, streams 56,
+ * frame_number 60, min_frame_bytes 64, max_frame_bytes 68, fill 72, wrapped 76 */
+typedef struct {
+    unsigned long long frames;           /* audio frames taken since reset */
+    unsigned long long blocks;           /* FLAC frames written since reset, the short ones of flushes among them */
+    unsigned long long stream_samples;   /* audio frames in the current stream's FLAC frames (the open block's are not among them) */
+    unsigned long long stream_bytes;     /* bytes of the current stream's FLAC frames */
+    unsigned long long clipped[2];       /* samples of L, R clamped to the 16-bit range */
+    unsigned long long nonfinite;        /* samples (of either rail) that were NaN or +-inf after the scale: encoded as 0 */
+    unsigned           streams;          /* streams ended since reset, by a flush or by the frame number's wrap */
+    unsigned           frame_number;     /* FLAC frames of the current stream: the next frame's number, below 2^31 */
+    unsigned           min_frame_bytes;  /* of the current stream's FLAC frames; 0 while it has none */
+    unsigned           max_frame_bytes;
+    unsigned           fill;             /* frames in the open block, 0 ... S - 1 */
+    unsigned           wrapped;          /* 1 once a stream has ended because its frame number would have reached 2^31 */
+} fmd_flac_status;
+#define FMD_FLAC_STREAM_HEADER_BYTES 42
+
+/* host-only (no GPU needed); block_frames as in the configuration (0 = 4096), FMD_ERR_ARG for any other value that is no valid S */
+/* the most bytes of a FLAC frame */
+int fmd_flac_frame_bound(int block_frames);
+/* ((S - 1 + n) / S) * fmd_flac_frame_bound(S), rounded up to 4: the most bytes a process call of n frames writes for a station,
+ * whatever its fill.  n in [0, 2^40] */
+long long fmd_flac_max_bytes(int block_frames, long long n);
+/* the FMD_FLAC_STREAM_HEADER_BYTES bytes in front of a stream's frames in a .flac file, *len = their number: `fLaC` and a last
+ * metadata block STREAMINFO with min = max block size = S, the frame sizes (0 = unknown), fs, 2 channels, 16 bits, total_samples
+ * (0 = unknown) and an MD5 signature of all zero, which the format reads as "not computed": a verifying decoder skips the check.
+ * FMD_ERR_ARG for fs outside 8000 ... 48000, total_samples outside [0, 2^36), frame bytes outside [0, 2^24) or min above max */
+int fmd_flac_stream_header(int fs, int block_frames, long long total_samples, int min_frame_bytes, int max_frame_bytes, uint8_t* out, int* len);
+/* the matching decoder of one stream's frames (no stream header), for this encoder's own subset: CONSTANT / VERBATIM / FIXED subframes,
+ * method 00, 16-bit stereo, every frame of S frames but a last shorter one.  pcm_out [cap][2] int16, interleaved; NULL with cap 0 only
+ * checks and counts.  *n_frames_out = the audio frames decoded.  Sync code, reserved bits, both CRCs, the frame numbers' sequence from
+ * 0, the codes' shortest forms and the decoded samples' range are checked: FMD_ERR_ARG on anything else, FMD_ERR_SIZE where pcm_out is
+ * too small; pcm_out may then hold the frames in front of the failure */
+int fmd_flac_decode(const uint8_t* bytes, long long len, int fs, int block_frames, int16_t* pcm_out, long long cap, long long* n_frames_out);
+
+int fmd_flac_create(const fmd_flac_config* cfg, fmd_flac* out);
+int fmd_flac_destroy(fmd_flac e);
+/* station `channel` (-1 = every station) as after create: counters 0, no open block, stream 0, frame number 0.  Waits for the
+ * encoder's earlier work */
+int fmd_flac_reset(fmd_flac e, int channel);
+/* takes n frames of every station.  d_in [C][in_stride][2] f32 on the device, 8-byte aligned; d_active: [C] uint8 on the device,
+ * NULL = all: a station whose byte is 0 is skipped whole, its row of d_out is left as it is and its counts are 0.  d_out: caller-owned
+ * bytes on the device, 4-byte aligned, station c's completed FLAC frames from d_out + c * out_stride on; out_stride in bytes, a
+ * multiple of 4 and at least fmd_flac_max_bytes(S, n).  d_nbytes, d_nframes: [C] int32 on the device, either may be NULL.  n < 0,
+ * n > in_stride, n > max_input_frames, a misaligned or null d_in or d_out or an out_stride that is too small or no multiple of 4
+ * return FMD_ERR_ARG and change nothing.  Asynchronous on `stream`; consecutive calls may use different streams (the library orders
+ * them). */
+int fmd_flac_process_f32_dev(fmd_flac e, const float* d_in, long long in_stride, long long n, const uint8_t* d_active, uint8_t* d_out,
+                             long long out_stride, int* d_nbytes, int* d_nframes, void* stream);
+/* ends the stream of station `channel` (-1 = of every station) as `flush` above says: 0 or 1 FLAC frame at d_out + c * out_stride, its
+ * bytes in d_nbytes[c] and 0 or 1 in d_nframes[c] (either may be NULL); other stations' rows and counts are left as they are.  d_out
+ * 4-byte aligned, out_stride a multiple of 4 and at least fmd_flac_max_bytes(S, 1), else FMD_ERR_ARG.  Asynchronous on `stream`,
+ * ordered like a process call */
+int fmd_flac_flush(fmd_flac e, int channel, uint8_t* d_out, long long out_stride, int* d_nbytes, int* d_nframes, void* stream);
+/* out [C]; synchronises with the encoder's work */
+int fmd_flac_get_status(fmd_flac e, fmd_flac_status* out);
+/* the device's own [C] records, for a consumer on the device: ordered behind the encoder's work on the stream of its last call, valid
+ * until the next call */
+int fmd_flac_status_dev(fmd_flac e, const fmd_flac_status** d_status);
+const char* fmd_flac_last_error(fmd_flac e);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * EAS SAME decoder (NOT part of the reference): which alert is on the air.  The tone detector says that the 853 + 960 Hz attention
  * signal is on a station; the machine-readable part in front of it -- three bursts of a SAME header (47 CFR 11.31), 520.83 bit/s AFSK
  * of `ZCZC-ORG-EEE-PSSCCC...+TTTT-JJJHHMM-LLLLLLLL-`, and three `NNNN` bursts at the alert's end -- says which.  It reads the device
