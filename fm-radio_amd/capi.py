@@ -255,6 +255,24 @@ FLAC_DEFAULT_BLOCK_FRAMES = 4096
 FLAC_STREAM_HEADER_BYTES = 42
 
 
+class LogmelConfig(C.Structure):
+    """include/fmdemod.h fmd_logmel_config"""
+    _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("win", C.c_int), ("hop", C.c_int), ("n_mels", C.c_int), ("f_min_hz", C.c_double),
+                ("f_max_hz", C.c_double), ("mel_scale", C.c_int), ("out_mode", C.c_int), ("log_floor", C.c_float), ("max_input_frames", C.c_longlong),
+                ("device", C.c_int)]
+
+
+class LogmelDesign(C.Structure):
+    _fields_ = [("n_bins", C.c_int), ("empty_bands", C.c_int)]
+
+
+# include/fmdemod.h fmd_logmel_status (32 bytes)
+LOGMEL_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("spectra", "<u8"), ("nonfinite", "<u8"), ("fill", "<u4"), ("reserved", "<u4")])
+assert LOGMEL_STATUS_DTYPE.itemsize == 32
+LOGMEL_SLANEY, LOGMEL_HTK = 0, 1
+LOGMEL_POWER, LOGMEL_LOG10 = 0, 1
+
+
 class SameConfig(C.Structure):
     _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
 
@@ -520,6 +538,15 @@ def load_library():
     L.fmd_flac_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fmd_flac_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
     L.fmd_debug_flac_set_frame_number.argtypes = [C.c_void_p, C.c_int, C.c_uint]
+    L.fmd_logmel_default_config.argtypes = [C.c_int, C.POINTER(LogmelConfig)]
+    L.fmd_logmel_design.argtypes = [C.POINTER(LogmelConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(LogmelDesign)]
+    L.fmd_logmel_bins.argtypes = [C.POINTER(LogmelConfig)]
+    L.fmd_logmel_max_frames.argtypes = [C.c_int, C.c_longlong]
+    L.fmd_logmel_max_frames.restype = C.c_longlong
+    L.fmd_logmel_flog10.argtypes = [C.c_float]
+    L.fmd_logmel_flog10.restype = C.c_float
+    L.fmd_logmel_create.argtypes = [C.POINTER(LogmelConfig), C.POINTER(C.c_void_p)]
+    L.fmd_logmel_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
     L.fmd_same_default_params.argtypes = [C.POINTER(SameParams)]
     L.fmd_same_default_params.restype = None
     L.fmd_same_encode.argtypes = [C.POINTER(SameEncodeConfig), C.c_char_p, C.c_int, C.c_void_p, C.c_longlong]
@@ -531,13 +558,13 @@ def load_library():
     L.fmd_same_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SameParams)]
     L.fmd_same_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # what every side object declares alike
-    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "rdsdec"):
+    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "rdsdec"):
         getattr(L, f"fmd_{pre}_destroy").argtypes = [C.c_void_p]
         getattr(L, f"fmd_{pre}_last_error").restype = C.c_char_p
         getattr(L, f"fmd_{pre}_last_error").argtypes = [C.c_void_p]
-    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac"):
+    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel"):
         getattr(L, f"fmd_{pre}_reset").argtypes = [C.c_void_p, C.c_int]
-        if pre not in ("tonedet", "adpcm", "same", "flac"):       # (the tone detector, the encoders and the SAME decoder hold no peaks)
+        if pre not in ("tonedet", "adpcm", "same", "flac", "logmel"):   # (the tone detector, the encoders, the SAME decoder and the log-mel front end hold no peaks)
             getattr(L, f"fmd_{pre}_reset_peaks").argtypes = [C.c_void_p, C.c_int]
         getattr(L, f"fmd_{pre}_get_status").argtypes = [C.c_void_p, C.c_void_p]
         getattr(L, f"fmd_{pre}_status_dev").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -2230,3 +2257,108 @@ class FlacEncoder(_Monitor):
     def debug_set_frame_number(self, channel: int, value: int):
         """fmd_debug_flac_set_frame_number (include/fmdemod_flac_debug.h): a test hook"""
         self._check(self.L.fmd_debug_flac_set_frame_number(self.e, int(channel), int(value)))
+
+
+def logmel_default_config(fs: int, **fields) -> LogmelConfig:
+    """fmd_logmel_default_config (host only): win = fs / 40 rounded up to a multiple of 16, hop = fs / 100, 80 Slaney bands from 0 Hz to
+    min(8000, fs / 2), log10 with floor 1e-10; `fields` then replace the named fields"""
+    L = load_library()
+    cfg = LogmelConfig()
+    rc = L.fmd_logmel_default_config(int(fs), C.byref(cfg))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_logmel", rc)
+    for k, v in fields.items():
+        if k not in dict(LogmelConfig._fields_):
+            raise TypeError(f"LogmelConfig has no field {k}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def logmel_max_frames(hop: int, n: int) -> int:
+    """fmd_logmel_max_frames (host only): (n + hop - 1) / hop, the most spectral frames a call of n frames completes for a station"""
+    L = load_library()
+    rc = L.fmd_logmel_max_frames(int(hop), int(n))
+    if rc < 0:
+        raise _global_error(L, "fmd_logmel", int(rc))
+    return int(rc)
+
+
+def logmel_design(cfg: LogmelConfig | None = None, fs: int = 32000, **fields):
+    """fmd_logmel_design (host only) of `cfg` (default: logmel_default_config(fs, **fields)): (w [win] float32, fb [n_mels, K] float32, K,
+    empty_bands); logmel_tables gives the cos / sin table too"""
+    w, tc, ts, fb, K, empty = logmel_tables(cfg, fs, **fields)
+    return w, fb, K, empty
+
+
+def logmel_tables(cfg: LogmelConfig | None = None, fs: int = 32000, **fields):
+    """as logmel_design, with the DFT's table: (w, tc [win], ts [win], fb, K, empty_bands)"""
+    L = load_library()
+    cfg = cfg if cfg is not None else logmel_default_config(fs, **fields)
+    K = L.fmd_logmel_bins(C.byref(cfg))
+    if K < 0:
+        raise _global_error(L, "fmd_logmel", K)
+    w, tc, ts = (np.zeros(cfg.win, np.float32) for _ in range(3))
+    fb = np.zeros((cfg.n_mels, K), np.float32)
+    d = LogmelDesign()
+    rc = L.fmd_logmel_design(C.byref(cfg), *(a.ctypes.data_as(C.c_void_p) for a in (w, tc, ts, fb)), C.byref(d))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_logmel", rc)
+    return w, tc, ts, fb, d.n_bins, d.empty_bands
+
+
+def logmel_flog10(x) -> np.ndarray:
+    """fmd_logmel_flog10 (host only) of every element of x: the fixed base-10 logarithm the kernel applies"""
+    L = load_library()
+    a = np.ascontiguousarray(x, np.float32)
+    return np.array([L.fmd_logmel_flog10(float(v)) for v in a.reshape(-1)], np.float32).reshape(a.shape)
+
+
+class LogMel(_Monitor):
+    """Log-mel front end of C stations' audio on the GPU (fmd_logmel_*): per station the log-mel spectrogram a model takes, kept
+    continuous across calls.  Feed it the same [C, n, 2] float32 CUDA tensors as AudioMixer and the monitors; it changes nothing in
+    them.  process() returns the [C, max_frames, n_mels] float32 rows (the completed spectral frames first, oldest first) and the [C]
+    int32 counts.  status() returns LOGMEL_STATUS_DTYPE records.  **config: the fields of LogmelConfig over logmel_default_config(fs)."""
+    _prefix, _attr, _status_dtype = "fmd_logmel", "g", LOGMEL_STATUS_DTYPE
+
+    def __init__(self, n_channels: int, fs: int = 32000, **config):
+        self.L = load_library()
+        self.g = None
+        self.cfg = logmel_default_config(fs, n_channels=int(n_channels), **config)
+        self._create("create", C.byref(self.cfg))
+        self.n_channels, self.fs = int(n_channels), int(fs)
+        self.win, self.hop, self.n_mels = self.cfg.win, self.cfg.hop, self.cfg.n_mels
+        self.n_bins = self.L.fmd_logmel_bins(C.byref(self.cfg))
+
+    def reset_peaks(self, channel: int = -1):
+        raise AttributeError("the front end holds no peaks")
+
+    def frame_time(self, t):
+        """the centre of spectral frame t (counted from the station's reset) in seconds"""
+        return (np.asarray(t, np.float64) * self.hop + self.win / 2) / self.fs
+
+    def process(self, x, n: int | None = None, active=None, out=None, nframes=None, stream=None):
+        """takes the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
+        uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole: its rows and its count are kept); out: the
+        [C, >= logmel_max_frames(hop, n), n_mels] float32 CUDA tensor to write, None = a new zeroed one of exactly that; nframes: the
+        [C] int32 CUDA tensor to write, None = a new one, False = not written.  Returns (out, nframes).  Asynchronous on `stream`
+        (default: torch's current)."""
+        import torch
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32",), "frames")
+        pa, stream = _active_ptr(active, self.n_channels), _stream_ptr(stream, x.device)
+        rows = (max(n, 0) + self.hop - 1) // self.hop
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=x.device) if stream else torch.cuda.default_stream(x.device)):
+            if out is None:
+                out = torch.zeros((self.n_channels, max(rows, 1), self.n_mels), dtype=torch.float32, device=x.device)
+            if nframes is None:
+                nframes = torch.zeros(self.n_channels, dtype=torch.int32, device=x.device)
+        if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and out.shape[0] == self.n_channels and out.shape[2] == self.n_mels
+                and out.stride(2) == 1 and out.stride(1) == self.n_mels):
+            raise ValueError("out must be a [C, max_frames, n_mels] float32 CUDA tensor with contiguous rows")
+        if out.shape[1] < rows:
+            raise ValueError(f"out holds {out.shape[1]} rows a station; the call may write {rows}")
+        if nframes is not False and not (nframes.is_cuda and nframes.dtype == torch.int32 and nframes.shape == (self.n_channels,) and nframes.is_contiguous()):
+            raise ValueError("nframes must be a contiguous [C] int32 CUDA tensor")
+        stride = out.stride(0) if self.n_channels > 1 else out.shape[1] * self.n_mels
+        pn = None if nframes is False else C.c_void_p(nframes.data_ptr())
+        self._check(self.L.fmd_logmel_process_f32_dev(self.g, px, in_stride, n, pa, C.c_void_p(out.data_ptr()), stride, pn, C.c_void_p(stream)))
+        return out, (None if nframes is False else nframes)

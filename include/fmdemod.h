@@ -1502,6 +1502,110 @@ int fmd_flac_status_dev(fmd_flac e, const fmd_flac_status** d_status);
 const char* fmd_flac_last_error(fmd_flac e);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Log-mel front end (NOT part of the reference): station audio as the features a model takes.  Transcription, speech / music / advert
+ * segmentation and fingerprinting models all start from a log-mel spectrogram: 25 ms Hann window, 10 ms hop, 80 mel bands from 0 to
+ * 8 kHz.  This object reads the device array [C][in_stride][2] f32 (interleaved L, R) that the mixer and the monitors read, changes
+ * nothing in it, keeps every station's window overlap across calls, and writes the completed spectral frames as rows of n_mels f32 to a
+ * caller-owned device array.  It is no spectrum display: its output is a tensor for a model (DESIGN.md §7 keeps the reference's GUI
+ * spectra out of scope, and that stays).
+ * The rules, restated in C by tests/cpp/logmel_ref.c.  N = win, every fused multiply-add is one fmaf, fp32 denormals are kept:
+ *   design      host, double, host libm (fmd_logmel_design):  w[n] = (float)(0.5 - 0.5 cos(2 pi n / N)), the periodic Hann window;
+ *               tc[j] = (float)cos(2 pi j / N), ts[j] = (float)sin(2 pi j / N), j = 0 ... N - 1;  K = min(N / 2, floor(f_max N / fs)) + 1
+ *               bins at f_k = k fs / N.  Mel scale 0 (Slaney): mel(f) = f / (200 / 3) below 1000 Hz, 15 + ln(f / 1000) / (ln(6.4) / 27)
+ *               from there, and its inverse;  1 (HTK): mel(f) = 2595 log10(1 + f / 700), inverse 700 (10^(m / 2595) - 1).  Edges
+ *               mu_i = mel(f_min) + i (mel(f_max) - mel(f_min)) / (n_mels + 1), F_i = mel^-1(mu_i), i = 0 ... n_mels + 1.  Weights
+ *               fb[j][k] = (float)(max(0, min((f_k - F_j) / (F_j+1 - F_j), (F_j+2 - f_k) / (F_j+2 - F_j+1))) s_j), s_j = 2 / (F_j+2 - F_j)
+ *               for Slaney (area normalisation) and 1 for HTK.  empty_bands counts the bands whose weights are all zero; create accepts
+ *               such a design.
+ *   sample      the sample index counts absolutely, in 64 bits, from the station's reset.  m = 0.5f * (L + R) in fp32: one rounding (the
+ *               halving is exact except into denormals, which are kept).
+ *   frame t     covers m[t hop ... t hop + N - 1]: no centring, no padding; its centre lies at (t hop + N / 2) / fs seconds, and it exists
+ *               once frames >= t hop + N.  xw[n] = w[n] * m[t hop + n], one fp32 rounding.  For every bin k < K, from +0 in ascending n:
+ *               re_k = fmaf(xw[n], tc[(k n) mod N], re_k),  im_k = fmaf(xw[n], ts[(k n) mod N], im_k).  P_k = fmaf(re_k, re_k, im_k * im_k).
+ *               For every band j, from +0 in ascending k over ALL k < K, zero weights included: mel_j = fmaf(fb[j][k], P_k, mel_j).
+ *               A non-finite sample makes the frame's bands non-finite as these chains give them: nothing is special-cased.
+ *   output      mode 0 writes mel_j; mode 1 writes flog10(v), v = mel_j > log_floor ? mel_j : (mel_j != mel_j ? mel_j : log_floor).  A NaN
+ *               is written as the quiet NaN 0x7fc00000 in both modes, whatever sign or payload the chains gave it.
+ *   flog10      a fixed algorithm (fm-radio_amd/csrc/fmd_logmel_math.h), no libm:  u = bits(x) - 0x3f3504f3;  e = (int)u >> 23;
+ *               f = bits((u & 0x7fffff) + 0x3f3504f3) - 1.0f (exact; 1 + f in [sqrt(1/2), sqrt(2)));  r = c11, then r = fmaf(f, r, c_i) for
+ *               i = 10 ... 1;  t = fmaf(f, r, C0lo);  lm = fmaf(f, C0hi, f * t);  y = fmaf(e, L2hi, fmaf(e, L2lo, lm)).  C0hi, C0lo, L2hi,
+ *               L2lo = 0x3ede5bd9, 0xb22d91af, 0x3e9a2000, 0x369a84fc;  c1 ... c11 = 0xbe5e5bd9, 0x3e143d3a, 0xbdde5bb4, 0x3db1e377,
+ *               0xbd9445b2, 0x3d7e1719, 0xbd5cc607, 0x3d446f9a, 0xbd41dcff, 0x3d3d35d2, 0xbccff948.  +inf gives +inf and NaN the argument.
+ *               Its argument is never below FLT_MIN.  Within 8 fp32 ulp of float64 log10 over every finite float >= FLT_MIN (measured
+ *               worst case: DESIGN.md §6n).
+ *   streaming   per station the object keeps the mono samples from the next uncompleted frame's start onward (at most N - 1) and the
+ *               32-byte record below.  A call of n frames completes T(frames + n) - T(frames) spectral frames of the station,
+ *               T(f) = f < N ? 0 : (f - N) / hop + 1, and writes them oldest first as rows of n_mels f32 from d_out + c * out_stride on
+ *               and their number to d_nframes[c]; floats behind the rows are left alone.  Nothing depends, bit for bit, on how the
+ *               frames are split into calls, on streams, on the batch or on the station's row.  Stations may stand at different places
+ *               in their windows.  Ordinary stores, no global atomics, no workgroup waits on another.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_logmel_s* fmd_logmel;
+typedef struct {
+    int       n_channels;         /* C: station rows of the input */
+    int       fs;                 /* the audio's rate in Hz, 8000 ... 48000 */
+    int       win;                /* N: frames of a window, a multiple of 16 in 64 ... 2048 */
+    int       hop;                /* frames from one window's start to the next, 16 ... win */
+    int       n_mels;             /* mel bands, 1 ... 128 */
+    double    f_min_hz;           /* 0 <= f_min_hz < f_max_hz <= fs / 2 */
+    double    f_max_hz;
+    int       mel_scale;          /* 0 = Slaney with area normalisation, 1 = HTK, unnormalised */
+    int       out_mode;           /* 0 = mel power, 1 = log10 */
+    float     log_floor;          /* finite and >= FLT_MIN */
+    long long max_input_frames;   /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_logmel_config;
+typedef struct {
+    int n_bins;                   /* K */
+    int empty_bands;              /* bands whose weights are all zero */
+} fmd_logmel_design_t;
+/* one per station, 32 bytes: frames at byte 0, spectra 8, nonfinite 16, fill 24, reserved 28 */
+typedef struct {
+    unsigned long long frames;    /* audio frames taken since reset */
+    unsigned long long spectra;   /* spectral frames written since reset: T(frames) */
+    unsigned long long nonfinite; /* spectral frames with a band that was +-inf or NaN */
+    unsigned           fill;      /* mono samples kept for the next frame: frames - spectra * hop, 0 ... N - 1 */
+    unsigned           reserved;
+} fmd_logmel_status;
+
+/* host-only (no GPU needed) */
+/* the usual geometry at the audio's own rate: win = fs / 40 rounded up to a multiple of 16, hop = fs / 100, 80 bands from 0 Hz to
+ * min(8000, fs / 2), Slaney, log10, floor 1e-10f, one station, max_input_frames 65536, the current device.  At 32 kHz win = 800 and
+ * hop = 320: the 201 bins of an 800-point DFT up to 8 kHz are the bin frequencies and the 25 ms window of 16 kHz / 400 / 160, with no
+ * resampler in front.  FMD_ERR_ARG for fs outside 8000 ... 48000 */
+int fmd_logmel_default_config(int fs, fmd_logmel_config* cfg);
+/* the design of a valid configuration: w [win], tc [win], ts [win], fb [n_mels][K] with K = fmd_logmel_bins(cfg); any of the four may be
+ * NULL and is then not written; *out (may be NULL) K and empty_bands.  FMD_ERR_ARG for an invalid configuration */
+int fmd_logmel_design(const fmd_logmel_config* cfg, float* w, float* tc, float* ts, float* fb, fmd_logmel_design_t* out);
+/* K of a valid configuration, FMD_ERR_ARG otherwise */
+int fmd_logmel_bins(const fmd_logmel_config* cfg);
+/* (n + hop - 1) / hop: the most spectral frames a process call of n frames completes for a station, wherever it stands in its window.
+ * FMD_ERR_ARG for hop outside 16 ... 2048 or n outside [0, 2^40] */
+long long fmd_logmel_max_frames(int hop, long long n);
+/* flog10 above, evaluated on the host */
+float fmd_logmel_flog10(float x);
+
+int fmd_logmel_create(const fmd_logmel_config* cfg, fmd_logmel* out);
+int fmd_logmel_destroy(fmd_logmel h);
+/* station `channel` (-1 = every station) as after create: counters 0, no samples kept; the configuration stays.  Waits for the
+ * object's earlier work */
+int fmd_logmel_reset(fmd_logmel h, int channel);
+/* takes n frames of every station.  d_in [C][in_stride][2] f32 on the device, 8-byte aligned; d_active: [C] uint8 on the device,
+ * NULL = all: a station whose byte is 0 is skipped whole, its rows and its count are left as they are.  d_out: caller-owned floats on
+ * the device, 4-byte aligned; out_stride in floats, at least fmd_logmel_max_frames(hop, n) * n_mels.  d_nframes: [C] int32 on the
+ * device, may be NULL.  n = 0 is valid.  n < 0, n > in_stride, n > max_input_frames, a null or misaligned d_in or d_out or a short
+ * out_stride return FMD_ERR_ARG and change nothing.  Asynchronous on `stream`; consecutive calls may use different streams (the library
+ * orders them). */
+int fmd_logmel_process_f32_dev(fmd_logmel h, const float* d_in, long long in_stride, long long n, const uint8_t* d_active, float* d_out,
+                               long long out_stride, int* d_nframes, void* stream);
+/* out [C]; synchronises with the object's work */
+int fmd_logmel_get_status(fmd_logmel h, fmd_logmel_status* out);
+/* the device's own [C] records, for a consumer on the device: ordered behind the object's work on the stream of its last call, valid
+ * until the next call */
+int fmd_logmel_status_dev(fmd_logmel h, const fmd_logmel_status** d_status);
+const char* fmd_logmel_last_error(fmd_logmel h);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * EAS SAME decoder (NOT part of the reference): which alert is on the air.  The tone detector says that the 853 + 960 Hz attention
  * signal is on a station; the machine-readable part in front of it -- three bursts of a SAME header (47 CFR 11.31), 520.83 bit/s AFSK
  * of `ZCZC-ORG-EEE-PSSCCC...+TTTT-JJJHHMM-LLLLLLLL-`, and three `NNNN` bursts at the alert's end -- says which.  It reads the device
