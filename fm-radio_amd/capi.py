@@ -273,6 +273,21 @@ LOGMEL_SLANEY, LOGMEL_HTK = 0, 1
 LOGMEL_POWER, LOGMEL_LOG10 = 0, 1
 
 
+class FprintConfig(C.Structure):
+    """include/fmdemod.h fmd_fprint_config"""
+    _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("hop", C.c_int), ("n_sub", C.c_int), ("n_bands", C.c_int), ("f_min_hz", C.c_double),
+                ("f_max_hz", C.c_double), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
+
+
+class FprintDesign(C.Structure):
+    _fields_ = [("n_bins", C.c_int), ("first_bin", C.c_int)]
+
+
+# include/fmdemod.h fmd_fprint_status (32 bytes)
+FPRINT_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("prints", "<u8"), ("nonfinite", "<u8"), ("fill", "<u4"), ("reserved", "<u4")])
+assert FPRINT_STATUS_DTYPE.itemsize == 32
+
+
 class SameConfig(C.Structure):
     _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
 
@@ -547,6 +562,16 @@ def load_library():
     L.fmd_logmel_flog10.restype = C.c_float
     L.fmd_logmel_create.argtypes = [C.POINTER(LogmelConfig), C.POINTER(C.c_void_p)]
     L.fmd_logmel_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_fprint_default_config.argtypes = [C.c_int, C.POINTER(FprintConfig)]
+    L.fmd_fprint_design.argtypes = [C.POINTER(FprintConfig), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FprintDesign)]
+    L.fmd_fprint_bins.argtypes = [C.POINTER(FprintConfig)]
+    L.fmd_fprint_max_prints.argtypes = [C.c_int, C.c_longlong]
+    L.fmd_fprint_max_prints.restype = C.c_longlong
+    L.fmd_fprint_state_bytes.argtypes = [C.POINTER(FprintConfig), C.c_int]
+    L.fmd_fprint_state_bytes.restype = C.c_longlong
+    L.fmd_fprint_create.argtypes = [C.POINTER(FprintConfig), C.POINTER(C.c_void_p)]
+    L.fmd_fprint_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                             C.c_longlong, C.c_void_p]
     L.fmd_same_default_params.argtypes = [C.POINTER(SameParams)]
     L.fmd_same_default_params.restype = None
     L.fmd_same_encode.argtypes = [C.POINTER(SameEncodeConfig), C.c_char_p, C.c_int, C.c_void_p, C.c_longlong]
@@ -558,13 +583,13 @@ def load_library():
     L.fmd_same_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SameParams)]
     L.fmd_same_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # what every side object declares alike
-    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "rdsdec"):
+    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "fprint", "rdsdec"):
         getattr(L, f"fmd_{pre}_destroy").argtypes = [C.c_void_p]
         getattr(L, f"fmd_{pre}_last_error").restype = C.c_char_p
         getattr(L, f"fmd_{pre}_last_error").argtypes = [C.c_void_p]
-    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel"):
+    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "fprint"):
         getattr(L, f"fmd_{pre}_reset").argtypes = [C.c_void_p, C.c_int]
-        if pre not in ("tonedet", "adpcm", "same", "flac", "logmel"):   # (the tone detector, the encoders, the SAME decoder and the log-mel front end hold no peaks)
+        if pre not in ("tonedet", "adpcm", "same", "flac", "logmel", "fprint"):   # (the tone detector, the encoders, the SAME decoder, the log-mel front end and the fingerprinter hold no peaks)
             getattr(L, f"fmd_{pre}_reset_peaks").argtypes = [C.c_void_p, C.c_int]
         getattr(L, f"fmd_{pre}_get_status").argtypes = [C.c_void_p, C.c_void_p]
         getattr(L, f"fmd_{pre}_status_dev").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -2362,3 +2387,149 @@ class LogMel(_Monitor):
         pn = None if nframes is False else C.c_void_p(nframes.data_ptr())
         self._check(self.L.fmd_logmel_process_f32_dev(self.g, px, in_stride, n, pa, C.c_void_p(out.data_ptr()), stride, pn, C.c_void_p(stream)))
         return out, (None if nframes is False else nframes)
+
+
+def fprint_default_config(fs: int, **fields) -> FprintConfig:
+    """fmd_fprint_default_config (host only): hop = fs * 0.0115 rounded to a multiple of 16, 32 sub-blocks a window, 33 bands from 300 to
+    2000 Hz; `fields` then replace the named fields"""
+    L = load_library()
+    cfg = FprintConfig()
+    rc = L.fmd_fprint_default_config(int(fs), C.byref(cfg))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_fprint", rc)
+    for k, v in fields.items():
+        if k not in dict(FprintConfig._fields_):
+            raise TypeError(f"FprintConfig has no field {k}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def fprint_max_prints(hop: int, n: int) -> int:
+    """fmd_fprint_max_prints (host only): (n + hop - 1) / hop, the most words a call of n frames completes for a station"""
+    L = load_library()
+    rc = L.fmd_fprint_max_prints(int(hop), int(n))
+    if rc < 0:
+        raise _global_error(L, "fmd_fprint", int(rc))
+    return int(rc)
+
+
+def fprint_state_bytes(cfg: FprintConfig, channels: int) -> int:
+    """fmd_fprint_state_bytes (host only): the device memory an object of `channels` stations holds"""
+    L = load_library()
+    rc = L.fmd_fprint_state_bytes(C.byref(cfg), int(channels))
+    if rc < 0:
+        raise _global_error(L, "fmd_fprint", int(rc))
+    return int(rc)
+
+
+def fprint_design(cfg: FprintConfig | None = None, fs: int = 32000, **fields):
+    """fmd_fprint_design (host only) of `cfg` (default: fprint_default_config(fs, **fields)): (bc [hop, K] float32, bs [hop, K] float32,
+    wc [n_sub], ws [n_sub], edges [n_bands + 1] int32, K, first_bin)"""
+    L = load_library()
+    cfg = cfg if cfg is not None else fprint_default_config(fs, **fields)
+    K = L.fmd_fprint_bins(C.byref(cfg))
+    if K < 0:
+        raise _global_error(L, "fmd_fprint", K)
+    bc, bs = (np.zeros((cfg.hop, K), np.float32) for _ in range(2))
+    wc, ws = (np.zeros(cfg.n_sub, np.float32) for _ in range(2))
+    edges = np.zeros(cfg.n_bands + 1, np.int32)
+    d = FprintDesign()
+    rc = L.fmd_fprint_design(C.byref(cfg), *(a.ctypes.data_as(C.c_void_p) for a in (bc, bs, wc, ws, edges)), C.byref(d))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_fprint", rc)
+    return bc, bs, wc, ws, edges, d.n_bins, d.first_bin
+
+
+def _fprint_words(a, n_bits: int) -> np.ndarray:
+    a = np.ascontiguousarray(a, np.uint32).reshape(-1)
+    if not 1 <= n_bits <= 32:
+        raise ValueError("n_bits outside 1 ... 32")
+    return a
+
+
+def fprint_ber(a, b, n_bits: int = 32) -> float:
+    """the bit error rate between two equally long runs of words (host, numpy): differing bits among the top n_bits of each word, over
+    their number.  Identical programmes give a few per cent, unrelated ones about 0.5; the paper's threshold is 0.35"""
+    a, b = _fprint_words(a, n_bits), _fprint_words(b, n_bits)
+    if a.size != b.size or a.size == 0:
+        raise ValueError("two runs of the same, non-zero length")
+    x = (a ^ b) >> np.uint32(32 - n_bits)
+    return float(np.unpackbits(x.view(np.uint8)).sum()) / (a.size * n_bits)
+
+
+def fprint_match(query, reference, n_bits: int = 32):
+    """where `query` lies in `reference` (host, numpy): (offset, ber), the offset in words 0 ... len(reference) - len(query) with the
+    smallest bit error rate over the query's whole length, the first such, and that rate.  That rate is what a caller compares with the
+    paper's 0.35"""
+    q, r = _fprint_words(query, n_bits), _fprint_words(reference, n_bits)
+    if q.size == 0 or r.size < q.size:
+        raise ValueError("the reference must be at least as long as the non-empty query")
+    win = np.lib.stride_tricks.sliding_window_view(r, q.size)
+    x = (win ^ q[None, :]) >> np.uint32(32 - n_bits)
+    errs = np.unpackbits(np.ascontiguousarray(x).view(np.uint8), axis=1).sum(axis=1)
+    at = int(np.argmin(errs))
+    return at, float(errs[at]) / (q.size * n_bits)
+
+
+class Fingerprinter(_Monitor):
+    """Audio fingerprinter of C stations' audio on the GPU (fmd_fprint_*): per station the Haitsma-Kalker robust hash, one uint32 word a
+    hop, kept continuous across calls.  Feed it the same [C, n, 2] float32 CUDA tensors as AudioMixer and the monitors; it changes nothing
+    in them.  process() returns the [C, max_prints] words (int32 tensors holding the uint32 bit patterns; the completed words first,
+    oldest first) and the [C] int32 counts.  status() returns FPRINT_STATUS_DTYPE records.  **config: the fields of FprintConfig over
+    fprint_default_config(fs)."""
+    _prefix, _attr, _status_dtype = "fmd_fprint", "g", FPRINT_STATUS_DTYPE
+
+    def __init__(self, n_channels: int, fs: int = 32000, **config):
+        self.L = load_library()
+        self.g = None
+        self.cfg = fprint_default_config(fs, n_channels=int(n_channels), **config)
+        self._create("create", C.byref(self.cfg))
+        self.n_channels, self.fs = int(n_channels), int(fs)
+        self.hop, self.n_sub, self.n_bands, self.n_bits = self.cfg.hop, self.cfg.n_sub, self.cfg.n_bands, self.cfg.n_bands - 1
+        self.n_bins = self.L.fmd_fprint_bins(C.byref(self.cfg))
+        self.state_bytes = fprint_state_bytes(self.cfg, self.n_channels)
+
+    def reset_peaks(self, channel: int = -1):
+        raise AttributeError("the fingerprinter holds no peaks")
+
+    def word_time(self, i):
+        """the start of word i (counted from the station's reset) in seconds: sample (i + 1) hop"""
+        return (np.asarray(i, np.float64) + 1.0) * self.hop / self.fs
+
+    def process(self, x, n: int | None = None, active=None, out=None, nprints=None, energy=None, stream=None):
+        """takes the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
+        uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole: its state, words and count are kept); out: the
+        [C, >= fprint_max_prints(hop, n)] int32 CUDA tensor to write, None = a new zeroed one of exactly that; nprints: the [C] int32
+        CUDA tensor to write, None = a new one, False = not written; energy: None = not written, True = a new zeroed
+        [C, max_prints, n_bands] float32 tensor, or such a tensor.  Returns (out, nprints), or (out, nprints, energy) where energy
+        was asked for.  Asynchronous on `stream` (default: torch's current)."""
+        import torch
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32",), "frames")
+        pa, stream = _active_ptr(active, self.n_channels), _stream_ptr(stream, x.device)
+        rows = (max(n, 0) + self.hop - 1) // self.hop
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=x.device) if stream else torch.cuda.default_stream(x.device)):
+            if out is None:
+                out = torch.zeros((self.n_channels, max(rows, 1)), dtype=torch.int32, device=x.device)
+            if nprints is None:
+                nprints = torch.zeros(self.n_channels, dtype=torch.int32, device=x.device)
+            if energy is True:
+                energy = torch.zeros((self.n_channels, max(rows, 1), self.n_bands), dtype=torch.float32, device=x.device)
+        if not (out.is_cuda and out.dtype == torch.int32 and out.dim() == 2 and out.shape[0] == self.n_channels and out.stride(1) == 1):
+            raise ValueError("out must be a [C, max_prints] int32 CUDA tensor with contiguous rows")
+        if out.shape[1] < rows:
+            raise ValueError(f"out holds {out.shape[1]} words a station; the call may write {rows}")
+        if nprints is not False and not (nprints.is_cuda and nprints.dtype == torch.int32 and nprints.shape == (self.n_channels,) and nprints.is_contiguous()):
+            raise ValueError("nprints must be a contiguous [C] int32 CUDA tensor")
+        pe, estride = None, 0
+        if energy is not None:
+            if not (energy.is_cuda and energy.dtype == torch.float32 and energy.dim() == 3 and energy.shape[0] == self.n_channels and energy.shape[2] == self.n_bands
+                    and energy.stride(2) == 1 and energy.stride(1) == self.n_bands):
+                raise ValueError("energy must be a [C, max_prints, n_bands] float32 CUDA tensor with contiguous rows")
+            if energy.shape[1] < rows:
+                raise ValueError(f"energy holds {energy.shape[1]} rows a station; the call may write {rows}")
+            pe, estride = C.c_void_p(energy.data_ptr()), (energy.stride(0) if self.n_channels > 1 else energy.shape[1] * self.n_bands)
+        stride = out.stride(0) if self.n_channels > 1 else out.shape[1]
+        pn = None if nprints is False else C.c_void_p(nprints.data_ptr())
+        self._check(self.L.fmd_fprint_process_f32_dev(self.g, px, in_stride, n, pa, C.c_void_p(out.data_ptr()), stride, pn, pe, estride, C.c_void_p(stream)))
+        res = (out, None if nprints is False else nprints)
+        return res if energy is None else res + (energy,)

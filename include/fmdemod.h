@@ -1762,6 +1762,115 @@ int fmd_same_get_status(fmd_same d, fmd_same_status* out);
 int fmd_same_status_dev(fmd_same d, const fmd_same_status** d_status);
 const char* fmd_same_last_error(fmd_same d);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Audio fingerprinter (NOT part of the reference): which programme is on a station.  The robust hash of Haitsma and Kalker ("A Highly
+ * Robust Audio Fingerprinting System", ISMIR 2002): one 32-bit word per hop of 11.5 ms, each bit the sign of an energy difference across
+ * neighbouring bands and neighbouring frames, compared by bit error rate (BER) over a few hundred words: 344 bytes a second and station.
+ * This object reads the device array [C][in_stride][2] f32 (interleaved L, R) that the mixer and the monitors read, changes nothing in
+ * it, keeps every station's state across calls, and writes the completed words as uint32 rows to a caller-owned device array.  The
+ * window is R = n_sub hops long, so every hop-sized sub-block is transformed ONCE and a frame is assembled from R kept sub-block spectra.
+ * The rules, restated in C by tests/cpp/fprint_ref.c.  H = hop, R = n_sub, N = R H, B = n_bands; every fused multiply-add is one fmaf,
+ * fp32 denormals are kept:
+ *   design      host, double, host libm (fmd_fprint_design), each value rounded once to f32.  Band edges f_b = f_min (f_max / f_min)^(b / B),
+ *               b = 0 ... B (pow);  bin edges k_b = floor(f_b N / fs + 0.5);  band b is the bins [k_b, k_b+1).  Valid: every band non-empty
+ *               (k_b < k_b+1), k_0 >= 1 and k_B <= N / 2 - 1; else FMD_ERR_ARG with the reason.  K = k_B - k_0 + 2 bins are transformed,
+ *               k_0 - 1 ... k_B: one more on each side for the window.  Sub-block basis for n < H and those bins:
+ *               bc[n][k] = (float)cos(phi), bs[n][k] = (float)(-sin(phi)), phi = 2 pi ((k n) mod N) / N.  Frame twiddles for q < R:
+ *               wc[q] = (float)cos(2 pi q / R), ws[q] = (float)sin(2 pi q / R), but at the multiples of R / 4 exactly 1, 0, -1, 0 and
+ *               0, 1, 0, -1.
+ *   sample      the sample index counts absolutely, in 64 bits, from the station's reset.  m = 0.5f * (L + R): one rounding.
+ *   sub-block g covers m[g H ... g H + H - 1].  Per bin, from +0 in ascending n:  Sr = fmaf(m[g H + n], bc[n][k], Sr),
+ *               Si = fmaf(m[g H + n], bs[n][k], Si).
+ *   frame t     covers sub-blocks t ... t + R - 1 (no centring, no padding).  Per bin, from +0 in ascending j = 0 ... R - 1, with
+ *               q = (k j) mod R and S = S of sub-block t + j:  re = fmaf(Sr, wc[q], re);  re = fmaf(Si, ws[q], re);
+ *               im = fmaf(Si, wc[q], im);  im = fmaf(-Sr, ws[q], im).  That is X = sum_j e^(-2 pi i k j / R) S_j, the N-point DFT.
+ *   window      the periodic Hann window as three taps, for k = k_0 ... k_B - 1 and for re and im alike:
+ *               Xw = fmaf(-0.25f, X[k-1] + X[k+1], 0.5f * X[k]);  P_k = fmaf(Xw_re, Xw_re, Xw_im * Xw_im).
+ *   band        E_t[b], from +0 in ascending k over [k_b, k_b+1):  E = E + P_k.
+ *   word        for t >= 1 and b < B - 1:  d = (E_t[b] - E_t[b+1]) - (E_t-1[b] - E_t-1[b+1]), every operation rounded to f32.  Bit b of
+ *               word t is d > 0 (a NaN compares false), stored at position 31 - b; the unused low bits are 0.  `nonfinite` counts
+ *               the words one of whose 2 B energies E_t[.], E_t-1[.] is +-inf or NaN.  In d_energy a NaN is written as the quiet NaN
+ *               0x7fc00000, whatever sign or payload the chains gave it; nothing else is special-cased.
+ *   streaming   after f frames a station has s = f / H sub-blocks and prints = max(0, s - R) words: word i compares frames i + 1 and
+ *               i and starts at sample (i + 1) H; the first word exists once f = (R + 1) H.  Per station the object keeps the carried
+ *               mono samples (fewer than H), the last R - 1 sub-block spectra, E of the last frame and the 32-byte record below.
+ *               A call of n frames writes the newly completed words, oldest first, from d_out + c * out_stride on and their number
+ *               to d_nprints[c]: at most fmd_fprint_max_prints(hop, n); the slots behind them are left alone.  d_energy (optional)
+ *               receives E_t of the same frames as rows of B f32.  Nothing depends, bit for bit, on how the frames are split into
+ *               calls, on streams, on the batch or on the station's row.  Ordinary stores, no global atomics, no workgroup waits on
+ *               another.
+ *   memory      the kept spectra take (R - 1) * 2 * Kp * 4 bytes a station, Kp = K rounded up to a multiple of 16: at the default
+ *               geometry at 32 kHz (K = 628) 158 720 bytes, 0.65 GB for 4096 stations; a per-call scratch of up to 64 KB a station comes
+ *               on top (0.13 GB for 4096 stations at max_input_frames 2048).  fmd_fprint_state_bytes reports the whole.  A call longer
+ *               than the scratch holds is cut into pieces inside the library, which by the rule above changes nothing.
+ * Not built: the paper's reliability ordering of bits, a database or search on the device, resampling to 5 kHz, per-station
+ * configurations, overlapping or weighted bands.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_fprint_s* fmd_fprint;
+typedef struct {
+    int       n_channels;         /* C: station rows of the input */
+    int       fs;                 /* the audio's rate in Hz, 8000 ... 48000 */
+    int       hop;                /* H: frames of a sub-block and between words, a multiple of 16 in 16 ... 1024 */
+    int       n_sub;              /* R: sub-blocks of a window, one of 4, 8, 16, 32 */
+    int       n_bands;            /* B: 2 ... 33; a word has B - 1 bits */
+    double    f_min_hz;           /* 0 < f_min_hz < f_max_hz */
+    double    f_max_hz;
+    long long max_input_frames;   /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_fprint_config;
+typedef struct {
+    int n_bins;                   /* K = k_B - k_0 + 2 */
+    int first_bin;                /* k_0 - 1: the DFT bin of column 0 of bc and bs */
+} fmd_fprint_design_t;
+/* one per station, 32 bytes: frames at byte 0, prints 8, nonfinite 16, fill 24, reserved 28 */
+typedef struct {
+    unsigned long long frames;    /* audio frames taken since reset */
+    unsigned long long prints;    /* words written since reset: max(0, frames / H - R) */
+    unsigned long long nonfinite; /* words with an energy that was +-inf or NaN */
+    unsigned           fill;      /* mono samples carried to the next sub-block: frames mod H */
+    unsigned           reserved;
+} fmd_fprint_status;
+
+/* host-only (no GPU needed) */
+/* the paper's geometry at the audio's own rate, with no resampler in front: hop = fs * 0.0115 rounded to a multiple of 16 (368 at
+ * 32 kHz), n_sub = 32 (a window of 0.368 s), 33 bands from 300 to 2000 Hz, one station, max_input_frames 65536, the current device.
+ * FMD_ERR_ARG for fs outside 8000 ... 48000 */
+int fmd_fprint_default_config(int fs, fmd_fprint_config* cfg);
+/* the design of a valid configuration: bc, bs [hop][K], wc, ws [n_sub], edges [n_bands + 1] (the DFT bins k_b) with
+ * K = fmd_fprint_bins(cfg); any of the five may be NULL and is then not written; *out may be NULL.  FMD_ERR_ARG for an invalid
+ * configuration or design, and then nothing is written */
+int fmd_fprint_design(const fmd_fprint_config* cfg, float* bc, float* bs, float* wc, float* ws, int* edges, fmd_fprint_design_t* out);
+/* K of a valid configuration, FMD_ERR_ARG otherwise */
+int fmd_fprint_bins(const fmd_fprint_config* cfg);
+/* (n + hop - 1) / hop: the most words a process call of n frames completes for a station, wherever it stands in its sub-block.
+ * FMD_ERR_ARG for hop outside 16 ... 1024 or n outside [0, 2^40] */
+long long fmd_fprint_max_prints(int hop, long long n);
+/* the bytes of device memory an object of `channels` stations holds (kept spectra, scratch, carries, energies, records, design);
+ * FMD_ERR_ARG for an invalid configuration or channels <= 0 */
+long long fmd_fprint_state_bytes(const fmd_fprint_config* cfg, int channels);
+
+/* FMD_ERR_DEVICE where the device memory (fmd_fprint_state_bytes) cannot be had */
+int fmd_fprint_create(const fmd_fprint_config* cfg, fmd_fprint* out);
+int fmd_fprint_destroy(fmd_fprint h);
+/* station `channel` (-1 = every station) as after create: counters 0, nothing kept; the configuration stays.  Waits for the object's
+ * earlier work */
+int fmd_fprint_reset(fmd_fprint h, int channel);
+/* takes n frames of every station.  d_in [C][in_stride][2] f32 on the device, 8-byte aligned; d_active: [C] uint8 on the device,
+ * NULL = all: a station whose byte is 0 is skipped whole: its state, its words, its energies and its count are left as they are.
+ * d_out: caller-owned uint32 on the device, 4-byte aligned; out_stride in words, at least fmd_fprint_max_prints(hop, n).  d_nprints:
+ * [C] int32 on the device, may be NULL.  d_energy: caller-owned f32 on the device, 4-byte aligned, may be NULL; energy_stride in
+ * floats, at least fmd_fprint_max_prints(hop, n) * n_bands.  n = 0 is valid.  n < 0, n > in_stride, n > max_input_frames, a null or
+ * misaligned d_in or d_out, a misaligned d_energy or a short stride return FMD_ERR_ARG and change nothing.  Asynchronous on `stream`;
+ * consecutive calls may use different streams (the library orders them). */
+int fmd_fprint_process_f32_dev(fmd_fprint h, const float* d_in, long long in_stride, long long n, const uint8_t* d_active, uint32_t* d_out,
+                               long long out_stride, int* d_nprints, float* d_energy, long long energy_stride, void* stream);
+/* out [C]; synchronises with the object's work */
+int fmd_fprint_get_status(fmd_fprint h, fmd_fprint_status* out);
+/* the device's own [C] records, for a consumer on the device: ordered behind the object's work on the stream of its last call, valid
+ * until the next call */
+int fmd_fprint_status_dev(fmd_fprint h, const fmd_fprint_status** d_status);
+const char* fmd_fprint_last_error(fmd_fprint h);
+
 #ifdef __cplusplus
 }
 #endif
