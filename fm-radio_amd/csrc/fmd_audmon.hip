@@ -4,13 +4,11 @@
 // the station audio [C][in_stride][2] f32 that the resampler, the mixer and the loudness meter read, read in place; at an interval's end
 // the five hysteresis detectors (silence, left lost, right lost, antiphase, mono), and at a call's end the [C] flags and ok bytes.
 //
-// One kernel per call, k_audmon.  Interleaved L, R f32 has the byte layout of the carrier squelch's cf32, and k_squelch's geometry
-// carries over: one wavefront per station over rows of 256 consecutive frames that start at a multiple of 256 of r, r the frame's place
-// in its interval; lane l loads frames 4 l ... 4 l + 3 with two 16-byte non-temporal loads, four rows in registers ahead of the row it
-// works on.  With NP = 64 and j = (r >> 2) & 63 lane l owns exactly partial l of each of the three sums and adds its four terms of a row
-// in ascending r.  A frame outside the segment at hand is not loaded and reads as (+0, +0), which changes no partial (fma(+0, +0, s) = s:
-// a partial is never -0) and no peak.  An interval's end is wave-uniform: the partials fold by cross-lane moves in the contract's halving
-// order, and lane 0 alone writes the ring, runs the detectors on the station's record and stores, with ordinary stores.  The open
+// One kernel per call, k_audmon, on the row walk of fmd_rows.h (one wavefront per station, rows of 256 frames, four rows in registers
+// ahead): interleaved L, R f32 has the byte layout of the carrier squelch's cf32.  With NP = 64 and j = (r >> 2) & 63 lane l owns exactly
+// partial l of each of the three sums and adds its four terms of a row in ascending r; a frame that reads as (+0, +0) changes no partial
+// (fma(+0, +0, s) = s: a partial is never -0) and no peak.  At an interval's end the partials fold by cross-lane moves in the contract's
+// halving order, and lane 0 alone writes the ring, runs the detectors on the station's record and stores, with ordinary stores.  The open
 // interval's 1.5 KB of partials are read at the call's start and written at its end.  No atomics, no LDS, no scratch.
 //
 // Denormals: fp64 and fp32 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
@@ -22,6 +20,7 @@
 #include <vector>
 
 #include "fmd_audmon_design.h"
+#include "fmd_rows.h"
 #include "fmd_side.h"
 #include "fmdemod.h"
 
@@ -32,9 +31,9 @@ using fmd::kAudmonRing;
 
 namespace {
 
-constexpr int kT = 64;               // threads per workgroup: one wavefront, one station
-constexpr int kQ = 4;                // frames per lane and row
-constexpr int kRow = kT * kQ;        // frames per row
+namespace rows = fmd::rows;
+using rows::kQ;                      // frames per lane and row
+using rows::kT;                      // threads per workgroup: one wavefront, one station
 constexpr int kPf = 4;               // rows loaded ahead
 constexpr int kPartD = 3 * kAudmonPartials;    // doubles per station: the open interval's ll, rr and lr partials
 static_assert(kAudmonPartials == kT && kAudmonRing == 30 && kAudmonDetectors == 5, "k_audmon's lane layout");
@@ -45,36 +44,6 @@ static_assert(sizeof(fmd_audmon_status) == 840 && offsetof(fmd_audmon_status, in
               offsetof(fmd_audmon_status, transitions) == 812 && offsetof(fmd_audmon_status, nonfinite) == 832 && offsetof(fmd_audmon_status, flags) == 836 &&
               offsetof(fmd_audmon_status, ok) == 837 && offsetof(fmd_audmon_status, reserved) == 838, "fmd_audmon_status layout");
 static_assert(sizeof(AudmonGate) == 80 && sizeof(fmd_audmon_params) == 80, "AudmonGate and fmd_audmon_params layout");
-
-// A lane's four frames of a row, loaded at once.  The station's rows are aligned to a frame only (8 bytes): the types carry that
-// alignment, and the device's global loads take any.
-typedef float am_f4 __attribute__((ext_vector_type(4), aligned(8)));
-typedef float am_f2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void am_load4(const float2* p, float2 (&z)[kQ]) {
-    const am_f4 a = __builtin_nontemporal_load(reinterpret_cast<const am_f4*>(p));
-    const am_f4 b = __builtin_nontemporal_load(reinterpret_cast<const am_f4*>(p + 2));
-    z[0] = make_float2(a.x, a.y); z[1] = make_float2(a.z, a.w); z[2] = make_float2(b.x, b.y); z[3] = make_float2(b.z, b.w);
-}
-__device__ __forceinline__ float2 am_load1(const float2* p) {
-    const am_f2 v = __builtin_nontemporal_load(reinterpret_cast<const am_f2*>(p));
-    return make_float2(v.x, v.y);
-}
-
-// One detector's update on the station's record (lane 0, at an interval's end)
-__device__ __forceinline__ unsigned am_detect(fmd_audmon_status* st, int k, unsigned flags, bool bad, int raise, int clear) {
-    const unsigned bit = 1u << k;
-    unsigned run = st->run[k];
-    if (!(flags & bit)) {
-        run = bad ? run + 1 : 0;
-        if (run >= (unsigned)raise) { flags |= bit; run = 0; st->transitions[k]++; }
-    } else {
-        run = bad ? 0 : run + 1;
-        if (run >= (unsigned)clear) { flags &= ~bit; run = 0; st->transitions[k]++; }
-    }
-    st->run[k] = run;
-    return flags;
-}
 
 // in [C][in_stride] frames (L, R); gate [C]; status [C]; part [C][3][64]; carry [C][2]; out_flags, out_ok [C] or null
 __global__ __launch_bounds__(kT) void k_audmon(const float2* __restrict__ in, long long in_stride, long long n, const uint8_t* __restrict__ active, int M,
@@ -99,34 +68,14 @@ __global__ __launch_bounds__(kT) void k_audmon(const float2* __restrict__ in, lo
 
     const unsigned long long frames0 = st->frames;
     unsigned long long G = st->intervals;
-    int r0 = __builtin_amdgcn_readfirstlane((int)(frames0 - G * (unsigned long long)M));   // the first frame's place in its interval
+    const int r0 = __builtin_amdgcn_readfirstlane((int)(frames0 - G * (unsigned long long)M));   // the first frame's place in its interval
     float cpl = carry[2 * c], cpr = carry[2 * c + 1];                        // the open interval's peaks before this call
     double ll = pp[0], rr = pp[kAudmonPartials], lr = pp[2 * kAudmonPartials];
     float pl = 0.0f, pr = 0.0f;                                              // the lane's, over the segment at hand
     float hl = 0.0f, hr = 0.0f;                                              // over the call
 
-    long long s0 = 0;                                                        // the segment's first frame: a segment ends with its interval or the call
-    while (s0 < n) {
-        const long long left = (long long)(M - r0);
-        const long long seg_end = n - s0 < left ? n : s0 + left;
-        const long long rb = s0 - (long long)(r0 & (kRow - 1));              // the first row's frame 0 (before s0: those frames read as zero)
-
-        float2 nxt[kPf][kQ];
-        auto fetch = [&](long long row) {
-#pragma unroll
-            for (int p = 0; p < kPf; p++) {
-                const long long i = row + (long long)p * kRow + kQ * lane;
-                if (i >= s0 && i + kQ <= seg_end) am_load4(base + i, nxt[p]);
-                else {
-#pragma unroll
-                    for (int k = 0; k < kQ; k++) {
-                        nxt[p][k] = make_float2(0.0f, 0.0f);
-                        if (i + k >= s0 && i + k < seg_end) nxt[p][k] = am_load1(base + i + k);
-                    }
-                }
-            }
-        };
-        auto process = [&](const float2 (&v)[kQ]) {
+    rows::walk<kPf>(base, lane, n, M, r0, make_float2(0.0f, 0.0f),
+        [&](const float2 (&v)[kQ]) {
 #pragma unroll
             for (int k = 0; k < kQ; k++) {
                 const double l = (double)v[k].x, r_ = (double)v[k].y;
@@ -136,51 +85,34 @@ __global__ __launch_bounds__(kT) void k_audmon(const float2* __restrict__ in, lo
                 pl = fmaxf(pl, fabsf(v[k].x));
                 pr = fmaxf(pr, fabsf(v[k].y));
             }
-        };
-
-        fetch(rb);
-        for (long long row = rb; row < seg_end; row += (long long)kPf * kRow) {
-            float2 cur[kPf][kQ];
-#pragma unroll
-            for (int p = 0; p < kPf; p++)
-#pragma unroll
-                for (int k = 0; k < kQ; k++) cur[p][k] = nxt[p][k];
-            if (row + (long long)kPf * kRow < seg_end) fetch(row + (long long)kPf * kRow);   // in flight while these rows run
-#pragma unroll
-            for (int p = 0; p < kPf; p++)
-                if (row + (long long)p * kRow < seg_end) process(cur[p]);
-        }
-
-        // the segment's peaks: no operand is ever a NaN, so the order of a maximum does not matter
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) { pl = fmaxf(pl, __shfl_xor(pl, d)); pr = fmaxf(pr, __shfl_xor(pr, d)); }
-        cpl = fmaxf(cpl, pl); cpr = fmaxf(cpr, pr);
-        hl = fmaxf(hl, pl); hr = fmaxf(hr, pr);
-        pl = 0.0f; pr = 0.0f;
-        r0 += (int)(seg_end - s0);
-        if (r0 == M) {                                                       // the interval is complete (wave-uniform)
-#pragma unroll
-            for (int w = kT / 2; w >= 1; w >>= 1) {                          // p_j += p_{j+w} for j < w, w = 32 ... 1: partial j + w sits w lanes up
-                ll += __shfl_down(ll, w); rr += __shfl_down(rr, w); lr += __shfl_down(lr, w);
-            }
+        },
+        [&](bool complete) {
+            pl = rows::wave_max(pl); pr = rows::wave_max(pr);      // the segment's peaks
+            cpl = fmaxf(cpl, pl); cpr = fmaxf(cpr, pr);
+            hl = fmaxf(hl, pl); hr = fmaxf(hr, pr);
+            pl = 0.0f; pr = 0.0f;
+            if (!complete) return;
+            rows::fold(ll, rr, lr);
             if (lane == 0) {
                 const double LL = ll, RR = rr, LR = lr;
                 const int k = (int)(G % (unsigned long long)kAudmonRing);
                 st->ring_ll[k] = LL; st->ring_rr[k] = RR; st->ring_lr[k] = LR;
                 st->last_peak[0] = cpl; st->last_peak[1] = cpr;
-                const double big = 1.7976931348623157e308;                   // neither inf nor NaN
-                const bool finite = fabs(LL) <= big && fabs(RR) <= big && fabs(LR) <= big;
+                const bool finite = rows::finite(LL) && rows::finite(RR) && rows::finite(LR);
                 if (!finite) st->nonfinite++;
                 const double E = LL + RR;
                 const bool silent = !(finite && E > gt.min_e);
-                flags = am_detect(st, 0, flags, silent, gt.raise_intervals[0], gt.clear_intervals[0]);
+                auto detect = [&](int d, bool bad) {
+                    flags = rows::detect(flags, d, bad, gt.raise_intervals[d], gt.clear_intervals[d], st->run[d], st->transitions[d]);
+                };
+                detect(0, silent);
                 if (!silent) {                                               // (silent: detectors 1 ... 4 hold)
                     const double c_loss = gt.c_loss;
                     const double S = fma(-2.0, LR, E), Md = fma(2.0, LR, E);
-                    flags = am_detect(st, 1, flags, LL < c_loss * RR, gt.raise_intervals[1], gt.clear_intervals[1]);
-                    flags = am_detect(st, 2, flags, RR < c_loss * LL, gt.raise_intervals[2], gt.clear_intervals[2]);
-                    flags = am_detect(st, 3, flags, LR < 0.0 && LR * LR > gt.c_anti * (LL * RR), gt.raise_intervals[3], gt.clear_intervals[3]);
-                    flags = am_detect(st, 4, flags, S < gt.c_mono * Md, gt.raise_intervals[4], gt.clear_intervals[4]);
+                    detect(1, LL < c_loss * RR);
+                    detect(2, RR < c_loss * LL);
+                    detect(3, LR < 0.0 && LR * LR > gt.c_anti * (LL * RR));
+                    detect(4, S < gt.c_mono * Md);
                 }
 #pragma unroll
                 for (int d = 0; d < kAudmonDetectors; d++)
@@ -189,10 +121,7 @@ __global__ __launch_bounds__(kT) void k_audmon(const float2* __restrict__ in, lo
             G++;
             ll = 0.0; rr = 0.0; lr = 0.0;
             cpl = 0.0f; cpr = 0.0f;
-            r0 = 0;
-        }
-        s0 = seg_end;
-    }
+        });
 
     // what the next call needs: the open interval's partials and peaks, and the record
     pp[0] = ll; pp[kAudmonPartials] = rr; pp[2 * kAudmonPartials] = lr;
@@ -252,12 +181,11 @@ static int am_fail(fmd_audmon a, int code, const char* fmt, A... args) { return 
 
 static int am_reset(fmd_audmon a, int channel, int peaks) {
     if (!a) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= a->C) return am_fail(a, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, a->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, a->C, &c0, &cn)) return am_fail(a, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, a->C);
     if (!a->order.quiesce()) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? a->C : 1;
     hipLaunchKernelGGL(k_audmon_reset, dim3((unsigned)cn), dim3(kT), 0, nullptr, c0, peaks, a->d_status, a->d_part, a->d_carry);
-    if (hipGetLastError() != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "k_audmon_reset launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_audmon_reset launch failed")) return am_fail(a, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 
@@ -307,14 +235,13 @@ int fmd_audmon_reset_peaks(fmd_audmon a, int channel) { return am_reset(a, chann
 
 int fmd_audmon_set_params(fmd_audmon a, int channel, const fmd_audmon_params* p) {
     if (!a) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= a->C) return am_fail(a, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, a->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, a->C, &c0, &cn)) return am_fail(a, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, a->C);
     AudmonGate g;
     if (fmd::audmon_gate(p, a->M, &g, &a->err) != FMD_OK) return FMD_ERR_ARG;
     if (!a->order.quiesce()) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? a->C : 1;
     hipLaunchKernelGGL(k_audmon_set, dim3((unsigned)((cn + kT - 1) / kT)), dim3(kT), 0, nullptr, c0, cn, g, a->d_gate, a->d_status);
-    if (hipGetLastError() != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "k_audmon_set launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return am_fail(a, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_audmon_set launch failed")) return am_fail(a, FMD_ERR_DEVICE, "%s", e);
     for (int c = c0; c < c0 + cn; c++) a->params[(size_t)c] = *p;
     return FMD_OK;
 }

@@ -25,6 +25,7 @@
 #include "fmd_iq.h"
 #include "fmd_math.h"
 #include "fmd_modmon_design.h"
+#include "fmd_rows.h"
 #include "fmd_side.h"
 #include "fmdemod.h"
 
@@ -181,16 +182,13 @@ __global__ __launch_bounds__(kT) void k_modmon(const typename fmd::Iq<S>::raw* _
         hi = -kInf; lo = kInf;
         r0 += (int)(seg_end - s0);
         if (r0 == M) {                                                       // the interval is complete (wave-uniform)
-#pragma unroll
-            for (int w = kT / 2; w >= 1; w >>= 1) {                          // p_j += p_{j+w} for j < w (the lanes from w up hold nothing that is used)
-                s1 += __shfl_down(s1, w); s2 += __shfl_down(s2, w); sc += __shfl_down(sc, w); ss += __shfl_down(ss, w);
-            }
+            fmd::rows::fold(s1, s2, sc, ss);
             G++;
             if (lane == 0) {
                 const double D = 0.5 * ((double)chi - (double)clo) * hz_per_rad;
                 st->last_hi = chi; st->last_lo = clo;
                 st->last_s1 = s1; st->last_s2 = s2; st->last_sc = sc; st->last_ss = ss;
-                if (!(fabs(D) <= 1.7976931348623157e308) || !(fabs(s2) <= 1.7976931348623157e308)) st->nonfinite++;   // inf or NaN
+                if (!fmd::rows::finite(D) || !fmd::rows::finite(s2)) st->nonfinite++;
                 else {
                     if (D >= fmd::kModmonBinHz * (double)kModmonBins) st->over++;
                     else {
@@ -276,12 +274,11 @@ static int mm_fail(fmd_modmon m, int code, const char* fmt, A... args) { return 
 
 static int mm_reset(fmd_modmon m, int channel, int peaks) {
     if (!m) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= m->C) return mm_fail(m, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, m->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, m->C, &c0, &cn)) return mm_fail(m, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, m->C);
     if (!m->order.quiesce()) return mm_fail(m, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? m->C : 1;
     hipLaunchKernelGGL(k_modmon_reset, dim3((unsigned)cn), dim3(kT), 0, nullptr, c0, peaks, m->d_status, m->d_part, m->d_carry, m->d_hist);
-    if (hipGetLastError() != hipSuccess) return mm_fail(m, FMD_ERR_DEVICE, "k_modmon_reset launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return mm_fail(m, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_modmon_reset launch failed")) return mm_fail(m, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 

@@ -49,6 +49,22 @@ private:
     bool recorded_ = false;
 };
 
+// A control call's `channel` as the stations c0 ... c0 + cn - 1 of C (-1: every station); false when it is outside [-1, C).
+inline bool channel_range(int channel, int C, int* c0, int* cn) {
+    if (channel < -1 || channel >= C) return false;
+    *c0 = channel < 0 ? 0 : channel;
+    *cn = channel < 0 ? C : 1;
+    return true;
+}
+
+// Closes a control launch on the null stream, which is done before a later call on any stream: nullptr, or the failed step's error
+// text (`launch_failed` for the launch itself).
+inline const char* control_end(const char* launch_failed) {
+    if (hipGetLastError() != hipSuccess) return launch_failed;
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return "synchronise failed";
+    return nullptr;
+}
+
 // the formatted message into `dst` (a handle's err or the object's global string); returns `code`
 inline int fail(std::string& dst, int code, const char* fmt, ...) {
     char buf[512];

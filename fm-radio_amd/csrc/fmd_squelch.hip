@@ -4,14 +4,12 @@
 // station baseband [C][in_stride][2] (cf32 or u8) that the demodulator takes and the channeliser writes, read in place; at an interval's
 // end the hysteresis gate, and at a call's end the [C] mask byte that the other side objects take as d_active.
 //
-// One kernel per call, k_squelch<format>.  One wavefront per station; lane l owns partials 4 l ... 4 l + 3 of the two interval sums
-// outright and adds its terms in ascending r, r the sample's place in its interval.  The wavefront walks rows of 256 consecutive samples
-// (2 KB of cf32 as two 16-byte loads per lane, 512 bytes of u8 as one 8-byte load, non-temporal: the IQ is read once), four rows in
-// registers ahead of the row it works on.  A row starts at a multiple of 256 of r, so the first row of a call and the rows around an
-// interval's end are partial: a lane's sample outside the segment at hand is not loaded and reads as (+0, +0), which changes no partial
-// (p = +0, s + +0 = s, fma(+0, +0, s) = s: a partial is never -0) and no peak.  An interval's end is wave-uniform: the partials fold by
-// cross-lane moves in the contract's halving order, and lane 0 alone runs the gate and stores, with ordinary stores.  The open
-// interval's 4 KB of partials are read at the call's start and written at its end.  No atomics, no LDS, no scratch.
+// One kernel per call, k_squelch<format>, on the row walk of fmd_rows.h (one wavefront per station, rows of 256 samples: 2 KB of cf32,
+// 512 bytes of u8; four rows in registers ahead).  Lane l owns partials 4 l ... 4 l + 3 of the two interval sums outright and adds its
+// terms in ascending r, r the sample's place in its interval; a sample that reads as (+0, +0) changes no partial (p = +0, s + +0 = s,
+// fma(+0, +0, s) = s: a partial is never -0) and no peak.  At an interval's end the partials fold by cross-lane moves in the contract's
+// halving order, and lane 0 alone runs the gate and stores, with ordinary stores.  The open interval's 4 KB of partials are read at the
+// call's start and written at its end.  No atomics, no LDS, no scratch.
 //
 // Denormals: fp64 and fp32 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
 #include <hip/hip_runtime.h>
@@ -22,6 +20,7 @@
 #include <vector>
 
 #include "fmd_iq.h"
+#include "fmd_rows.h"
 #include "fmd_side.h"
 #include "fmd_squelch_design.h"
 #include "fmdemod.h"
@@ -32,9 +31,10 @@ using fmd::SquelchGate;
 
 namespace {
 
-constexpr int kT = 64;               // threads per workgroup: one wavefront, one station
-constexpr int kQ = 4;                // samples (and partials) per lane and row
-constexpr int kRow = kT * kQ;        // samples per row
+namespace rows = fmd::rows;
+using rows::kQ;                      // samples (and partials) per lane and row
+using rows::kRow;                    // samples per row
+using rows::kT;                      // threads per workgroup: one wavefront, one station
 constexpr int kPf = 4;               // rows loaded ahead
 constexpr int kPartD = 2 * kSquelchPartials;   // doubles per station: the open interval's s2 and s4 partials
 static_assert(kSquelchPartials == kRow && kSquelchRing == 20, "k_squelch's lane layout");
@@ -45,27 +45,6 @@ static_assert(sizeof(fmd_squelch_status) == 368 && offsetof(fmd_squelch_status, 
               offsetof(fmd_squelch_status, nonfinite) == 360 && offsetof(fmd_squelch_status, open) == 364 && offsetof(fmd_squelch_status, mode) == 365 &&
               offsetof(fmd_squelch_status, reserved) == 366, "fmd_squelch_status layout");
 static_assert(sizeof(SquelchGate) == 40, "SquelchGate layout");
-
-// A lane's four samples of a row, loaded at once.  The station's rows are aligned to a sample only (8 bytes of cf32, 2 of u8): the types
-// carry that alignment, and the device's global loads take any.
-typedef float sq_f4 __attribute__((ext_vector_type(4), aligned(8)));
-typedef float sq_f2 __attribute__((ext_vector_type(2)));
-typedef unsigned sq_u2 __attribute__((ext_vector_type(2), aligned(2)));
-
-__device__ __forceinline__ void sq_load4(const float2* p, float2 (&z)[kQ]) {
-    const sq_f4 a = __builtin_nontemporal_load(reinterpret_cast<const sq_f4*>(p));
-    const sq_f4 b = __builtin_nontemporal_load(reinterpret_cast<const sq_f4*>(p + 2));
-    z[0] = make_float2(a.x, a.y); z[1] = make_float2(a.z, a.w); z[2] = make_float2(b.x, b.y); z[3] = make_float2(b.z, b.w);
-}
-__device__ __forceinline__ void sq_load4(const unsigned short* p, unsigned short (&z)[kQ]) {
-    const sq_u2 a = __builtin_nontemporal_load(reinterpret_cast<const sq_u2*>(p));
-    z[0] = (unsigned short)(a.x & 0xffffu); z[1] = (unsigned short)(a.x >> 16); z[2] = (unsigned short)(a.y & 0xffffu); z[3] = (unsigned short)(a.y >> 16);
-}
-__device__ __forceinline__ float2 sq_load1(const float2* p) {
-    const sq_f2 v = __builtin_nontemporal_load(reinterpret_cast<const sq_f2*>(p));
-    return make_float2(v.x, v.y);
-}
-__device__ __forceinline__ unsigned short sq_load1(const unsigned short* p) { return __builtin_nontemporal_load(p); }
 
 // in [C][in_stride] IQ pairs; gate [C]; status [C]; part [C][2][256]; carry [C]; mask [C] or null
 template <typename S>
@@ -88,7 +67,7 @@ __global__ __launch_bounds__(kT) void k_squelch(const typename fmd::Iq<S>::raw* 
 
     const unsigned long long samples0 = st->samples;
     unsigned long long G = st->intervals;
-    int r0 = __builtin_amdgcn_readfirstlane((int)(samples0 - G * (unsigned long long)M));   // the first sample's place in its interval
+    const int r0 = __builtin_amdgcn_readfirstlane((int)(samples0 - G * (unsigned long long)M));   // the first sample's place in its interval
     // the gate's state: lane 0's copies are the ones that are updated and stored
     unsigned run = st->run, transitions = st->transitions, nonfinite = st->nonfinite;
     unsigned long long g_open = st->intervals_open;
@@ -99,28 +78,8 @@ __global__ __launch_bounds__(kT) void k_squelch(const typename fmd::Iq<S>::raw* 
     float pk = 0.0f;                                                         // the lane's, over the segment at hand
     float hmax = 0.0f;                                                       // over the call
 
-    long long s0 = 0;                                                        // the segment's first sample: a segment ends with its interval or the call
-    while (s0 < n) {
-        const long long left = (long long)(M - r0);
-        const long long seg_end = n - s0 < left ? n : s0 + left;
-        const long long rb = s0 - (long long)(r0 & (kRow - 1));              // the first row's sample 0 (before s0: those samples read as zero)
-
-        raw nxt[kPf][kQ];
-        auto fetch = [&](long long row) {
-#pragma unroll
-            for (int p = 0; p < kPf; p++) {
-                const long long i = row + (long long)p * kRow + kQ * lane;
-                if (i >= s0 && i + kQ <= seg_end) sq_load4(base + i, nxt[p]);
-                else {
-#pragma unroll
-                    for (int k = 0; k < kQ; k++) {
-                        nxt[p][k] = fmd::Iq<S>::zero();
-                        if (i + k >= s0 && i + k < seg_end) nxt[p][k] = sq_load1(base + i + k);
-                    }
-                }
-            }
-        };
-        auto process = [&](const raw (&v)[kQ]) {
+    rows::walk<kPf>(base, lane, n, M, r0, fmd::Iq<S>::zero(),
+        [&](const raw (&v)[kQ]) {
 #pragma unroll
             for (int k = 0; k < kQ; k++) {
                 const float2 z = fmd::Iq<S>::cf32(v[k]);
@@ -130,41 +89,23 @@ __global__ __launch_bounds__(kT) void k_squelch(const typename fmd::Iq<S>::raw* 
                 s4[k] = fma(p, p, s4[k]);
                 pk = fmaxf(pk, fmaxf(fabsf(z.x), fabsf(z.y)));
             }
-        };
-
-        fetch(rb);
-        for (long long row = rb; row < seg_end; row += (long long)kPf * kRow) {
-            raw cur[kPf][kQ];
+        },
+        [&](bool complete) {
+            pk = rows::wave_max(pk);                                         // the segment's peak
+            cpk = fmaxf(cpk, pk);
+            hmax = fmaxf(hmax, pk);
+            pk = 0.0f;
+            if (!complete) return;
 #pragma unroll
-            for (int p = 0; p < kPf; p++)
-#pragma unroll
-                for (int k = 0; k < kQ; k++) cur[p][k] = nxt[p][k];
-            if (row + (long long)kPf * kRow < seg_end) fetch(row + (long long)kPf * kRow);   // in flight while these rows run
-#pragma unroll
-            for (int p = 0; p < kPf; p++)
-                if (row + (long long)p * kRow < seg_end) process(cur[p]);
-        }
-
-        // the segment's peak: no operand is ever a NaN, so the order of a maximum does not matter
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) pk = fmaxf(pk, __shfl_xor(pk, d));
-        cpk = fmaxf(cpk, pk);
-        hmax = fmaxf(hmax, pk);
-        pk = 0.0f;
-        r0 += (int)(seg_end - s0);
-        if (r0 == M) {                                                       // the interval is complete (wave-uniform)
-#pragma unroll
-            for (int w = kT / 2; w >= 1; w >>= 1) {                          // p_j += p_{j+w} for j < w, w = 128 ... 4: partial j + w sits 'w / 4' lanes up
-#pragma unroll
-                for (int k = 0; k < kQ; k++) { s2[k] += __shfl_down(s2[k], w); s4[k] += __shfl_down(s4[k], w); }
-            }
+            for (int k = 0; k < kQ; k++) rows::fold(s2[k], s4[k]);           // w = 128 ... 4: partial j + w sits 'w / 4' lanes up, so each of
+                                                                             // the lane's four partials folds across lanes on a chain of its own
             s2[0] += s2[2]; s2[1] += s2[3]; s2[0] += s2[1];                  // w = 2, 1
             s4[0] += s4[2]; s4[1] += s4[3]; s4[0] += s4[1];
             if (lane == 0) {
                 const double S2 = s2[0], S4 = s4[0];
                 const int k = (int)(G % (unsigned long long)kSquelchRing);
                 st->ring_s2[k] = S2; st->ring_s4[k] = S4; st->last_peak = cpk;
-                const bool finite = fabs(S2) <= 1.7976931348623157e308 && fabs(S4) <= 1.7976931348623157e308;   // neither inf nor NaN
+                const bool finite = rows::finite(S2) && rows::finite(S4);
                 if (!finite) nonfinite++;
                 const double a = S2 * S2;
                 const double d = fma(-(double)M, S4, 2.0 * a);
@@ -182,10 +123,7 @@ __global__ __launch_bounds__(kT) void k_squelch(const typename fmd::Iq<S>::raw* 
 #pragma unroll
             for (int k = 0; k < kQ; k++) { s2[k] = 0.0; s4[k] = 0.0; }
             cpk = 0.0f;
-            r0 = 0;
-        }
-        s0 = seg_end;
-    }
+        });
 
     // what the next call needs: the open interval's partials and peak, and the gate
 #pragma unroll
@@ -245,12 +183,11 @@ static int sq_fail(fmd_squelch q, int code, const char* fmt, A... args) { return
 
 static int sq_reset(fmd_squelch q, int channel, int peaks) {
     if (!q) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= q->C) return sq_fail(q, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, q->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, q->C, &c0, &cn)) return sq_fail(q, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, q->C);
     if (!q->order.quiesce()) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? q->C : 1;
     hipLaunchKernelGGL(k_squelch_reset, dim3((unsigned)cn), dim3(kT), 0, nullptr, c0, peaks, q->d_gate, q->d_status, q->d_part, q->d_carry);
-    if (hipGetLastError() != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "k_squelch_reset launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_squelch_reset launch failed")) return sq_fail(q, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 
@@ -315,14 +252,13 @@ int fmd_squelch_reset_peaks(fmd_squelch q, int channel) { return sq_reset(q, cha
 
 int fmd_squelch_set_params(fmd_squelch q, int channel, const fmd_squelch_params* p) {
     if (!q) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= q->C) return sq_fail(q, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, q->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, q->C, &c0, &cn)) return sq_fail(q, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, q->C);
     SquelchGate g;
     if (fmd::squelch_gate(p, q->M, &g, &q->err) != FMD_OK) return FMD_ERR_ARG;
     if (!q->order.quiesce()) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? q->C : 1;
     hipLaunchKernelGGL(k_squelch_set, dim3((unsigned)((cn + kT - 1) / kT)), dim3(kT), 0, nullptr, c0, cn, g, q->d_gate, q->d_status);
-    if (hipGetLastError() != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "k_squelch_set launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return sq_fail(q, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_squelch_set launch failed")) return sq_fail(q, FMD_ERR_DEVICE, "%s", e);
     for (int c = c0; c < c0 + cn; c++) q->params[(size_t)c] = *p;
     return FMD_OK;
 }

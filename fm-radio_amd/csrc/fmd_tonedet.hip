@@ -5,17 +5,16 @@
 // RE = sum m cos, IM = sum m sin against the handle's table of fs entries; at an interval's end the eight hysteresis detectors, and at a
 // call's end the [C] flags and ok bytes.
 //
-// One kernel per call, k_tonedet, with k_audmon's geometry: one wavefront per station over rows of 256 consecutive frames that start at a
-// multiple of 256 of r, r the frame's place in its interval; lane l loads frames 4 l ... 4 l + 3 with two 16-byte non-temporal loads, two
-// rows in registers ahead of the rows it works on.  With NP = 64 and j = (r >> 2) & 63 lane l owns exactly partial l of each of the 17
-// sums (34 fp64 accumulators with the mid signal's and eight slots') and adds its four terms of a row in ascending r.  Per frame and
-// used slot one 16-byte gather of (cos, sin) from the table in global memory (at most 768 KB, shared by every station: it stays in L2);
-// the table index moves from frame to frame and from row to row by an add and a conditional subtract, with one modulo per slot and
-// segment.  The slots are walked by an unrolled loop with a wave-uniform test per slot, so that the accumulators stay in registers.  A
-// frame outside the segment at hand is not loaded and reads as (+0, +0), which changes no partial (fma(+0, t, s) = s for a finite t: a
-// partial is never -0).  An interval's end is wave-uniform: the partials fold by cross-lane moves in the contract's halving order, and
-// lane 0 alone writes the ring, runs the detectors on the station's record and stores, with ordinary stores.  The open interval's 8.5 KB
-// of partials are read at the call's start and written at its end.  No atomics, no LDS, no scratch.
+// One kernel per call, k_tonedet, on the row walk of fmd_rows.h as k_audmon is (one wavefront per station, rows of 256 frames), with two
+// rows in registers ahead.  With NP = 64 and j = (r >> 2) & 63 lane l owns exactly partial l of each of the 17 sums (34 fp64
+// accumulators with the mid signal's and eight slots') and adds its four terms of a row in ascending r.  Per frame and used slot one
+// 16-byte gather of (cos, sin) from the table in global memory (at most 768 KB, shared by every station: it stays in L2); the table
+// index moves from frame to frame and from row to row by an add and a conditional subtract, with one modulo per slot and segment.  The
+// slots are walked by an unrolled loop with a wave-uniform test per slot, so that the accumulators stay in registers.  A frame that
+// reads as (+0, +0) changes no partial (fma(+0, t, s) = s for a finite t: a partial is never -0).  At an interval's end the partials
+// fold by cross-lane moves in the contract's halving order, and lane 0 alone writes the ring, runs the detectors on the station's
+// record and stores, with ordinary stores.  The open interval's 8.5 KB of partials are read at the call's start and written at its
+// end.  No atomics, no LDS, no scratch.
 //
 // Denormals: fp64 and fp32 denormals are kept (hipcc's default mode; this file is NOT built with -fgpu-flush-denormals-to-zero).
 #include <hip/hip_runtime.h>
@@ -25,6 +24,7 @@
 #include <string>
 #include <vector>
 
+#include "fmd_rows.h"
 #include "fmd_side.h"
 #include "fmd_tonedet_design.h"
 #include "fmdemod.h"
@@ -37,9 +37,10 @@ using fmd::TonedetGate;
 
 namespace {
 
-constexpr int kT = 64;               // threads per workgroup: one wavefront, one station
-constexpr int kQ = 4;                // frames per lane and row
-constexpr int kRow = kT * kQ;        // frames per row
+namespace rows = fmd::rows;
+using rows::kQ;                      // frames per lane and row
+using rows::kRow;                    // frames per row
+using rows::kT;                      // threads per workgroup: one wavefront, one station
 constexpr int kPf = 2;               // rows loaded ahead
 constexpr int kPartD = kTonedetSums * kTonedetPartials;    // doubles per station: the open interval's partials
 static_assert(kTonedetPartials == kT && kTonedetRing == 30 && kTonedetSlots == 8 && kTonedetSums == 17, "k_tonedet's lane layout");
@@ -51,40 +52,10 @@ static_assert(sizeof(fmd_tonedet_status) == 2344 && offsetof(fmd_tonedet_status,
               offsetof(fmd_tonedet_status, reserved) == 2342, "fmd_tonedet_status layout");
 static_assert(sizeof(TonedetGate) == 176 && sizeof(fmd_tonedet_params) == 176, "TonedetGate and fmd_tonedet_params layout");
 
-// A lane's four frames of a row, loaded at once.  The station's rows are aligned to a frame only (8 bytes): the types carry that
-// alignment, and the device's global loads take any.
-typedef float td_f4 __attribute__((ext_vector_type(4), aligned(8)));
-typedef float td_f2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void td_load4(const float2* p, float2 (&z)[kQ]) {
-    const td_f4 a = __builtin_nontemporal_load(reinterpret_cast<const td_f4*>(p));
-    const td_f4 b = __builtin_nontemporal_load(reinterpret_cast<const td_f4*>(p + 2));
-    z[0] = make_float2(a.x, a.y); z[1] = make_float2(a.z, a.w); z[2] = make_float2(b.x, b.y); z[3] = make_float2(b.z, b.w);
-}
-__device__ __forceinline__ float2 td_load1(const float2* p) {
-    const td_f2 v = __builtin_nontemporal_load(reinterpret_cast<const td_f2*>(p));
-    return make_float2(v.x, v.y);
-}
-
 // a + b mod fs for a, b < fs
 __device__ __forceinline__ unsigned td_step(unsigned a, unsigned b, unsigned fs) {
     const unsigned s = a + b;
     return s >= fs ? s - fs : s;
-}
-
-// One detector's update on the station's record (lane 0, at an interval's end)
-__device__ __forceinline__ unsigned td_detect(fmd_tonedet_status* st, int k, unsigned flags, bool present, int raise, int clear) {
-    const unsigned bit = 1u << k;
-    unsigned run = st->run[k];
-    if (!(flags & bit)) {
-        run = present ? run + 1 : 0;
-        if (run >= (unsigned)raise) { flags |= bit; run = 0; st->transitions[k]++; }
-    } else {
-        run = present ? 0 : run + 1;
-        if (run >= (unsigned)clear) { flags &= ~bit; run = 0; st->transitions[k]++; }
-    }
-    st->run[k] = run;
-    return flags;
 }
 
 // in [C][in_stride] frames (L, R); tab [fs] (cos, sin); gate [C]; status [C]; part [C][17][64]; out_flags, out_ok [C] or null
@@ -113,7 +84,7 @@ __global__ __launch_bounds__(kT) void k_tonedet(const float2* __restrict__ in, l
 
     const unsigned long long frames0 = st->frames;
     unsigned long long G = st->intervals;
-    int r0 = __builtin_amdgcn_readfirstlane((int)(frames0 - G * (unsigned long long)M));   // the first frame's place in its interval
+    const int r0 = __builtin_amdgcn_readfirstlane((int)(frames0 - G * (unsigned long long)M));   // the first frame's place in its interval
     unsigned f[kTonedetSlots];                                               // the frequencies in force (uniform), 0 = unused
     double mm = pp[0], re[kTonedetSlots], im[kTonedetSlots];
 #pragma unroll
@@ -123,39 +94,20 @@ __global__ __launch_bounds__(kT) void k_tonedet(const float2* __restrict__ in, l
         im[k] = pp[(2 + 2 * k) * kTonedetPartials];
     }
 
-    long long s0 = 0;                                                        // the segment's first frame: a segment ends with its interval or the call
-    while (s0 < n) {
-        const long long left = (long long)(M - r0);
-        const long long seg_end = n - s0 < left ? n : s0 + left;
-        const long long rb = s0 - (long long)(r0 & (kRow - 1));              // the first row's frame 0 (before s0: those frames read as zero)
-
-        // per used slot the table index of the lane's first frame of the row at hand, and the step from one row to the next
-        unsigned ix[kTonedetSlots], rowstep[kTonedetSlots];
+    // per used slot the table index of the lane's first frame of the row at hand, and the step from one row to the next
+    unsigned ix[kTonedetSlots], rowstep[kTonedetSlots];
+    rows::walk<kPf>(base, lane, n, M, r0, make_float2(0.0f, 0.0f),
+        [&](int r) {                                                         // the segment's first frame's place in its interval
 #pragma unroll
-        for (int k = 0; k < kTonedetSlots; k++) {
-            ix[k] = 0u; rowstep[k] = 0u;
-            if (f[k]) {
-                ix[k] = (f[k] * (unsigned)((r0 & ~(kRow - 1)) + kQ * lane)) % ufs;   // (below 2^31: f < 24000, r < 4800 + 256)
-                rowstep[k] = (f[k] * (unsigned)kRow) % ufs;
-            }
-        }
-
-        float2 nxt[kPf][kQ];
-        auto fetch = [&](long long row) {
-#pragma unroll
-            for (int p = 0; p < kPf; p++) {
-                const long long i = row + (long long)p * kRow + kQ * lane;
-                if (i >= s0 && i + kQ <= seg_end) td_load4(base + i, nxt[p]);
-                else {
-#pragma unroll
-                    for (int k = 0; k < kQ; k++) {
-                        nxt[p][k] = make_float2(0.0f, 0.0f);
-                        if (i + k >= s0 && i + k < seg_end) nxt[p][k] = td_load1(base + i + k);
-                    }
+            for (int k = 0; k < kTonedetSlots; k++) {
+                ix[k] = 0u; rowstep[k] = 0u;
+                if (f[k]) {
+                    ix[k] = (f[k] * (unsigned)((r & ~(kRow - 1)) + kQ * lane)) % ufs;   // (below 2^31: f < 24000, r < 4800 + 256)
+                    rowstep[k] = (f[k] * (unsigned)kRow) % ufs;
                 }
             }
-        };
-        auto process = [&](const float2 (&v)[kQ]) {
+        },
+        [&](const float2 (&v)[kQ]) {
             double m[kQ];
 #pragma unroll
             for (int q = 0; q < kQ; q++) {
@@ -180,36 +132,17 @@ __global__ __launch_bounds__(kT) void k_tonedet(const float2* __restrict__ in, l
                     ix[k] = td_step(ix[k], rowstep[k], ufs);
                 }
             }
-        };
-
-        fetch(rb);
-        for (long long row = rb; row < seg_end; row += (long long)kPf * kRow) {
-            float2 cur[kPf][kQ];
-#pragma unroll
-            for (int p = 0; p < kPf; p++)
-#pragma unroll
-                for (int k = 0; k < kQ; k++) cur[p][k] = nxt[p][k];
-            if (row + (long long)kPf * kRow < seg_end) fetch(row + (long long)kPf * kRow);   // in flight while these rows run
-#pragma unroll
-            for (int p = 0; p < kPf; p++)
-                if (row + (long long)p * kRow < seg_end) process(cur[p]);
-        }
-
-        r0 += (int)(seg_end - s0);
-        if (r0 == M) {                                                       // the interval is complete (wave-uniform)
-#pragma unroll
-            for (int w = kT / 2; w >= 1; w >>= 1) mm += __shfl_down(mm, w);  // p_j += p_{j+w} for j < w, w = 32 ... 1: partial j + w sits w lanes up
+        },
+        [&](bool complete) {
+            if (!complete) return;
+            rows::fold(mm);
 #pragma unroll
             for (int k = 0; k < kTonedetSlots; k++)
-                if (f[k]) {
-#pragma unroll
-                    for (int w = kT / 2; w >= 1; w >>= 1) { re[k] += __shfl_down(re[k], w); im[k] += __shfl_down(im[k], w); }
-                }
+                if (f[k]) rows::fold(re[k], im[k]);
             if (lane == 0) {
                 const double MM = mm;
                 const int g = (int)(G % (unsigned long long)kTonedetRing);
-                const double big = 1.7976931348623157e308;                   // neither inf nor NaN
-                const bool finite = fabs(MM) <= big;
+                const bool finite = rows::finite(MM);
                 st->ring_mm[g] = MM;
                 if (!finite) st->nonfinite++;
                 const bool usable = finite && MM > gt->min_e;
@@ -218,8 +151,8 @@ __global__ __launch_bounds__(kT) void k_tonedet(const float2* __restrict__ in, l
                 for (int k = 0; k < kTonedetSlots; k++) {
                     const double PW = f[k] ? fma(re[k], re[k], im[k] * im[k]) : 0.0;
                     st->ring_pw[k][g] = PW;
-                    const bool present = f[k] != 0u && usable && fabs(PW) <= big && 2.0 * PW > gt->c[k] * ref;
-                    flags = td_detect(st, k, flags, present, gt->raise_intervals[k], gt->clear_intervals[k]);
+                    const bool present = f[k] != 0u && usable && rows::finite(PW) && 2.0 * PW > gt->c[k] * ref;
+                    flags = rows::detect(flags, k, present, gt->raise_intervals[k], gt->clear_intervals[k], st->run[k], st->transitions[k]);
                 }
 #pragma unroll
                 for (int k = 0; k < kTonedetSlots; k++) {
@@ -234,10 +167,7 @@ __global__ __launch_bounds__(kT) void k_tonedet(const float2* __restrict__ in, l
                 re[k] = 0.0; im[k] = 0.0;
                 f[k] = (unsigned)__builtin_amdgcn_readfirstlane(gt->freq_hz[k]);
             }
-            r0 = 0;
-        }
-        s0 = seg_end;
-    }
+        });
 
     // what the next call needs: the open interval's partials, and the record
     pp[0] = mm;
@@ -346,25 +276,23 @@ int fmd_tonedet_destroy(fmd_tonedet t) {
 
 int fmd_tonedet_reset(fmd_tonedet t, int channel) {
     if (!t) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= t->C) return td_fail(t, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, t->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, t->C, &c0, &cn)) return td_fail(t, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, t->C);
     if (!t->order.quiesce()) return td_fail(t, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? t->C : 1;
     hipLaunchKernelGGL(k_tonedet_reset, dim3((unsigned)cn), dim3(kT), 0, nullptr, c0, t->d_gate, t->d_status, t->d_part);
-    if (hipGetLastError() != hipSuccess) return td_fail(t, FMD_ERR_DEVICE, "k_tonedet_reset launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return td_fail(t, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_tonedet_reset launch failed")) return td_fail(t, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 
 int fmd_tonedet_set_params(fmd_tonedet t, int channel, const fmd_tonedet_params* p) {
     if (!t) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= t->C) return td_fail(t, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, t->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, t->C, &c0, &cn)) return td_fail(t, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, t->C);
     TonedetGate g;
     if (fmd::tonedet_gate(p, t->fs, &g, &t->err) != FMD_OK) return FMD_ERR_ARG;
     if (!t->order.quiesce()) return td_fail(t, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? t->C : 1;
     hipLaunchKernelGGL(k_tonedet_set, dim3((unsigned)((cn + kT - 1) / kT)), dim3(kT), 0, nullptr, c0, cn, t->M, g, t->d_gate, t->d_status);
-    if (hipGetLastError() != hipSuccess) return td_fail(t, FMD_ERR_DEVICE, "k_tonedet_set launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return td_fail(t, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_tonedet_set launch failed")) return td_fail(t, FMD_ERR_DEVICE, "%s", e);
     for (int c = c0; c < c0 + cn; c++) t->params[(size_t)c] = *p;
     return FMD_OK;
 }

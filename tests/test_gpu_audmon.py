@@ -196,6 +196,30 @@ def test_call_lengths(pkg, x1, pre, basic, step):
     assert np.array_equal(bits(m.status()), bits(basic[0])) and np.array_equal(flags.cpu().numpy(), basic[1]) and np.array_equal(ok.cpu().numpy(), basic[2])
 
 
+@pytest.mark.parametrize("first", [0, M - 2])
+def test_small_calls(pkg, ref, x1, first):
+    """Calls of 1, 3, 4, 5, 255, 256 and 257 frames and one that runs to M + 2 behind their start, every station from frame 0 of a fresh
+    monitor or behind a first call of M - 2 frames, so that the 1-, 3- and 4-frame calls straddle an interval's end inside one lane's
+    four frames: a lone frame, a partial quad, a whole one, a quad plus one, a row less one, a whole row, a row plus one, and an
+    interval's end inside a quad and inside a row.  Records and bytes are the restatement's after every call."""
+    import torch
+    xd = _cuda(x1)
+    m = pkg.AudioMonitor(3, FS)
+    m.set_params(**SP)
+    chans = [ref.channel(FS, **SP) for _ in range(3)]
+    flags = torch.full((3,), 0xAA, dtype=torch.uint8, device="cuda")
+    ok = torch.full((3,), 0xAA, dtype=torch.uint8, device="cuda")
+    small = (1, 3, 4, 5, 255, 256, 257)
+    a = 0
+    for step in ((first,) if first else ()) + small + (M + 2 - sum(small),):      # the last call ends M + 2 frames behind the small calls' start
+        m.process(xd[:, a:], n=step, flags=flags, ok=ok)
+        for c in range(3):
+            chans[c].process(x1[c, a:a + step])
+        a += step
+        _same(m.status(), chans, f"first call {first}, {a} frames in", flags.cpu().numpy(), ok.cpu().numpy())
+    assert a == first + M + 2 and [int(v) for v in m.status()["intervals"]] == [2 if first else 1] * 3
+
+
 def test_n_zero_still_writes_both_bytes(pkg, ref, x1, pre):
     import torch
     xd = _cuda(x1)

@@ -157,6 +157,33 @@ def test_call_lengths(pkg, x1, basic, step):
     assert np.array_equal(bits(q.status()), bits(basic[0])) and np.array_equal(mask.cpu().numpy(), basic[1])
 
 
+@pytest.mark.parametrize("first", [0, M - 2])
+@pytest.mark.parametrize("fmt", ["cf32", "u8"])
+def test_small_calls(pkg, ref, x1, fmt, first):
+    """Calls of 1, 3, 4, 5, 255, 256 and 257 samples and one that runs to M + 2 behind their start, every station from sample 0 of a
+    fresh squelch or behind a first call of M - 2 samples, so that the 1-, 3- and 4-sample calls straddle an interval's end inside one
+    lane's four samples: a lone sample, a partial quad, a whole one, a quad plus one, a row less one, a whole row, a row plus one, and
+    an interval's end inside a quad and inside a row.  Records and mask bytes are the restatement's after every call."""
+    import torch
+    x = x1[:, :2 * M] if fmt == "cf32" else squelch_ref.to_u8(x1[:, :2 * M] * (40.0 / np.float32(AMPL))[:, None, None])
+    xd = _cuda(x)
+    q = pkg.Squelch(3, FS)
+    q.set_params(**GP)
+    chans = [ref.channel(FS) for _ in range(3)]
+    for ch in chans:
+        assert ch.set_params(**GP) == 0
+    mask = torch.full((3,), 0xAA, dtype=torch.uint8, device="cuda")
+    small = (1, 3, 4, 5, 255, 256, 257)
+    a = 0
+    for step in ((first,) if first else ()) + small + (M + 2 - sum(small),):      # the last call ends M + 2 samples behind the small calls' start
+        q.process(xd[:, a:], n=step, mask=mask)
+        for c in range(3):
+            chans[c].process(x[c, a:a + step])
+        a += step
+        _same(q.status(), chans, f"{fmt}, first call {first}, {a} samples in", mask.cpu().numpy())
+    assert a == first + M + 2 and [int(v) for v in q.status()["intervals"]] == [2 if first else 1] * 3
+
+
 def test_n_zero_still_writes_the_mask(pkg, ref, x1):
     import torch
     xd = _cuda(x1)
