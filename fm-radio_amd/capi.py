@@ -288,6 +288,25 @@ FPRINT_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("prints", "<u8"), ("nonfinit
 assert FPRINT_STATUS_DTYPE.itemsize == 32
 
 
+class FpmatchConfig(C.Structure):
+    """include/fmdemod.h fmd_fpmatch_config"""
+    _fields_ = [("n_channels", C.c_int), ("n_bits", C.c_int), ("block", C.c_int), ("interval", C.c_int), ("max_errs", C.c_int), ("hold", C.c_int),
+                ("max_words", C.c_int), ("max_tracks", C.c_int), ("max_catalogue_words", C.c_longlong), ("device", C.c_int)]
+
+
+class FpmatchDesign(C.Structure):
+    """include/fmdemod.h fmd_fpmatch_design_t"""
+    _fields_ = [("mask", C.c_uint), ("tile", C.c_int), ("query_block", C.c_int), ("groups", C.c_int), ("lds_bytes", C.c_int), ("max_events", C.c_longlong),
+                ("max_queries", C.c_longlong)]
+
+
+# include/fmdemod.h fmd_fpmatch_status (64 bytes) and fmd_fpmatch_event (24 bytes)
+FPMATCH_STATUS_DTYPE = np.dtype([("words", "<u8"), ("queries", "<u8"), ("hits", "<u8"), ("clamped", "<u8"), ("since", "<u8"), ("track", "<i4"), ("offset", "<i4"),
+                                 ("errs", "<u4"), ("misses", "<u4"), ("fill", "<u4"), ("flags", "<u4")])
+FPMATCH_EVENT_DTYPE = np.dtype([("end", "<u8"), ("track", "<i4"), ("offset", "<i4"), ("errs", "<u4"), ("flags", "<u4")])
+assert FPMATCH_STATUS_DTYPE.itemsize == 64 and FPMATCH_EVENT_DTYPE.itemsize == 24
+
+
 class SameConfig(C.Structure):
     _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
 
@@ -572,6 +591,19 @@ def load_library():
     L.fmd_fprint_create.argtypes = [C.POINTER(FprintConfig), C.POINTER(C.c_void_p)]
     L.fmd_fprint_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
                                              C.c_longlong, C.c_void_p]
+    L.fmd_fpmatch_default_config.argtypes = [C.POINTER(FpmatchConfig)]
+    L.fmd_fpmatch_max_events.argtypes = [C.c_int, C.c_longlong]
+    L.fmd_fpmatch_max_events.restype = C.c_longlong
+    L.fmd_fpmatch_max_errs.argtypes = [C.c_int, C.c_int, C.c_int]
+    L.fmd_fpmatch_max_errs.restype = C.c_longlong
+    L.fmd_fpmatch_design.argtypes = [C.POINTER(FpmatchConfig), C.POINTER(FpmatchDesign)]
+    L.fmd_fpmatch_check_catalogue.argtypes = [C.POINTER(FpmatchConfig), C.c_void_p, C.c_int]
+    L.fmd_fpmatch_state_bytes.argtypes = [C.POINTER(FpmatchConfig)]
+    L.fmd_fpmatch_state_bytes.restype = C.c_longlong
+    L.fmd_fpmatch_create.argtypes = [C.POINTER(FpmatchConfig), C.POINTER(C.c_void_p)]
+    L.fmd_fpmatch_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.fmd_fpmatch_process_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
     L.fmd_same_default_params.argtypes = [C.POINTER(SameParams)]
     L.fmd_same_default_params.restype = None
     L.fmd_same_encode.argtypes = [C.POINTER(SameEncodeConfig), C.c_char_p, C.c_int, C.c_void_p, C.c_longlong]
@@ -583,13 +615,13 @@ def load_library():
     L.fmd_same_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SameParams)]
     L.fmd_same_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # what every side object declares alike
-    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "fprint", "rdsdec"):
+    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "fprint", "fpmatch", "rdsdec"):
         getattr(L, f"fmd_{pre}_destroy").argtypes = [C.c_void_p]
         getattr(L, f"fmd_{pre}_last_error").restype = C.c_char_p
         getattr(L, f"fmd_{pre}_last_error").argtypes = [C.c_void_p]
-    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "fprint"):
+    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "fprint", "fpmatch"):
         getattr(L, f"fmd_{pre}_reset").argtypes = [C.c_void_p, C.c_int]
-        if pre not in ("tonedet", "adpcm", "same", "flac", "logmel", "fprint"):   # (the tone detector, the encoders, the SAME decoder, the log-mel front end and the fingerprinter hold no peaks)
+        if pre not in ("tonedet", "adpcm", "same", "flac", "logmel", "fprint", "fpmatch"):   # (the tone detector, the encoders, the SAME decoder, the log-mel front end, the fingerprinter and the matcher hold no peaks)
             getattr(L, f"fmd_{pre}_reset_peaks").argtypes = [C.c_void_p, C.c_int]
         getattr(L, f"fmd_{pre}_get_status").argtypes = [C.c_void_p, C.c_void_p]
         getattr(L, f"fmd_{pre}_status_dev").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -2533,3 +2565,158 @@ class Fingerprinter(_Monitor):
         self._check(self.L.fmd_fprint_process_f32_dev(self.g, px, in_stride, n, pa, C.c_void_p(out.data_ptr()), stride, pn, pe, estride, C.c_void_p(stream)))
         res = (out, None if nprints is False else nprints)
         return res if energy is None else res + (energy,)
+
+
+def fpmatch_default_config(**fields) -> FpmatchConfig:
+    """fmd_fpmatch_default_config (host only): 32 bits, blocks of 256 words searched every 64, the threshold at a bit error rate of
+    0.35, hold 3; `fields` then replace the named fields.  Where block or n_bits is given and max_errs is not, max_errs follows them at
+    0.35"""
+    L = load_library()
+    cfg = FpmatchConfig()
+    rc = L.fmd_fpmatch_default_config(C.byref(cfg))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_fpmatch", rc)
+    for k, v in fields.items():
+        if k not in dict(FpmatchConfig._fields_):
+            raise TypeError(f"FpmatchConfig has no field {k}")
+        setattr(cfg, k, v)
+    if "max_errs" not in fields and ("block" in fields or "n_bits" in fields):
+        cfg.max_errs = (35 * cfg.block * cfg.n_bits) // 100
+    return cfg
+
+
+def fpmatch_max_events(interval: int, n: int) -> int:
+    """fmd_fpmatch_max_events (host only): (n + interval - 1) / interval, the most events a call of n words writes for a station"""
+    L = load_library()
+    rc = L.fmd_fpmatch_max_events(int(interval), int(n))
+    if rc < 0:
+        raise _global_error(L, "fmd_fpmatch", int(rc))
+    return int(rc)
+
+
+def fpmatch_max_errs(ber_percent: int, block: int = 256, n_bits: int = 32) -> int:
+    """fmd_fpmatch_max_errs (host only): (ber_percent * block * n_bits) / 100 in integers"""
+    L = load_library()
+    rc = L.fmd_fpmatch_max_errs(int(ber_percent), int(block), int(n_bits))
+    if rc < 0:
+        raise _global_error(L, "fmd_fpmatch", int(rc))
+    return int(rc)
+
+
+def fpmatch_state_bytes(cfg: FpmatchConfig) -> int:
+    """fmd_fpmatch_state_bytes (host only): the device memory an object of cfg holds"""
+    L = load_library()
+    rc = L.fmd_fpmatch_state_bytes(C.byref(cfg))
+    if rc < 0:
+        raise _global_error(L, "fmd_fpmatch", int(rc))
+    return int(rc)
+
+
+def fpmatch_design(cfg: FpmatchConfig) -> FpmatchDesign:
+    """fmd_fpmatch_design (host only): the mask and what the search kernel is built on (tile, query_block, groups, lds_bytes)"""
+    L = load_library()
+    d = FpmatchDesign()
+    rc = L.fmd_fpmatch_design(C.byref(cfg), C.byref(d))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_fpmatch", rc)
+    return d
+
+
+def fpmatch_check_catalogue(cfg: FpmatchConfig, starts, n_tracks: int | None = None) -> bool:
+    """fmd_fpmatch_check_catalogue (host only): whether load() would take a catalogue whose tracks start at `starts` [T + 1]"""
+    L = load_library()
+    st = np.ascontiguousarray(starts if starts is not None else [], np.int64).reshape(-1)
+    T = int(n_tracks) if n_tracks is not None else max(st.size - 1, 0)
+    if T + 1 > st.size and T > 0:
+        raise ValueError("starts holds n_tracks + 1 entries")
+    return L.fmd_fpmatch_check_catalogue(C.byref(cfg), st.ctypes.data_as(C.c_void_p) if st.size else None, T) == FMD_OK
+
+
+def _fpmatch_words(t) -> np.ndarray:
+    """a run of fingerprint words as uint32: int32 arrays (what Fingerprinter's tensors give on the host) keep their bit patterns"""
+    t = np.ascontiguousarray(t).reshape(-1)
+    return t.view(np.uint32) if t.dtype == np.int32 else t.astype(np.uint32)
+
+
+class FingerprintMatcher(_Monitor):
+    """Catalogue search for C stations' fingerprints on the GPU (fmd_fpmatch_*): holds a catalogue of reference fingerprints and per
+    station its newest `block` words, takes what Fingerprinter.process returns (the [C, max_prints] int32 words and the [C] int32 counts)
+    and, whenever a station's word count crosses a multiple of `interval`, searches the whole catalogue for the station's newest words.
+    process() returns the events ([C, max_events, 3] int64 tensor: view a station's row with events_of()), their [C] int32 counts and the
+    [C] uint8 flags and ok bytes, all on the device.  status() returns FPMATCH_STATUS_DTYPE records.  **config: the fields of FpmatchConfig
+    over fpmatch_default_config()."""
+    _prefix, _attr, _status_dtype = "fmd_fpmatch", "g", FPMATCH_STATUS_DTYPE
+
+    def __init__(self, n_channels: int, **config):
+        self.L = load_library()
+        self.g = None
+        self.cfg = fpmatch_default_config(n_channels=int(n_channels), **config)
+        self._create("create", C.byref(self.cfg))
+        self.n_channels = int(n_channels)
+        self.block, self.interval, self.n_bits, self.max_errs, self.hold = self.cfg.block, self.cfg.interval, self.cfg.n_bits, self.cfg.max_errs, self.cfg.hold
+        self.design = fpmatch_design(self.cfg)
+        self.state_bytes = fpmatch_state_bytes(self.cfg)
+        self.n_tracks, self.catalogue_words = 0, 0
+
+    def reset_peaks(self, channel: int = -1):
+        raise AttributeError("the matcher holds no peaks")
+
+    def load(self, tracks):
+        """replaces the catalogue by `tracks`, a sequence of runs of uint32 words (an empty one empties it); waits for the object's work"""
+        tracks = [_fpmatch_words(t) for t in tracks]
+        starts = np.concatenate([[0], np.cumsum([t.size for t in tracks])]).astype(np.int64)
+        self.load_raw(np.concatenate(tracks) if tracks else np.zeros(0, np.uint32), starts, len(tracks))
+
+    def load_raw(self, words, starts, n_tracks: int):
+        """fmd_fpmatch_load: words [starts[n_tracks]] uint32 and starts [n_tracks + 1] in host memory"""
+        words = np.ascontiguousarray(words, np.uint32).reshape(-1)
+        starts = np.ascontiguousarray(starts, np.int64).reshape(-1)
+        if starts.size < int(n_tracks) + 1 or (int(n_tracks) > 0 and 0 <= int(starts[int(n_tracks)]) and words.size < int(starts[int(n_tracks)])):
+            raise ValueError("starts holds n_tracks + 1 entries and words starts[n_tracks] words")
+        self._check(self.L.fmd_fpmatch_load(self.g, words.ctypes.data_as(C.c_void_p) if words.size else None, starts.ctypes.data_as(C.c_void_p), int(n_tracks)))
+        self.n_tracks, self.catalogue_words = int(n_tracks), int(starts[int(n_tracks)]) if n_tracks else 0
+
+    @staticmethod
+    def events_of(events, nevents=None, channel: int = 0) -> np.ndarray:
+        """station `channel`'s row of process()'s events as FPMATCH_EVENT_DTYPE records on the host, the first nevents[channel] where the
+        counts are given"""
+        row = events[channel].cpu().numpy().reshape(-1).view(FPMATCH_EVENT_DTYPE)
+        return row if nevents is None else row[:int(nevents[channel])]
+
+    def process(self, words, nwords=None, n: int | None = None, active=None, events=None, nevents=None, flags=None, ok=None, stream=None):
+        """takes up to n words (default: all columns) of every station.  words: [C, >= n] int32 CUDA tensor with contiguous rows, as
+        Fingerprinter.process returns it; nwords: the [C] int32 counts on the device, None = n for every station; active: None or a [C]
+        uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole); events: the [C, >= fpmatch_max_events(interval, n), 3]
+        int64 CUDA tensor to write, None = a new zeroed one of exactly that; nevents: [C] int32, flags, ok: [C] uint8 CUDA tensors to
+        write, None = new ones, False = not written.  Returns (events, nevents, flags, ok).  Asynchronous on `stream` (default:
+        torch's current)."""
+        import torch
+        Cn = self.n_channels
+        if not (words.is_cuda and words.dtype == torch.int32 and words.dim() == 2 and words.shape[0] == Cn and (words.stride(1) == 1 or words.shape[1] <= 1)):
+            raise ValueError("words must be a [C, n] int32 CUDA tensor with contiguous rows")
+        n = int(words.shape[1]) if n is None else int(n)
+        wstride = words.stride(0) if Cn > 1 else words.shape[1]
+        if nwords is not None and not (nwords.is_cuda and nwords.dtype == torch.int32 and nwords.shape == (Cn,) and nwords.is_contiguous()):
+            raise ValueError("nwords must be a contiguous [C] int32 CUDA tensor")
+        pa, stream = _active_ptr(active, Cn), _stream_ptr(stream, words.device)
+        rows = (max(n, 0) + self.interval - 1) // self.interval
+        with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=words.device) if stream else torch.cuda.default_stream(words.device)):
+            if events is None:
+                events = torch.zeros((Cn, max(rows, 1), 3), dtype=torch.int64, device=words.device)
+            if nevents is None:
+                nevents = torch.zeros(Cn, dtype=torch.int32, device=words.device)
+        if not (events.is_cuda and events.dtype == torch.int64 and events.dim() == 3 and events.shape[0] == Cn and events.shape[2] == 3 and events.stride(2) == 1
+                and events.stride(1) == 3):
+            raise ValueError("events must be a [C, max_events, 3] int64 CUDA tensor with contiguous rows")
+        if events.shape[1] < rows:
+            raise ValueError(f"events holds {events.shape[1]} events a station; the call may write {rows}")
+        if nevents is not False and not (nevents.is_cuda and nevents.dtype == torch.int32 and nevents.shape == (Cn,) and nevents.is_contiguous()):
+            raise ValueError("nevents must be a contiguous [C] int32 CUDA tensor")
+        flags, pf = _byte_out(flags, "flags", Cn, words.device, stream)
+        ok, po = _byte_out(ok, "ok", Cn, words.device, stream)
+        estride = events.stride(0) // 3 if Cn > 1 else events.shape[1]
+        pn = None if nevents is False else C.c_void_p(nevents.data_ptr())
+        pw = None if nwords is None else C.c_void_p(nwords.data_ptr())
+        self._check(self.L.fmd_fpmatch_process_dev(self.g, C.c_void_p(words.data_ptr()), wstride, pw, n, pa, C.c_void_p(events.data_ptr()), estride, pn, pf, po,
+                                                   C.c_void_p(stream)))
+        return events, (None if nevents is False else nevents), flags, ok

@@ -1,0 +1,455 @@
+// Fingerprint matcher, device side (include/fmdemod.h, "Fingerprint matcher").
+//
+// NOT in the reference.  Per station a ring of its newest W fingerprint words; whenever the station's word count crosses a multiple of
+// the interval, its newest W words against every valid position of the catalogue: errs = sum popcount((q ^ cat) & mask), the smallest,
+// on a tie the lowest position.  All integer, so every tiling gives the same result.
+//
+// Four kernels a call:
+//   k_fpmatch_map     one workgroup: the queries each active station fires, as an exclusive prefix sum: the rows of the search.
+//   k_fpmatch_gather  a workgroup a query: its W words, masked, from the ring and the caller's new words into a contiguous window.
+//   k_fpmatch_search  queries x catalogue positions with depth W.  A workgroup holds kFpmatchQueries queries and walks the column tiles
+//                     of its column group: the tile's kFpmatchTile + W - 1 catalogue words are staged once in LDS, lane <-> position
+//                     (lane p reads word p + j: consecutive lanes, consecutive banks), the queries' words are wave-uniform and come
+//                     through scalar loads, and a step is one XOR and one accumulating population count a query.  The minimum is the
+//                     packed key errs << 32 | p, so an unsigned minimum is the tie rule; it is carried in registers over the group's
+//                     tiles, reduced across lanes by shuffles and across the four wavefronts through LDS, and written as the group's
+//                     partial minimum.
+//   k_fpmatch_finish  a wavefront a station: per query the minimum over the groups' partials, the track from the starts table, the
+//                     detector, the event; then the ring's newest words, the record, the count and the bytes.
+// No atomics, no register spills (scratch 0), no workgroup waits on another, ordinary vector stores only.
+//
+// Bounds: k_fpmatch_gather reads ring slots taken mod W, new words below the station's k <= n <= words_stride, and writes window rows
+// below qbase[C] <= C * max_events(I, n) <= max_queries.  k_fpmatch_search reads catalogue words below D (zero behind it), LDS words below
+// kFpmatchTile - 1 + W - 1 < lds_words, starts entries 0 ... T, window rows below qbase[C] (a row past the last repeats it) and writes
+// partials at row * G + group, group < G <= groups.  k_fpmatch_finish writes events below the station's count <= max_events(I, n) <=
+// events_stride and ring slots mod W.
+#include <hip/hip_runtime.h>
+
+#include <cstddef>
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "fmd_fpmatch_design.h"
+#include "fmd_side.h"
+#include "fmdemod.h"
+
+using fmd::FpmatchLayout;
+using fmd::kFpmatchQueries;
+using fmd::kFpmatchThreads;
+using fmd::kFpmatchTile;
+
+namespace {
+
+constexpr int kMapT = 1024;
+constexpr int kQR = kFpmatchQueries;
+constexpr int kWaves = kFpmatchThreads / 64;
+constexpr int kPasses = kFpmatchTile / kFpmatchThreads;
+constexpr unsigned long long kNoKey = ~0ull;
+static_assert(kFpmatchTile % kFpmatchThreads == 0, "a tile is whole passes of a workgroup");
+
+static_assert(sizeof(fmd_fpmatch_status) == 64 && offsetof(fmd_fpmatch_status, since) == 32 && offsetof(fmd_fpmatch_status, track) == 40 &&
+              offsetof(fmd_fpmatch_status, errs) == 48 && offsetof(fmd_fpmatch_status, flags) == 60, "fmd_fpmatch_status layout");
+static_assert(sizeof(fmd_fpmatch_event) == 24 && offsetof(fmd_fpmatch_event, track) == 8 && offsetof(fmd_fpmatch_event, errs) == 16, "fmd_fpmatch_event layout");
+
+// what the kernels read of the configuration
+struct FpmDev {
+    int C, W, I, hold;
+    unsigned max_errs, mask;
+};
+
+// ---- the pieces a later object (station against station) can reuse: the take, the query schedule, the ring and the error count
+
+// the words station c hands over: d_nwords[c] clamped into [0, n]
+__device__ __forceinline__ int fpm_take(const int* __restrict__ nwords, int c, int n, bool* clamped) {
+    *clamped = false;
+    if (!nwords) return n;
+    const int k = nwords[c];
+    *clamped = k < 0 || k > n;
+    return k < 0 ? 0 : (k > n ? n : k);
+}
+
+// the queries of a station that had `before` words and takes k: their number, and the first one's e
+__device__ __forceinline__ int fpm_queries(unsigned long long before, int k, int W, int I, unsigned long long* e0) {
+    const unsigned long long after = before + (unsigned long long)k;
+    const unsigned long long m = before > (unsigned long long)(W - 1) ? before : (unsigned long long)(W - 1);   // e > m
+    *e0 = (m / (unsigned long long)I + 1ull) * (unsigned long long)I;
+    const long long cnt = (long long)(after / (unsigned long long)I) - (long long)(m / (unsigned long long)I);
+    return cnt > 0 ? (int)cnt : 0;
+}
+
+// word i of a station (counted from its reset): in the ring [W] where the station had it before this call, else among the new words
+__device__ __forceinline__ uint32_t fpm_word(const uint32_t* __restrict__ ring, const uint32_t* __restrict__ fresh, int W, unsigned long long before,
+                                             unsigned long long i) {
+    return i < before ? ring[(int)(i % (unsigned long long)W)] : fresh[(size_t)(i - before)];
+}
+
+// errs += popcount(q ^ c), both masked already: v_xor_b32, v_bcnt_u32_b32
+__device__ __forceinline__ unsigned fpm_errs(unsigned errs, uint32_t q, uint32_t c) { return (unsigned)__builtin_popcount(q ^ c) + errs; }
+
+// the track of position p: the largest t with starts[t] <= p
+__device__ __forceinline__ int fpm_track(const int* __restrict__ starts, int T, int p) {
+    int lo = 0, hi = T;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (starts[mid] <= p) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+// the station of row r: qbase[c] <= r < qbase[c + 1]
+__device__ __forceinline__ int fpm_station(const int* __restrict__ qbase, int C, int r) {
+    int lo = 0, hi = C;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (qbase[mid] <= r) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ unsigned long long fpm_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+
+// the minimum over the wavefront, in every lane
+__device__ __forceinline__ unsigned long long fpm_wave_min(unsigned long long v) {
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, d, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), d, 64);
+        v = fpm_min(v, ((unsigned long long)hi << 32) | lo);
+    }
+    return v;
+}
+
+// qbase [C + 1]: the exclusive prefix sum of the queries each active station fires
+__global__ __launch_bounds__(kMapT) void k_fpmatch_map(FpmDev g, int n, const int* __restrict__ nwords, const uint8_t* __restrict__ active,
+                                                      const fmd_fpmatch_status* __restrict__ status, int* __restrict__ qbase) {
+    __shared__ int part[kMapT];
+    const int tid = threadIdx.x, C = g.C;
+    const int per = (C + kMapT - 1) / kMapT;
+    const int c0 = min(tid * per, C), c1 = min(c0 + per, C);
+    auto count = [&](int c) {
+        if (active && active[c] == 0) return 0;
+        bool cl;
+        unsigned long long e0;
+        return fpm_queries(status[c].words, fpm_take(nwords, c, n, &cl), g.W, g.I, &e0);
+    };
+    int sum = 0;
+    for (int c = c0; c < c1; c++) sum += count(c);
+    part[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < kMapT; d <<= 1) {
+        const int v = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    int run = part[tid] - sum;
+    for (int c = c0; c < c1; c++) {
+        qbase[c] = run;
+        run += count(c);
+    }
+    if (tid == kMapT - 1) qbase[C] = part[tid];
+}
+
+// qwin [rows][W]: row r's window, masked
+__global__ __launch_bounds__(64) void k_fpmatch_gather(FpmDev g, int n, const int* __restrict__ nwords, const fmd_fpmatch_status* __restrict__ status,
+                                                      const int* __restrict__ qbase, const uint32_t* __restrict__ ring_all, const uint32_t* __restrict__ words,
+                                                      long long words_stride, uint32_t* __restrict__ qwin) {
+    const int r = blockIdx.x;
+    if (r >= qbase[g.C]) return;                                             // surplus workgroups leave at once
+    const int c = fpm_station(qbase, g.C, r);
+    const unsigned long long before = status[c].words;
+    bool cl;
+    unsigned long long e0;
+    (void)fpm_queries(before, fpm_take(nwords, c, n, &cl), g.W, g.I, &e0);
+    const unsigned long long e = e0 + (unsigned long long)(r - qbase[c]) * (unsigned long long)g.I;
+    const uint32_t* ring = ring_all + (size_t)c * (size_t)g.W;
+    const uint32_t* fresh = words + (size_t)c * (size_t)words_stride;
+    for (int j = threadIdx.x; j < g.W; j += 64)
+        qwin[(size_t)r * (size_t)g.W + j] = fpm_word(ring, fresh, g.W, before, e - (unsigned long long)g.W + (unsigned long long)j) & g.mask;
+}
+
+// cat [D], masked; starts [T + 1]; part [rows][G]
+__global__ __launch_bounds__(kFpmatchThreads) void k_fpmatch_search(int C, int W, const int* __restrict__ qbase, const uint32_t* __restrict__ qwin,
+                                                                   const uint32_t* __restrict__ cat, int D, const int* __restrict__ starts, int T, int G,
+                                                                   unsigned long long* __restrict__ part) {
+    extern __shared__ uint32_t s_cat[];                                      // [kFpmatchTile + W - 1]
+    __shared__ unsigned long long s_red[kWaves][kQR];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int Q = qbase[C];
+    const int r0 = blockIdx.x * kQR;
+    if (r0 >= Q) return;                                                     // surplus workgroups leave at once (uniform)
+    const int npos = D - W + 1, ntiles = (npos + kFpmatchTile - 1) / kFpmatchTile;
+    const uint32_t* qp[kQR];
+#pragma unroll
+    for (int r = 0; r < kQR; r++) qp[r] = qwin + (size_t)min(r0 + r, Q - 1) * (size_t)W;   // a row past the last repeats it
+    unsigned long long best[kQR];
+#pragma unroll
+    for (int r = 0; r < kQR; r++) best[r] = kNoKey;
+
+    for (int t = blockIdx.y; t < ntiles; t += G) {
+        const int base = t * kFpmatchTile;
+        __syncthreads();                                                     // the tile before is read
+        for (int i = tid; i < kFpmatchTile + W - 1; i += kFpmatchThreads) s_cat[i] = base + i < D ? cat[base + i] : 0u;
+        __syncthreads();
+        for (int s = 0; s < kPasses; s++) {
+            const int pl = s * kFpmatchThreads + wave * 64 + lane, p = base + pl;
+            bool valid = p < npos;
+            if (valid) {
+                const int tr = fpm_track(starts, T, p);
+                valid = p + W <= starts[tr + 1];
+            }
+            if (!__any(valid)) continue;                                     // (per wavefront; no barrier inside)
+            unsigned acc[kQR];
+#pragma unroll
+            for (int r = 0; r < kQR; r++) acc[r] = 0u;
+            const uint32_t* cp = s_cat + pl;
+            for (int j0 = 0; j0 < W; j0 += 8) {
+#pragma unroll
+                for (int jj = 0; jj < 8; jj++) {
+                    const uint32_t cw = cp[j0 + jj];
+#pragma unroll
+                    for (int r = 0; r < kQR; r++) acc[r] = fpm_errs(acc[r], qp[r][j0 + jj], cw);
+                }
+            }
+            if (valid) {
+#pragma unroll
+                for (int r = 0; r < kQR; r++) best[r] = fpm_min(best[r], ((unsigned long long)acc[r] << 32) | (unsigned)p);
+            }
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kQR; r++) {
+        const unsigned long long m = fpm_wave_min(best[r]);
+        if (lane == 0) s_red[wave][r] = m;
+    }
+    __syncthreads();
+    if (tid < kQR && r0 + tid < Q) {
+        unsigned long long m = s_red[0][tid];
+#pragma unroll
+        for (int w = 1; w < kWaves; w++) m = fpm_min(m, s_red[w][tid]);
+        part[(size_t)(r0 + tid) * (size_t)G + blockIdx.y] = m;
+    }
+}
+
+// a wavefront a station; G = 0 with an empty catalogue
+__global__ __launch_bounds__(64) void k_fpmatch_finish(FpmDev g, int n, const int* __restrict__ nwords, const uint8_t* __restrict__ active, const int* __restrict__ qbase,
+                                                      const unsigned long long* __restrict__ part, int G, const int* __restrict__ starts, int T,
+                                                      const uint32_t* __restrict__ words, long long words_stride, fmd_fpmatch_status* __restrict__ status,
+                                                      uint32_t* __restrict__ ring_all, fmd_fpmatch_event* __restrict__ events, long long events_stride,
+                                                      int* __restrict__ nevents, uint8_t* __restrict__ flags, uint8_t* __restrict__ ok) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (active && active[c] == 0) return;
+    fmd_fpmatch_status st = status[c];
+    const unsigned long long before = st.words;
+    bool clamped;
+    const int k = fpm_take(nwords, c, n, &clamped);
+    unsigned long long e0;
+    const int cnt = fpm_queries(before, k, g.W, g.I, &e0);
+    const int row0 = qbase[c];
+    // every lane walks the detector alike; lane 0 stores
+    for (int i = 0; i < cnt; i++) {
+        unsigned long long key = kNoKey;
+        for (int y = lane; y < G; y += 64) key = fpm_min(key, part[(size_t)(row0 + i) * (size_t)G + y]);
+        key = fpm_wave_min(key);
+        const unsigned long long e = e0 + (unsigned long long)i * (unsigned long long)g.I;
+        int track = -1, offset = 0;
+        unsigned errs = 0xffffffffu;
+        if (key != kNoKey) {
+            const int p = (int)(unsigned)key;
+            errs = (unsigned)(key >> 32);
+            track = fpm_track(starts, T, p);
+            offset = p - starts[track];
+        }
+        const bool hit = track >= 0 && errs <= g.max_errs;
+        st.queries += 1;
+        st.errs = errs;
+        if (hit) {
+            st.hits += 1;
+            if (st.track != track) { st.track = track; st.since = e; }
+            st.offset = offset;
+            st.misses = 0;
+        } else if (st.track >= 0) {
+            st.misses += 1;
+            if (st.misses == (unsigned)g.hold) { st.track = -1; st.misses = 0; }
+        }
+        st.flags = hit ? 2u : 0u;
+        if (lane == 0) {
+            fmd_fpmatch_event ev;
+            ev.end = e; ev.track = track; ev.offset = offset; ev.errs = errs; ev.flags = hit ? 1u : 0u;
+            events[(size_t)c * (size_t)events_stride + (size_t)i] = ev;
+        }
+    }
+    // the ring's newest words: of the k new ones the last min(k, W)  (k_fpmatch_gather, the ring's only reader, is done)
+    uint32_t* ring = ring_all + (size_t)c * (size_t)g.W;
+    for (int j = (k > g.W ? k - g.W : 0) + lane; j < k; j += 64)
+        ring[(int)((before + (unsigned long long)j) % (unsigned long long)g.W)] = words[(size_t)c * (size_t)words_stride + (size_t)j];
+    if (lane == 0) {
+        st.words = before + (unsigned long long)k;
+        st.clamped += clamped ? 1ull : 0ull;
+        st.fill = st.words < (unsigned long long)g.W ? (unsigned)st.words : (unsigned)g.W;
+        st.flags = (st.flags & 2u) | (st.track >= 0 ? 1u : 0u);
+        status[c] = st;
+        if (nevents) nevents[c] = cnt;
+        if (flags) flags[c] = (uint8_t)st.flags;
+        if (ok) ok[c] = (uint8_t)(st.flags & 1u);
+    }
+}
+
+// stations c0 ... as after create
+__global__ __launch_bounds__(64) void k_fpmatch_reset(int c0, int cn, fmd_fpmatch_status* __restrict__ status) {
+    const int i = blockIdx.x * 64 + threadIdx.x;
+    if (i >= cn) return;
+    fmd_fpmatch_status z{};
+    z.track = -1;
+    status[c0 + i] = z;
+}
+
+// a new catalogue: every station's detector cleared, the catalogue's words masked in place
+__global__ __launch_bounds__(256) void k_fpmatch_loaded(int C, fmd_fpmatch_status* __restrict__ status, uint32_t* __restrict__ cat, int D, unsigned mask) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < C) {
+        status[i].track = -1;
+        status[i].misses = 0u;
+        status[i].flags &= 2u;
+    }
+    if (i < D) cat[i] &= mask;
+}
+
+}  // namespace
+
+struct fmd_fpmatch_s {
+    fmd_fpmatch_config cfg{};
+    FpmatchLayout lay{};
+    FpmDev dev{};
+    int D = 0, T = 0;                              // the catalogue's words and tracks
+    fmd_fpmatch_status* d_status = nullptr;        // [C]
+    uint32_t* d_ring = nullptr;                    // [C][W]: word i lies in slot i mod W
+    uint32_t* d_cat = nullptr;                     // [max_catalogue_words], masked
+    int* d_starts = nullptr;                       // [max_tracks + 1]
+    int* d_qbase = nullptr;                        // [C + 1]
+    uint32_t* d_qwin = nullptr;                    // [max_queries][W]
+    unsigned long long* d_part = nullptr;          // [max_queries][groups]
+    fmd::CallOrder order;
+    std::string err;
+};
+
+template <typename... A>
+static int fpm_fail(fmd_fpmatch h, int code, const char* fmt, A... args) { return fmd::fail(h ? h->err : fmd::fpmatch_global_error(), code, fmt, args...); }
+
+extern "C" {
+
+int fmd_fpmatch_create(const fmd_fpmatch_config* cfg, fmd_fpmatch* out) {
+    if (!cfg || !out) return fpm_fail(nullptr, FMD_ERR_ARG, "null configuration or handle");
+    std::string why;
+    if (fmd::fpmatch_check(cfg, &why) != FMD_OK) return fpm_fail(nullptr, FMD_ERR_ARG, "%s", why.c_str());
+    if (fmd_device_count() <= 0) return fpm_fail(nullptr, FMD_ERR_NO_DEVICE, "no gfx950 device");
+    int dev = cfg->device;
+    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return fpm_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
+    fmd_fpmatch h = new fmd_fpmatch_s();
+    h->cfg = *cfg;
+    h->lay = fmd::fpmatch_layout(cfg);
+    h->dev = FpmDev{cfg->n_channels, cfg->block, cfg->interval, cfg->hold, (unsigned)cfg->max_errs, h->lay.mask};
+    const size_t C = (size_t)cfg->n_channels, W = (size_t)cfg->block, Qm = (size_t)h->lay.max_queries;
+    bool ok = h->order.init(dev);
+    ok = ok && hipMalloc(&h->d_status, sizeof(fmd_fpmatch_status) * C) == hipSuccess;
+    ok = ok && hipMalloc(&h->d_ring, sizeof(uint32_t) * C * W) == hipSuccess;
+    ok = ok && hipMalloc(&h->d_cat, sizeof(uint32_t) * (size_t)cfg->max_catalogue_words) == hipSuccess;
+    ok = ok && hipMalloc(&h->d_starts, sizeof(int) * ((size_t)cfg->max_tracks + 1)) == hipSuccess;
+    ok = ok && hipMalloc(&h->d_qbase, sizeof(int) * (C + 1)) == hipSuccess;
+    ok = ok && hipMalloc(&h->d_qwin, sizeof(uint32_t) * Qm * W) == hipSuccess;
+    ok = ok && hipMalloc(&h->d_part, sizeof(unsigned long long) * Qm * (size_t)h->lay.groups) == hipSuccess;
+    ok = ok && hipMemset(h->d_starts, 0, sizeof(int) * ((size_t)cfg->max_tracks + 1)) == hipSuccess;
+    if (!ok || fmd_fpmatch_reset(h, -1) != FMD_OK) {
+        (void)hipGetLastError();
+        fmd_fpmatch_destroy(h);
+        return fpm_fail(nullptr, FMD_ERR_DEVICE, "device allocation of %lld bytes failed", fmd::fpmatch_layout(cfg).bytes);
+    }
+    *out = h;
+    return FMD_OK;
+}
+
+int fmd_fpmatch_destroy(fmd_fpmatch h) {
+    if (!h) return FMD_ERR_ARG;
+    (void)h->order.quiesce();
+    for (void* p : {(void*)h->d_status, (void*)h->d_ring, (void*)h->d_cat, (void*)h->d_starts, (void*)h->d_qbase, (void*)h->d_qwin, (void*)h->d_part})
+        if (p) (void)hipFree(p);
+    delete h;
+    return FMD_OK;
+}
+
+int fmd_fpmatch_reset(fmd_fpmatch h, int channel) {
+    if (!h) return FMD_ERR_ARG;
+    int c0, cn;
+    if (!fmd::channel_range(channel, h->cfg.n_channels, &c0, &cn)) return fpm_fail(h, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, h->cfg.n_channels);
+    if (!h->order.quiesce()) return fpm_fail(h, FMD_ERR_DEVICE, "synchronise failed");
+    hipLaunchKernelGGL(k_fpmatch_reset, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, nullptr, c0, cn, h->d_status);
+    if (const char* e = fmd::control_end("k_fpmatch_reset launch failed")) return fpm_fail(h, FMD_ERR_DEVICE, "%s", e);
+    return FMD_OK;
+}
+
+int fmd_fpmatch_load(fmd_fpmatch h, const uint32_t* words, const long long* starts, int n_tracks) {
+    if (!h) return FMD_ERR_ARG;
+    std::string why;
+    if (fmd::fpmatch_check_catalogue(&h->cfg, starts, n_tracks, &why) != FMD_OK) return fpm_fail(h, FMD_ERR_ARG, "%s", why.c_str());
+    const long long D = n_tracks > 0 ? starts[n_tracks] : 0;
+    if (D > 0 && !words) return fpm_fail(h, FMD_ERR_ARG, "null words");
+    if (!h->order.quiesce()) return fpm_fail(h, FMD_ERR_DEVICE, "synchronise failed");
+    std::vector<int> st((size_t)n_tracks + 1, 0);
+    for (int t = 0; t <= n_tracks && n_tracks > 0; t++) st[(size_t)t] = (int)starts[t];
+    if (D > 0 && hipMemcpy(h->d_cat, words, sizeof(uint32_t) * (size_t)D, hipMemcpyHostToDevice) != hipSuccess) return fpm_fail(h, FMD_ERR_DEVICE, "copy failed");
+    if (hipMemcpy(h->d_starts, st.data(), sizeof(int) * st.size(), hipMemcpyHostToDevice) != hipSuccess) return fpm_fail(h, FMD_ERR_DEVICE, "copy failed");
+    h->D = (int)D;
+    h->T = n_tracks;
+    const long long most = D > h->cfg.n_channels ? D : h->cfg.n_channels;
+    hipLaunchKernelGGL(k_fpmatch_loaded, dim3((unsigned)((most + 255) / 256)), dim3(256), 0, nullptr, h->cfg.n_channels, h->d_status, h->d_cat, (int)D, h->lay.mask);
+    if (const char* e = fmd::control_end("k_fpmatch_loaded launch failed")) return fpm_fail(h, FMD_ERR_DEVICE, "%s", e);
+    return FMD_OK;
+}
+
+int fmd_fpmatch_process_dev(fmd_fpmatch h, const uint32_t* d_words, long long words_stride, const int* d_nwords, int n, const uint8_t* d_active,
+                            fmd_fpmatch_event* d_events, long long events_stride, int* d_nevents, uint8_t* d_flags, uint8_t* d_ok, void* stream) {
+    if (!h) return FMD_ERR_ARG;
+    if (!d_words || reinterpret_cast<uintptr_t>(d_words) % 4 != 0) return fpm_fail(h, FMD_ERR_ARG, "null words, or words not aligned to 4 bytes");
+    if (!d_events || reinterpret_cast<uintptr_t>(d_events) % 8 != 0) return fpm_fail(h, FMD_ERR_ARG, "null events, or events not aligned to 8 bytes");
+    if (reinterpret_cast<uintptr_t>(d_nwords) % 4 != 0 || reinterpret_cast<uintptr_t>(d_nevents) % 4 != 0) return fpm_fail(h, FMD_ERR_ARG, "counts not aligned to 4 bytes");
+    if (n < 0 || n > words_stride || n > h->cfg.max_words)
+        return fpm_fail(h, FMD_ERR_ARG, "n %d outside [0, words_stride %lld] or above max_words %d", n, words_stride, h->cfg.max_words);
+    const long long need = fmd_fpmatch_max_events(h->cfg.interval, n);
+    if (events_stride < need) return fpm_fail(h, FMD_ERR_ARG, "events_stride %lld below the %lld events the call may write", events_stride, need);
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (const char* e = h->order.begin(s)) return fpm_fail(h, FMD_ERR_DEVICE, "%s", e);
+    const int C = h->cfg.n_channels, W = h->cfg.block;
+    const long long rows_max = (long long)C * need;                          // the host never learns the count: launched for the most
+    const long long tiles = fmd::fpmatch_tiles(h->D, W);
+    const int G = (int)(tiles < h->lay.groups ? tiles : h->lay.groups);      // 0 with an empty catalogue
+    hipLaunchKernelGGL(k_fpmatch_map, dim3(1), dim3(kMapT), 0, s, h->dev, n, d_nwords, d_active, h->d_status, h->d_qbase);
+    if (rows_max > 0 && G > 0) {
+        hipLaunchKernelGGL(k_fpmatch_gather, dim3((unsigned)rows_max), dim3(64), 0, s, h->dev, n, d_nwords, h->d_status, h->d_qbase, h->d_ring, d_words, words_stride,
+                           h->d_qwin);
+        hipLaunchKernelGGL(k_fpmatch_search, dim3((unsigned)((rows_max + kQR - 1) / kQR), (unsigned)G), dim3(kFpmatchThreads), sizeof(uint32_t) * (size_t)h->lay.lds_words, s,
+                           C, W, h->d_qbase, h->d_qwin, h->d_cat, h->D, h->d_starts, h->T, G, h->d_part);
+    }
+    hipLaunchKernelGGL(k_fpmatch_finish, dim3((unsigned)C), dim3(64), 0, s, h->dev, n, d_nwords, d_active, h->d_qbase, h->d_part, G, h->d_starts, h->T, d_words,
+                       words_stride, h->d_status, h->d_ring, d_events, events_stride, d_nevents, d_flags, d_ok);
+    if (hipGetLastError() != hipSuccess) return fpm_fail(h, FMD_ERR_DEVICE, "k_fpmatch launch failed");
+    if (const char* e = h->order.end(s)) return fpm_fail(h, FMD_ERR_DEVICE, "%s", e);
+    return FMD_OK;
+}
+
+int fmd_fpmatch_get_status(fmd_fpmatch h, fmd_fpmatch_status* out) {
+    if (!h || !out) return fpm_fail(h, FMD_ERR_ARG, "null object or output");
+    if (!h->order.quiesce()) return fpm_fail(h, FMD_ERR_DEVICE, "synchronise failed");
+    if (hipMemcpy(out, h->d_status, sizeof(fmd_fpmatch_status) * (size_t)h->cfg.n_channels, hipMemcpyDeviceToHost) != hipSuccess)
+        return fpm_fail(h, FMD_ERR_DEVICE, "copy failed");
+    return FMD_OK;
+}
+
+int fmd_fpmatch_status_dev(fmd_fpmatch h, const fmd_fpmatch_status** d_status) {
+    if (!h || !d_status) return fpm_fail(h, FMD_ERR_ARG, "null object or output");
+    *d_status = h->d_status;
+    return FMD_OK;
+}
+
+const char* fmd_fpmatch_last_error(fmd_fpmatch h) { return h ? h->err.c_str() : fmd::fpmatch_global_error().c_str(); }
+
+}  // extern "C"

@@ -1871,6 +1871,133 @@ int fmd_fprint_get_status(fmd_fprint h, fmd_fprint_status* out);
 int fmd_fprint_status_dev(fmd_fprint h, const fmd_fprint_status** d_status);
 const char* fmd_fprint_last_error(fmd_fprint h);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Fingerprint matcher (NOT part of the reference): which recording is on a station.  The object holds a catalogue of reference
+ * fingerprints on the device, T tracks stored as runs of uint32 words, and per station a ring of the station's newest W words.  It
+ * takes the fingerprinter's device outputs as they are (the d_out rows and d_nprints), and whenever a station's word count crosses a
+ * multiple of the search interval it searches the WHOLE catalogue for the station's newest W words, by brute force: exact integer
+ * arithmetic (XOR, population count, minimum), so every result is the same in every call split and tiling.  The rules, restated in
+ * numpy by tests/fpmatch_ref.py.  W = block, I = interval, mask = 0xffffffff << (32 - n_bits):
+ *   catalogue   D = starts[T] words; track t is the words starts[t] ... starts[t + 1] - 1 and is at least W words long.  A position p is
+ *               valid iff the W words p ... p + W - 1 lie inside one track.  fmd_fpmatch_load replaces the whole catalogue from host
+ *               memory, waits for the object's earlier work, clears every station's detector (track = -1, misses = 0, bit 0 of
+ *               flags) and keeps every station's ring and counters; n_tracks = 0 empties the catalogue.  FMD_ERR_ARG, and nothing
+ *               changed, for a track shorter than W, starts[0] != 0, T above max_tracks, D above max_catalogue_words, a starts array
+ *               that does not ascend or null words with D > 0.
+ *   push        a call hands station c  k = d_nwords[c] clamped into [0, n]  new words (a clamp adds 1 to `clamped`), k = n where
+ *               d_nwords is NULL: d_words[c * words_stride + 0 ... k - 1], oldest first, the layout the fingerprinter writes.  The
+ *               station's word index counts absolutely, in 64 bits, from its reset.
+ *   query       one for every e with e = 0 (mod I), e >= W and words_before < e <= words_before + k, in ascending e; its window q is the
+ *               station's words e - W ... e - 1.  For every valid p, errs(p) = sum_j popcount((q[j] ^ cat[p + j]) & mask); the result is
+ *               the smallest errs, on a tie the smallest p, reported as track, offset = p - starts[track] and errs.  With an empty
+ *               catalogue track = -1, offset = 0, errs = 0xffffffff.
+ *   detector    per query, comparisons only.  hit = track >= 0 and errs <= max_errs.  On a hit: where the record's track differs, track
+ *               and since = e are set; offset is set, misses = 0.  On a miss with the record's track >= 0: misses + 1, and at
+ *               misses == hold the station is released: track = -1, misses = 0.
+ *   event       24 bytes, 8-byte aligned, one per query: end (e) u64 at byte 0, track i32 at 8, offset i32 at 12, errs u32 at 16,
+ *               flags u32 at 20 (bit 0 = hit).  A call writes a station's events, oldest first, from d_events + c * events_stride
+ *               (in events) and their number to d_nevents[c]: at most fmd_fpmatch_max_events(interval, n); the slots behind them are
+ *               left alone.
+ *   bytes       d_flags[c]: bit 0 = identified (the record's track >= 0 after the call's last query), bit 1 = the station's last
+ *               query ever was a hit; d_ok[c] = bit 0.  Written for every active station on every call, from the record, even when no
+ *               query fired.  The record's flags hold the same two bits.
+ *   inactive    a station whose d_active byte is 0 is skipped whole: ring, record, events, count and bytes are left as they are.
+ * Nothing depends on how a station's words are split into calls, on streams, on the batch, on the station's row or on any tile size.
+ * Ordinary vector stores, no global atomics, no workgroup waits on another.
+ *   memory      the catalogue (4 bytes a word), a ring of W words a station, the call's query windows (W words a query) and the
+ *               partial minima of the search (8 bytes a query and column group, at most 256 groups): fmd_fpmatch_state_bytes reports
+ *               the whole for max_words, max_catalogue_words and max_tracks.
+ * Not built: the paper's hash-index prefilter (this exact search is the baseline one would be checked against), soft bits,
+ * station-against-station comparison, catalogues loaded from device memory or appended to, several catalogues, per-station
+ * configurations.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_fpmatch_s* fmd_fpmatch;
+typedef struct {
+    int       n_channels;          /* C: station rows */
+    int       n_bits;              /* 1 ... 32: the top n_bits of a word count */
+    int       block;               /* W: words of a query, a multiple of 16 in 16 ... 1024 */
+    int       interval;            /* I: words between searches, 1 ... 1024 */
+    int       max_errs;            /* a query hits at errs <= max_errs: 0 ... W * n_bits */
+    int       hold;                /* misses in a row that release a station, >= 1 */
+    int       max_words;           /* largest n of a process call, in (0, 65536] */
+    int       max_tracks;          /* in [1, 2^20] */
+    long long max_catalogue_words; /* in [W, 2^28] */
+    int       device;              /* HIP device ordinal, -1 = current */
+} fmd_fpmatch_config;
+/* what the kernels are built on, from the constants they use */
+typedef struct {
+    unsigned  mask;                /* 0xffffffff << (32 - n_bits) */
+    int       tile;                /* catalogue positions of a column tile of the search */
+    int       query_block;         /* queries a workgroup of the search holds in registers */
+    int       groups;              /* column groups of the search at max_catalogue_words: the partial minima a query has, at most 256 */
+    int       lds_bytes;           /* the search's LDS image: (tile + W - 1) words */
+    long long max_events;          /* fmd_fpmatch_max_events(interval, max_words) */
+    long long max_queries;         /* n_channels * max_events */
+} fmd_fpmatch_design_t;
+/* one per query, 24 bytes */
+typedef struct {
+    unsigned long long end;        /* e: the station's word count at the window's end */
+    int                track;      /* -1 with an empty catalogue */
+    int                offset;     /* p - starts[track] */
+    unsigned           errs;
+    unsigned           flags;      /* bit 0 = hit */
+} fmd_fpmatch_event;
+/* one per station, 64 bytes: words at byte 0, queries 8, hits 16, clamped 24, since 32, track 40, offset 44, errs 48, misses 52,
+ * fill 56, flags 60.  After create and reset: all 0 but track = -1 */
+typedef struct {
+    unsigned long long words;      /* words taken since reset */
+    unsigned long long queries;    /* searches since reset */
+    unsigned long long hits;       /* of them hits */
+    unsigned long long clamped;    /* calls whose d_nwords entry lay outside [0, n] */
+    unsigned long long since;      /* e of the query that identified the current track */
+    int                track;      /* the identified track, -1 = none */
+    int                offset;     /* of the last hit */
+    unsigned           errs;       /* the last query's */
+    unsigned           misses;     /* misses in a row while identified */
+    unsigned           fill;       /* min(words, W) */
+    unsigned           flags;      /* bit 0 = identified, bit 1 = the last query was a hit */
+} fmd_fpmatch_status;
+
+/* host-only (no GPU needed) */
+/* one station, n_bits 32, block 256 (the paper's), interval 64, max_errs (35 * 256 * 32) / 100, hold 3, max_words 64,
+ * max_tracks 4096, max_catalogue_words 2^22, the current device */
+int fmd_fpmatch_default_config(fmd_fpmatch_config* cfg);
+/* (n + interval - 1) / interval: the most events a call of n words writes for a station.  FMD_ERR_ARG for interval outside
+ * 1 ... 1024 or n outside [0, 65536] */
+long long fmd_fpmatch_max_events(int interval, long long n);
+/* (ber_percent * block * n_bits) / 100 in integers: the threshold for a bit error rate in per cent.  FMD_ERR_ARG for ber_percent
+ * outside 0 ... 100, block no multiple of 16 in 16 ... 1024 or n_bits outside 1 ... 32 */
+long long fmd_fpmatch_max_errs(int ber_percent, int block, int n_bits);
+/* FMD_OK for a valid configuration and then *out (may be NULL) written; FMD_ERR_ARG otherwise and nothing written */
+int fmd_fpmatch_design(const fmd_fpmatch_config* cfg, fmd_fpmatch_design_t* out);
+/* FMD_OK where fmd_fpmatch_load would take starts [n_tracks + 1] (NULL allowed for n_tracks = 0) under cfg, FMD_ERR_ARG otherwise */
+int fmd_fpmatch_check_catalogue(const fmd_fpmatch_config* cfg, const long long* starts, int n_tracks);
+/* the bytes of device memory an object of cfg holds; FMD_ERR_ARG for an invalid configuration */
+long long fmd_fpmatch_state_bytes(const fmd_fpmatch_config* cfg);
+
+/* FMD_ERR_DEVICE where the device memory (fmd_fpmatch_state_bytes) cannot be had */
+int fmd_fpmatch_create(const fmd_fpmatch_config* cfg, fmd_fpmatch* out);
+int fmd_fpmatch_destroy(fmd_fpmatch h);
+/* station `channel` (-1 = every station) as after create: ring emptied, counters 0, track -1; the catalogue stays.  Waits for the
+ * object's earlier work */
+int fmd_fpmatch_reset(fmd_fpmatch h, int channel);
+/* replaces the catalogue: words [starts[n_tracks]] and starts [n_tracks + 1] in host memory (see "catalogue" above) */
+int fmd_fpmatch_load(fmd_fpmatch h, const uint32_t* words, const long long* starts, int n_tracks);
+/* takes up to n words of every station.  d_words [C][words_stride] uint32 on the device, 4-byte aligned; d_nwords: [C] int32 on the
+ * device or NULL; d_active: [C] uint8 on the device or NULL = all; d_events: caller-owned fmd_fpmatch_event rows on the device, 8-byte
+ * aligned, events_stride in events, at least fmd_fpmatch_max_events(interval, n); d_nevents [C] int32, d_flags [C] uint8 and d_ok [C]
+ * uint8 on the device, each may be NULL.  n = 0 is valid.  n < 0, n > max_words, n > words_stride, a short events_stride, or a null or
+ * misaligned d_words or d_events return FMD_ERR_ARG and change nothing.  Asynchronous on `stream`; consecutive calls may use different
+ * streams (the library orders them). */
+int fmd_fpmatch_process_dev(fmd_fpmatch h, const uint32_t* d_words, long long words_stride, const int* d_nwords, int n, const uint8_t* d_active,
+                            fmd_fpmatch_event* d_events, long long events_stride, int* d_nevents, uint8_t* d_flags, uint8_t* d_ok, void* stream);
+/* out [C]; synchronises with the object's work */
+int fmd_fpmatch_get_status(fmd_fpmatch h, fmd_fpmatch_status* out);
+/* the device's own [C] records, for a consumer on the device: ordered behind the object's work on the stream of its last call, valid
+ * until the next call */
+int fmd_fpmatch_status_dev(fmd_fpmatch h, const fmd_fpmatch_status** d_status);
+const char* fmd_fpmatch_last_error(fmd_fpmatch h);
+
 #ifdef __cplusplus
 }
 #endif
