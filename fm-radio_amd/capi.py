@@ -307,6 +307,21 @@ FPMATCH_EVENT_DTYPE = np.dtype([("end", "<u8"), ("track", "<i4"), ("offset", "<i
 assert FPMATCH_STATUS_DTYPE.itemsize == 64 and FPMATCH_EVENT_DTYPE.itemsize == 24
 
 
+class FpmatchIndexConfig(C.Structure):
+    """include/fmdemod.h fmd_fpmatch_index_config"""
+    _fields_ = [("max_bucket", C.c_int), ("follow", C.c_int)]
+
+
+class FpmatchIndexDesign(C.Structure):
+    """include/fmdemod.h fmd_fpmatch_index_design_t"""
+    _fields_ = [("dir_bits", C.c_int), ("chunk", C.c_int), ("chunk_words", C.c_int), ("table", C.c_int), ("dir_entries", C.c_longlong), ("index_bytes", C.c_longlong)]
+
+
+# include/fmdemod.h fmd_fpmatch_index_status (32 bytes)
+FPMATCH_INDEX_STATUS_DTYPE = np.dtype([("candidates", "<u8"), ("skipped", "<u8"), ("followed", "<u8"), ("empty", "<u8")])
+assert FPMATCH_INDEX_STATUS_DTYPE.itemsize == 32
+
+
 class SameConfig(C.Structure):
     _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
 
@@ -602,6 +617,13 @@ def load_library():
     L.fmd_fpmatch_state_bytes.restype = C.c_longlong
     L.fmd_fpmatch_create.argtypes = [C.POINTER(FpmatchConfig), C.POINTER(C.c_void_p)]
     L.fmd_fpmatch_load.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    L.fmd_fpmatch_index_default_config.argtypes = [C.POINTER(FpmatchIndexConfig)]
+    L.fmd_fpmatch_index_design.argtypes = [C.POINTER(FpmatchConfig), C.POINTER(FpmatchIndexConfig), C.POINTER(FpmatchIndexDesign)]
+    L.fmd_fpmatch_index_state_bytes.argtypes = [C.POINTER(FpmatchConfig), C.POINTER(FpmatchIndexConfig)]
+    L.fmd_fpmatch_index_state_bytes.restype = C.c_longlong
+    L.fmd_fpmatch_index_build.argtypes = [C.POINTER(FpmatchConfig), C.POINTER(FpmatchIndexConfig), C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.fmd_fpmatch_create_ex.argtypes = [C.POINTER(FpmatchConfig), C.POINTER(FpmatchIndexConfig), C.POINTER(C.c_void_p)]
+    L.fmd_fpmatch_get_index_status.argtypes = [C.c_void_p, C.c_void_p]
     L.fmd_fpmatch_process_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]
     L.fmd_same_default_params.argtypes = [C.POINTER(SameParams)]
@@ -2632,6 +2654,53 @@ def fpmatch_check_catalogue(cfg: FpmatchConfig, starts, n_tracks: int | None = N
     return L.fmd_fpmatch_check_catalogue(C.byref(cfg), st.ctypes.data_as(C.c_void_p) if st.size else None, T) == FMD_OK
 
 
+def fpmatch_index_default_config(**fields) -> FpmatchIndexConfig:
+    """fmd_fpmatch_index_default_config (host only): max_bucket 8, follow 2; `fields` then replace the named fields"""
+    L = load_library()
+    idx = FpmatchIndexConfig()
+    rc = L.fmd_fpmatch_index_default_config(C.byref(idx))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_fpmatch", rc)
+    for k, v in fields.items():
+        if k not in dict(FpmatchIndexConfig._fields_):
+            raise TypeError(f"FpmatchIndexConfig has no field {k}")
+        setattr(idx, k, v)
+    return idx
+
+
+def fpmatch_index_design(cfg: FpmatchConfig, idx: FpmatchIndexConfig) -> FpmatchIndexDesign:
+    """fmd_fpmatch_index_design (host only): the directory's bits and entries, the index bytes and the probe kernel's chunk and set"""
+    L = load_library()
+    d = FpmatchIndexDesign()
+    rc = L.fmd_fpmatch_index_design(C.byref(cfg), C.byref(idx), C.byref(d))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_fpmatch", rc)
+    return d
+
+
+def fpmatch_index_state_bytes(cfg: FpmatchConfig, idx: FpmatchIndexConfig) -> int:
+    """fmd_fpmatch_index_state_bytes (host only): the device memory an indexed object of cfg and idx holds"""
+    L = load_library()
+    rc = L.fmd_fpmatch_index_state_bytes(C.byref(cfg), C.byref(idx))
+    if rc < 0:
+        raise _global_error(L, "fmd_fpmatch", int(rc))
+    return int(rc)
+
+
+def fpmatch_index_build(cfg: FpmatchConfig, idx: FpmatchIndexConfig, words):
+    """fmd_fpmatch_index_build (host only): the index load() builds for a catalogue of `words`, as (keys uint32 [D], pos int32 [D], dir
+    int32 [dir_entries])"""
+    L = load_library()
+    words = _fpmatch_words(words)
+    d = fpmatch_index_design(cfg, idx)
+    keys, pos, dirs = np.zeros(words.size, np.uint32), np.zeros(words.size, np.int32), np.zeros(d.dir_entries, np.int32)
+    ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a.size else None
+    rc = L.fmd_fpmatch_index_build(C.byref(cfg), C.byref(idx), ptr(words), words.size, ptr(keys), ptr(pos), ptr(dirs))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_fpmatch", rc)
+    return keys, pos, dirs
+
+
 def _fpmatch_words(t) -> np.ndarray:
     """a run of fingerprint words as uint32: int32 arrays (what Fingerprinter's tensors give on the host) keep their bit patterns"""
     t = np.ascontiguousarray(t).reshape(-1)
@@ -2644,19 +2713,34 @@ class FingerprintMatcher(_Monitor):
     and, whenever a station's word count crosses a multiple of `interval`, searches the whole catalogue for the station's newest words.
     process() returns the events ([C, max_events, 3] int64 tensor: view a station's row with events_of()), their [C] int32 counts and the
     [C] uint8 flags and ok bytes, all on the device.  status() returns FPMATCH_STATUS_DTYPE records.  **config: the fields of FpmatchConfig
-    over fpmatch_default_config()."""
+    over fpmatch_default_config().  index: None searches by brute force; True or a dict of FpmatchIndexConfig's fields (max_bucket,
+    follow) over fpmatch_index_default_config() makes an indexed object (fmd_fpmatch_create_ex), which looks the query's words up in a
+    sorted index of the catalogue and counts errors only at the positions they propose; index_status() then returns its
+    FPMATCH_INDEX_STATUS_DTYPE records."""
     _prefix, _attr, _status_dtype = "fmd_fpmatch", "g", FPMATCH_STATUS_DTYPE
 
-    def __init__(self, n_channels: int, **config):
+    def __init__(self, n_channels: int, index=None, **config):
         self.L = load_library()
         self.g = None
         self.cfg = fpmatch_default_config(n_channels=int(n_channels), **config)
-        self._create("create", C.byref(self.cfg))
+        self.index = None if index is None or index is False else fpmatch_index_default_config(**({} if index is True else dict(index)))
+        if self.index is None:
+            self._create("create", C.byref(self.cfg))
+        else:
+            self._create("create_ex", C.byref(self.cfg), C.byref(self.index))
+            self.index_design = fpmatch_index_design(self.cfg, self.index)
         self.n_channels = int(n_channels)
         self.block, self.interval, self.n_bits, self.max_errs, self.hold = self.cfg.block, self.cfg.interval, self.cfg.n_bits, self.cfg.max_errs, self.cfg.hold
         self.design = fpmatch_design(self.cfg)
-        self.state_bytes = fpmatch_state_bytes(self.cfg)
+        self.state_bytes = fpmatch_state_bytes(self.cfg) if self.index is None else fpmatch_index_state_bytes(self.cfg, self.index)
         self.n_tracks, self.catalogue_words = 0, 0
+
+    def index_status(self) -> np.ndarray:
+        """fmd_fpmatch_get_index_status: [C] FPMATCH_INDEX_STATUS_DTYPE records; waits for the object's work.  FMD_ERR_STATE on an object
+        without an index"""
+        out = np.zeros(self.n_channels, FPMATCH_INDEX_STATUS_DTYPE)
+        self._check(self.L.fmd_fpmatch_get_index_status(self.g, out.ctypes.data_as(C.c_void_p)))
+        return out
 
     def reset_peaks(self, channel: int = -1):
         raise AttributeError("the matcher holds no peaks")

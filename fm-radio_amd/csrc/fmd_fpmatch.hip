@@ -16,13 +16,30 @@
 //                     partial minimum.
 //   k_fpmatch_finish  a wavefront a station: per query the minimum over the groups' partials, the track from the starts table, the
 //                     detector, the event; then the ring's newest words, the record, the count and the bytes.
-// No atomics, no register spills (scratch 0), no workgroup waits on another, ordinary vector stores only.
+// An indexed object (fmd_fpmatch_create_ex) keeps map and gather and puts two kernels of its own behind them:
+//   k_fpmatch_probe       a workgroup a query.  Lane <-> window word j: the directory slice of the word's key, a binary search for the
+//                         key's run in the sorted keys, runs longer than K skipped.  A run's positions p' propose p = p' - j; a proposal
+//                         inside [0, D - W] that the workgroup's LDS set has not seen goes into the LDS list, so a position most of the W
+//                         look-ups agree on is counted once.  The window is walked in chunks of chunk_words words so that a chunk's
+//                         runs fit the list.  Then a wavefront (16 lanes where W < 64) a listed position: track validity, and the W
+//                         catalogue words at p read by consecutive lanes against the window in LDS, XOR, population count, a shuffle
+//                         sum.  The packed minimum as in the search; one partial a row, and the row's (candidates, skipped) counts.
+//   k_fpmatch_finish_idx  k_fpmatch_finish for the indexed object: walks a station's queries in order, and before a query's detector
+//                         step counts the follow rule's 2 d + 1 positions around the expected one itself, because they depend on the
+//                         detector state the query before left; adds the row's counts to the station's index record.
+// No global atomics (the probe's set and list use LDS atomics inside one workgroup), no register spills (scratch 0), no workgroup waits
+// on another, ordinary vector stores only.
 //
 // Bounds: k_fpmatch_gather reads ring slots taken mod W, new words below the station's k <= n <= words_stride, and writes window rows
 // below qbase[C] <= C * max_events(I, n) <= max_queries.  k_fpmatch_search reads catalogue words below D (zero behind it), LDS words below
 // kFpmatchTile - 1 + W - 1 < lds_words, starts entries 0 ... T, window rows below qbase[C] (a row past the last repeats it) and writes
 // partials at row * G + group, group < G <= groups.  k_fpmatch_finish writes events below the station's count <= max_events(I, n) <=
-// events_stride and ring slots mod W.
+// events_stride and ring slots mod W.  k_fpmatch_probe reads window row r < qbase[C], directory entries b and b + 1 with b = key >> (32 -
+// dir_bits) < 2^dir_bits (the directory holds 2^dir_bits + 1), keys and positions at dir[b] ... dir[b + 1] - 1 < D, s_win below W <= 1024;
+// a chunk lists at most chunk_words * K <= kFpmIndexChunk positions (chunk_words = min(256, kFpmIndexChunk / K): W = 1024 at K = 64 is 16
+// chunks of 64 words), each in [0, D - W], so the catalogue words p ... p + W - 1 lie below D; the set holds at most 3/4 of its
+// kFpmIndexTable slots (it is emptied before a chunk that could take it above that), so a probe sequence ends; starts entries 0 ... T.
+// k_fpmatch_finish_idx counts only positions in [0, D - W] whose W words lie inside one track, from window row row0 + i < qbase[C].
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
@@ -31,6 +48,7 @@
 #include <vector>
 
 #include "fmd_fpmatch_design.h"
+#include "fmd_fpmatch_index.h"
 #include "fmd_side.h"
 #include "fmdemod.h"
 
@@ -38,6 +56,9 @@ using fmd::FpmatchLayout;
 using fmd::kFpmatchQueries;
 using fmd::kFpmatchThreads;
 using fmd::kFpmatchTile;
+using fmd::kFpmIndexChunk;
+using fmd::kFpmIndexTable;
+using fmd::kFpmIndexThreads;
 
 namespace {
 
@@ -50,12 +71,22 @@ static_assert(kFpmatchTile % kFpmatchThreads == 0, "a tile is whole passes of a 
 
 static_assert(sizeof(fmd_fpmatch_status) == 64 && offsetof(fmd_fpmatch_status, since) == 32 && offsetof(fmd_fpmatch_status, track) == 40 &&
               offsetof(fmd_fpmatch_status, errs) == 48 && offsetof(fmd_fpmatch_status, flags) == 60, "fmd_fpmatch_status layout");
+static_assert(sizeof(fmd_fpmatch_index_status) == 32 && offsetof(fmd_fpmatch_index_status, empty) == 24, "fmd_fpmatch_index_status layout");
+static_assert(kFpmIndexThreads == kFpmatchThreads && (kFpmIndexTable & (kFpmIndexTable - 1)) == 0, "the probe's workgroup and set");
 static_assert(sizeof(fmd_fpmatch_event) == 24 && offsetof(fmd_fpmatch_event, track) == 8 && offsetof(fmd_fpmatch_event, errs) == 16, "fmd_fpmatch_event layout");
 
 // what the kernels read of the configuration
 struct FpmDev {
     int C, W, I, hold;
     unsigned max_errs, mask;
+};
+
+// what k_fpmatch_probe and k_fpmatch_finish_idx read of the index: keys [D] ascending, pos [D], dir [2^dir_bits + 1]
+struct FpmIdxDev {
+    const uint32_t* keys;
+    const int* pos;
+    const int* dir;
+    int dir_bits, K, chunk_words, follow;
 };
 
 // ---- the pieces a later object (station against station) can reuse: the take, the query schedule, the ring and the error count
@@ -295,6 +326,206 @@ __global__ __launch_bounds__(64) void k_fpmatch_finish(FpmDev g, int n, const in
     }
 }
 
+// whether position p, inside [0, D - W], has its W words inside one track
+__device__ __forceinline__ bool fpm_valid(const int* __restrict__ starts, int T, int p, int W) { return p + W <= starts[fpm_track(starts, T, p) + 1]; }
+
+// the sum over groups of L consecutive lanes (L = 16 or 64), in every lane of the group
+template <int L>
+__device__ __forceinline__ unsigned fpm_group_sum(unsigned v) {
+#pragma unroll
+    for (int d = L / 2; d >= 1; d >>= 1) v += (unsigned)__shfl_xor((int)v, d, 64);
+    return v;
+}
+
+// the listed positions s_list[0 ... n - 1] against the window: L lanes a position, 64 / L positions a wavefront at once
+template <int L>
+__device__ __forceinline__ unsigned long long fpm_count_list(const int* s_list, int n, const uint32_t* s_win, int W, const uint32_t* __restrict__ cat,
+                                                             const int* __restrict__ starts, int T, unsigned long long best) {
+    constexpr int per = 64 / L;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, g = lane / L, l = lane % L;
+    for (int i0 = 0; i0 < n; i0 += kWaves * per) {                           // (uniform bounds: every lane reaches the shuffles)
+        const int i = i0 + wave * per + g;
+        const int p = i < n ? s_list[i] : 0;
+        const bool valid = i < n && fpm_valid(starts, T, p, W);
+        unsigned e = 0u;
+        if (valid)
+            for (int j = l; j < W; j += L) e = fpm_errs(e, s_win[j], cat[(size_t)p + (size_t)j]);
+        e = fpm_group_sum<L>(e);
+        if (valid) best = fpm_min(best, ((unsigned long long)e << 32) | (unsigned)p);
+    }
+    return best;
+}
+
+// part [rows]: the row's minimum over its look-ups' valid positions; rowstat [rows]: (candidates, skipped)
+__global__ __launch_bounds__(kFpmIndexThreads) void k_fpmatch_probe(int C, int W, const int* __restrict__ qbase, const uint32_t* __restrict__ qwin,
+                                                                   const uint32_t* __restrict__ cat, int D, const int* __restrict__ starts, int T, FpmIdxDev x,
+                                                                   unsigned long long* __restrict__ part, uint2* __restrict__ rowstat) {
+    __shared__ uint32_t s_win[1024];                                         // the window (W <= 1024)
+    __shared__ int s_list[kFpmIndexChunk];                                   // the chunk's positions, each once
+    __shared__ int s_tab[kFpmIndexTable];                                    // the set of the positions listed so far, open addressing, -1 = free
+    __shared__ int s_n;                                                      // positions in the list
+    __shared__ unsigned long long s_red[kWaves];
+    __shared__ unsigned s_cnt[kWaves][2];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int r = blockIdx.x;
+    if (r >= qbase[C]) return;                                               // surplus workgroups leave at once (uniform)
+    for (int j = tid; j < W; j += kFpmIndexThreads) s_win[j] = qwin[(size_t)r * (size_t)W + j];
+    for (int i = tid; i < kFpmIndexTable; i += kFpmIndexThreads) s_tab[i] = -1;
+    if (tid == 0) s_n = 0;
+    int fill = 0;                                                            // the set's entries (uniform)
+    unsigned long long best = kNoKey;
+    unsigned cand = 0u, skip = 0u;
+    __syncthreads();
+    for (int j0 = 0; j0 < W; j0 += x.chunk_words) {
+        if (fill + x.chunk_words * x.K > kFpmIndexTable / 4 * 3) {           // the set could pass 3/4: emptied (repeats of earlier chunks are then counted again)
+            for (int i = tid; i < kFpmIndexTable; i += kFpmIndexThreads) s_tab[i] = -1;
+            fill = 0;
+            __syncthreads();
+        }
+        const int j = j0 + tid;
+        if (tid < x.chunk_words && j < W) {
+            const uint32_t k = s_win[j];
+            const unsigned b = k >> (32 - x.dir_bits);
+            const int hi = x.dir[b + 1];
+            int a = x.dir[b], z = hi;
+            while (a < z) {                                                  // the first key >= k of the slice
+                const int mid = (a + z) >> 1;
+                if (x.keys[mid] < k) a = mid + 1; else z = mid;
+            }
+            const int first = a;
+            z = min(hi, first + x.K + 1);
+            while (a < z) {                                                  // the first key > k among the K + 1 behind it
+                const int mid = (a + z) >> 1;
+                if (x.keys[mid] <= k) a = mid + 1; else z = mid;
+            }
+            const int run = a - first;
+            if (run > x.K) {
+                skip += 1u;
+            } else {
+                cand += (unsigned)run;
+                for (int i = first; i < first + run; i++) {
+                    const int p = x.pos[i] - j;
+                    if (p < 0 || p > D - W) continue;
+                    unsigned h = ((unsigned)p * 2654435761u) >> 19;          // 13 bits
+                    static_assert(kFpmIndexTable == 1 << 13, "the hash's width");
+                    for (;;) {
+                        const int old = atomicCAS(&s_tab[h], -1, p);
+                        if (old == -1) { s_list[atomicAdd(&s_n, 1)] = p; break; }
+                        if (old == p) break;
+                        h = (h + 1u) & (unsigned)(kFpmIndexTable - 1);
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        const int n = s_n;
+        best = W >= 64 ? fpm_count_list<64>(s_list, n, s_win, W, cat, starts, T, best) : fpm_count_list<16>(s_list, n, s_win, W, cat, starts, T, best);
+        fill += n;
+        __syncthreads();                                                     // the list is read
+        if (tid == 0) s_n = 0;
+        __syncthreads();
+    }
+    best = fpm_wave_min(best);
+    cand = fpm_group_sum<64>(cand);
+    skip = fpm_group_sum<64>(skip);
+    if (lane == 0) { s_red[wave] = best; s_cnt[wave][0] = cand; s_cnt[wave][1] = skip; }
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long m = s_red[0];
+        uint2 cs = make_uint2(s_cnt[0][0], s_cnt[0][1]);
+#pragma unroll
+        for (int w = 1; w < kWaves; w++) { m = fpm_min(m, s_red[w]); cs.x += s_cnt[w][0]; cs.y += s_cnt[w][1]; }
+        part[r] = m;
+        rowstat[r] = cs;
+    }
+}
+
+// k_fpmatch_finish for the indexed object: a wavefront a station; probed = 0 with an empty catalogue (no rows were probed)
+__global__ __launch_bounds__(64) void k_fpmatch_finish_idx(FpmDev g, int n, const int* __restrict__ nwords, const uint8_t* __restrict__ active, const int* __restrict__ qbase,
+                                                          const unsigned long long* __restrict__ part, const uint2* __restrict__ rowstat, int probed,
+                                                          const uint32_t* __restrict__ qwin, const uint32_t* __restrict__ cat, int D, int follow,
+                                                          const int* __restrict__ starts, int T, const uint32_t* __restrict__ words, long long words_stride,
+                                                          fmd_fpmatch_status* __restrict__ status, fmd_fpmatch_index_status* __restrict__ istatus,
+                                                          uint32_t* __restrict__ ring_all, fmd_fpmatch_event* __restrict__ events, long long events_stride,
+                                                          int* __restrict__ nevents, uint8_t* __restrict__ flags, uint8_t* __restrict__ ok) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (active && active[c] == 0) return;
+    fmd_fpmatch_status st = status[c];
+    fmd_fpmatch_index_status ix = istatus[c];
+    const unsigned long long before = st.words;
+    bool clamped;
+    const int k = fpm_take(nwords, c, n, &clamped);
+    unsigned long long e0;
+    const int cnt = fpm_queries(before, k, g.W, g.I, &e0);
+    const int row0 = qbase[c];
+    // every lane walks the detector alike; lane 0 stores
+    for (int i = 0; i < cnt; i++) {
+        unsigned long long key = kNoKey;
+        if (probed) {
+            key = part[row0 + i];
+            const uint2 cs = rowstat[row0 + i];
+            ix.candidates += cs.x;
+            ix.skipped += cs.y;
+        }
+        if (follow > 0 && st.track >= 0) {                                   // (identified: the catalogue is not empty, since a load clears the track)
+            ix.followed += 1ull;
+            const long long p_exp = (long long)starts[st.track] + (long long)st.offset + (long long)g.I * ((long long)st.misses + 1ll);
+            const uint32_t* q = qwin + (size_t)(row0 + i) * (size_t)g.W;
+            for (long long p = p_exp - follow; p <= p_exp + follow; p++) {   // (uniform: every lane reaches the shuffles)
+                if (p < 0 || p > (long long)(D - g.W) || !fpm_valid(starts, T, (int)p, g.W)) continue;
+                unsigned e = 0u;
+                for (int j = lane; j < g.W; j += 64) e = fpm_errs(e, q[j], cat[(size_t)p + (size_t)j]);
+                e = fpm_group_sum<64>(e);
+                key = fpm_min(key, ((unsigned long long)e << 32) | (unsigned)p);
+            }
+        }
+        const unsigned long long e = e0 + (unsigned long long)i * (unsigned long long)g.I;
+        int track = -1, offset = 0;
+        unsigned errs = 0xffffffffu;
+        if (key != kNoKey) {
+            const int p = (int)(unsigned)key;
+            errs = (unsigned)(key >> 32);
+            track = fpm_track(starts, T, p);
+            offset = p - starts[track];
+        } else {
+            ix.empty += 1ull;
+        }
+        const bool hit = track >= 0 && errs <= g.max_errs;
+        st.queries += 1;
+        st.errs = errs;
+        if (hit) {
+            st.hits += 1;
+            if (st.track != track) { st.track = track; st.since = e; }
+            st.offset = offset;
+            st.misses = 0;
+        } else if (st.track >= 0) {
+            st.misses += 1;
+            if (st.misses == (unsigned)g.hold) { st.track = -1; st.misses = 0; }
+        }
+        st.flags = hit ? 2u : 0u;
+        if (lane == 0) {
+            fmd_fpmatch_event ev;
+            ev.end = e; ev.track = track; ev.offset = offset; ev.errs = errs; ev.flags = hit ? 1u : 0u;
+            events[(size_t)c * (size_t)events_stride + (size_t)i] = ev;
+        }
+    }
+    // the ring's newest words: of the k new ones the last min(k, W)  (k_fpmatch_gather and this kernel's follow step, the ring's and the windows' readers, are done)
+    uint32_t* ring = ring_all + (size_t)c * (size_t)g.W;
+    for (int j = (k > g.W ? k - g.W : 0) + lane; j < k; j += 64)
+        ring[(int)((before + (unsigned long long)j) % (unsigned long long)g.W)] = words[(size_t)c * (size_t)words_stride + (size_t)j];
+    if (lane == 0) {
+        st.words = before + (unsigned long long)k;
+        st.clamped += clamped ? 1ull : 0ull;
+        st.fill = st.words < (unsigned long long)g.W ? (unsigned)st.words : (unsigned)g.W;
+        st.flags = (st.flags & 2u) | (st.track >= 0 ? 1u : 0u);
+        status[c] = st;
+        istatus[c] = ix;
+        if (nevents) nevents[c] = cnt;
+        if (flags) flags[c] = (uint8_t)st.flags;
+        if (ok) ok[c] = (uint8_t)(st.flags & 1u);
+    }
+}
+
 // stations c0 ... as after create
 __global__ __launch_bounds__(64) void k_fpmatch_reset(int c0, int cn, fmd_fpmatch_status* __restrict__ status) {
     const int i = blockIdx.x * 64 + threadIdx.x;
@@ -328,7 +559,16 @@ struct fmd_fpmatch_s {
     int* d_starts = nullptr;                       // [max_tracks + 1]
     int* d_qbase = nullptr;                        // [C + 1]
     uint32_t* d_qwin = nullptr;                    // [max_queries][W]
-    unsigned long long* d_part = nullptr;          // [max_queries][groups]
+    unsigned long long* d_part = nullptr;          // [max_queries][groups]; indexed: [max_queries]
+    // an indexed object (fmd_fpmatch_create_ex) only
+    bool indexed = false;
+    fmd_fpmatch_index_config icfg{};
+    fmd::FpmIndexLayout ilay{};
+    uint32_t* d_keys = nullptr;                    // [max_catalogue_words]: the masked words ascending
+    int* d_pos = nullptr;                          // [max_catalogue_words]: their positions
+    int* d_dir = nullptr;                          // [2^dir_bits + 1]
+    uint2* d_rowstat = nullptr;                    // [max_queries]: (candidates, skipped) of a row
+    fmd_fpmatch_index_status* d_istatus = nullptr; // [C]
     fmd::CallOrder order;
     std::string err;
 };
@@ -338,10 +578,12 @@ static int fpm_fail(fmd_fpmatch h, int code, const char* fmt, A... args) { retur
 
 extern "C" {
 
-int fmd_fpmatch_create(const fmd_fpmatch_config* cfg, fmd_fpmatch* out) {
+int fmd_fpmatch_create(const fmd_fpmatch_config* cfg, fmd_fpmatch* out) { return fmd_fpmatch_create_ex(cfg, nullptr, out); }
+
+int fmd_fpmatch_create_ex(const fmd_fpmatch_config* cfg, const fmd_fpmatch_index_config* idx, fmd_fpmatch* out) {
     if (!cfg || !out) return fpm_fail(nullptr, FMD_ERR_ARG, "null configuration or handle");
     std::string why;
-    if (fmd::fpmatch_check(cfg, &why) != FMD_OK) return fpm_fail(nullptr, FMD_ERR_ARG, "%s", why.c_str());
+    if (fmd::fpmatch_check(cfg, &why) != FMD_OK || (idx && fmd::fpmatch_index_check(idx, &why) != FMD_OK)) return fpm_fail(nullptr, FMD_ERR_ARG, "%s", why.c_str());
     if (fmd_device_count() <= 0) return fpm_fail(nullptr, FMD_ERR_NO_DEVICE, "no gfx950 device");
     int dev = cfg->device;
     if (dev < 0 && hipGetDevice(&dev) != hipSuccess) return fpm_fail(nullptr, FMD_ERR_DEVICE, "hipGetDevice failed");
@@ -350,6 +592,12 @@ int fmd_fpmatch_create(const fmd_fpmatch_config* cfg, fmd_fpmatch* out) {
     h->lay = fmd::fpmatch_layout(cfg);
     h->dev = FpmDev{cfg->n_channels, cfg->block, cfg->interval, cfg->hold, (unsigned)cfg->max_errs, h->lay.mask};
     const size_t C = (size_t)cfg->n_channels, W = (size_t)cfg->block, Qm = (size_t)h->lay.max_queries;
+    if (idx) {
+        h->indexed = true;
+        h->icfg = *idx;
+        h->ilay = fmd::fpmatch_index_layout(cfg, idx);
+    }
+    const size_t parts = idx ? 1 : (size_t)h->lay.groups;
     bool ok = h->order.init(dev);
     ok = ok && hipMalloc(&h->d_status, sizeof(fmd_fpmatch_status) * C) == hipSuccess;
     ok = ok && hipMalloc(&h->d_ring, sizeof(uint32_t) * C * W) == hipSuccess;
@@ -357,12 +605,21 @@ int fmd_fpmatch_create(const fmd_fpmatch_config* cfg, fmd_fpmatch* out) {
     ok = ok && hipMalloc(&h->d_starts, sizeof(int) * ((size_t)cfg->max_tracks + 1)) == hipSuccess;
     ok = ok && hipMalloc(&h->d_qbase, sizeof(int) * (C + 1)) == hipSuccess;
     ok = ok && hipMalloc(&h->d_qwin, sizeof(uint32_t) * Qm * W) == hipSuccess;
-    ok = ok && hipMalloc(&h->d_part, sizeof(unsigned long long) * Qm * (size_t)h->lay.groups) == hipSuccess;
+    ok = ok && hipMalloc(&h->d_part, sizeof(unsigned long long) * Qm * parts) == hipSuccess;
     ok = ok && hipMemset(h->d_starts, 0, sizeof(int) * ((size_t)cfg->max_tracks + 1)) == hipSuccess;
+    if (idx) {
+        ok = ok && hipMalloc(&h->d_keys, sizeof(uint32_t) * (size_t)cfg->max_catalogue_words) == hipSuccess;
+        ok = ok && hipMalloc(&h->d_pos, sizeof(int) * (size_t)cfg->max_catalogue_words) == hipSuccess;
+        ok = ok && hipMalloc(&h->d_dir, sizeof(int) * (size_t)h->ilay.dir_entries) == hipSuccess;
+        ok = ok && hipMalloc(&h->d_rowstat, sizeof(uint2) * Qm) == hipSuccess;
+        ok = ok && hipMalloc(&h->d_istatus, sizeof(fmd_fpmatch_index_status) * C) == hipSuccess;
+        ok = ok && hipMemset(h->d_dir, 0, sizeof(int) * (size_t)h->ilay.dir_entries) == hipSuccess;
+    }
     if (!ok || fmd_fpmatch_reset(h, -1) != FMD_OK) {
+        const long long bytes = idx ? h->ilay.bytes : h->lay.bytes;
         (void)hipGetLastError();
         fmd_fpmatch_destroy(h);
-        return fpm_fail(nullptr, FMD_ERR_DEVICE, "device allocation of %lld bytes failed", fmd::fpmatch_layout(cfg).bytes);
+        return fpm_fail(nullptr, FMD_ERR_DEVICE, "device allocation of %lld bytes failed", bytes);
     }
     *out = h;
     return FMD_OK;
@@ -371,7 +628,8 @@ int fmd_fpmatch_create(const fmd_fpmatch_config* cfg, fmd_fpmatch* out) {
 int fmd_fpmatch_destroy(fmd_fpmatch h) {
     if (!h) return FMD_ERR_ARG;
     (void)h->order.quiesce();
-    for (void* p : {(void*)h->d_status, (void*)h->d_ring, (void*)h->d_cat, (void*)h->d_starts, (void*)h->d_qbase, (void*)h->d_qwin, (void*)h->d_part})
+    for (void* p : {(void*)h->d_status, (void*)h->d_ring, (void*)h->d_cat, (void*)h->d_starts, (void*)h->d_qbase, (void*)h->d_qwin, (void*)h->d_part,
+                    (void*)h->d_keys, (void*)h->d_pos, (void*)h->d_dir, (void*)h->d_rowstat, (void*)h->d_istatus})
         if (p) (void)hipFree(p);
     delete h;
     return FMD_OK;
@@ -383,6 +641,8 @@ int fmd_fpmatch_reset(fmd_fpmatch h, int channel) {
     if (!fmd::channel_range(channel, h->cfg.n_channels, &c0, &cn)) return fpm_fail(h, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, h->cfg.n_channels);
     if (!h->order.quiesce()) return fpm_fail(h, FMD_ERR_DEVICE, "synchronise failed");
     hipLaunchKernelGGL(k_fpmatch_reset, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, nullptr, c0, cn, h->d_status);
+    if (h->indexed && hipMemsetAsync(h->d_istatus + c0, 0, sizeof(fmd_fpmatch_index_status) * (size_t)cn, nullptr) != hipSuccess)
+        return fpm_fail(h, FMD_ERR_DEVICE, "clearing the index records failed");
     if (const char* e = fmd::control_end("k_fpmatch_reset launch failed")) return fpm_fail(h, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
@@ -394,6 +654,15 @@ int fmd_fpmatch_load(fmd_fpmatch h, const uint32_t* words, const long long* star
     const long long D = n_tracks > 0 ? starts[n_tracks] : 0;
     if (D > 0 && !words) return fpm_fail(h, FMD_ERR_ARG, "null words");
     if (!h->order.quiesce()) return fpm_fail(h, FMD_ERR_DEVICE, "synchronise failed");
+    if (h->indexed) {                                                        // the index of the new catalogue, built here on the host
+        std::vector<uint32_t> keys((size_t)D);
+        std::vector<int32_t> pos((size_t)D), dir((size_t)h->ilay.dir_entries);
+        fmd::fpmatch_index_build(words, D, h->lay.mask, h->ilay.dir_bits, keys.data(), pos.data(), dir.data());
+        if ((D > 0 && (hipMemcpy(h->d_keys, keys.data(), sizeof(uint32_t) * (size_t)D, hipMemcpyHostToDevice) != hipSuccess ||
+                       hipMemcpy(h->d_pos, pos.data(), sizeof(int) * (size_t)D, hipMemcpyHostToDevice) != hipSuccess)) ||
+            hipMemcpy(h->d_dir, dir.data(), sizeof(int) * dir.size(), hipMemcpyHostToDevice) != hipSuccess)
+            return fpm_fail(h, FMD_ERR_DEVICE, "copy failed");
+    }
     std::vector<int> st((size_t)n_tracks + 1, 0);
     for (int t = 0; t <= n_tracks && n_tracks > 0; t++) st[(size_t)t] = (int)starts[t];
     if (D > 0 && hipMemcpy(h->d_cat, words, sizeof(uint32_t) * (size_t)D, hipMemcpyHostToDevice) != hipSuccess) return fpm_fail(h, FMD_ERR_DEVICE, "copy failed");
@@ -423,6 +692,22 @@ int fmd_fpmatch_process_dev(fmd_fpmatch h, const uint32_t* d_words, long long wo
     const long long tiles = fmd::fpmatch_tiles(h->D, W);
     const int G = (int)(tiles < h->lay.groups ? tiles : h->lay.groups);      // 0 with an empty catalogue
     hipLaunchKernelGGL(k_fpmatch_map, dim3(1), dim3(kMapT), 0, s, h->dev, n, d_nwords, d_active, h->d_status, h->d_qbase);
+    if (h->indexed) {
+        const int probed = rows_max > 0 && h->D > 0 ? 1 : 0;
+        if (probed) {
+            const FpmIdxDev x{h->d_keys, h->d_pos, h->d_dir, h->ilay.dir_bits, h->icfg.max_bucket, h->ilay.chunk_words, h->icfg.follow};
+            hipLaunchKernelGGL(k_fpmatch_gather, dim3((unsigned)rows_max), dim3(64), 0, s, h->dev, n, d_nwords, h->d_status, h->d_qbase, h->d_ring, d_words, words_stride,
+                               h->d_qwin);
+            hipLaunchKernelGGL(k_fpmatch_probe, dim3((unsigned)rows_max), dim3(kFpmIndexThreads), 0, s, C, W, h->d_qbase, h->d_qwin, h->d_cat, h->D, h->d_starts, h->T, x,
+                               h->d_part, h->d_rowstat);
+        }
+        hipLaunchKernelGGL(k_fpmatch_finish_idx, dim3((unsigned)C), dim3(64), 0, s, h->dev, n, d_nwords, d_active, h->d_qbase, h->d_part, h->d_rowstat, probed, h->d_qwin,
+                           h->d_cat, h->D, h->icfg.follow, h->d_starts, h->T, d_words, words_stride, h->d_status, h->d_istatus, h->d_ring, d_events, events_stride,
+                           d_nevents, d_flags, d_ok);
+        if (hipGetLastError() != hipSuccess) return fpm_fail(h, FMD_ERR_DEVICE, "k_fpmatch launch failed");
+        if (const char* e = h->order.end(s)) return fpm_fail(h, FMD_ERR_DEVICE, "%s", e);
+        return FMD_OK;
+    }
     if (rows_max > 0 && G > 0) {
         hipLaunchKernelGGL(k_fpmatch_gather, dim3((unsigned)rows_max), dim3(64), 0, s, h->dev, n, d_nwords, h->d_status, h->d_qbase, h->d_ring, d_words, words_stride,
                            h->d_qwin);
@@ -447,6 +732,15 @@ int fmd_fpmatch_get_status(fmd_fpmatch h, fmd_fpmatch_status* out) {
 int fmd_fpmatch_status_dev(fmd_fpmatch h, const fmd_fpmatch_status** d_status) {
     if (!h || !d_status) return fpm_fail(h, FMD_ERR_ARG, "null object or output");
     *d_status = h->d_status;
+    return FMD_OK;
+}
+
+int fmd_fpmatch_get_index_status(fmd_fpmatch h, fmd_fpmatch_index_status* out) {
+    if (!h || !out) return fpm_fail(h, FMD_ERR_ARG, "null object or output");
+    if (!h->indexed) return fpm_fail(h, FMD_ERR_STATE, "the object was created without an index");
+    if (!h->order.quiesce()) return fpm_fail(h, FMD_ERR_DEVICE, "synchronise failed");
+    if (hipMemcpy(out, h->d_istatus, sizeof(fmd_fpmatch_index_status) * (size_t)h->cfg.n_channels, hipMemcpyDeviceToHost) != hipSuccess)
+        return fpm_fail(h, FMD_ERR_DEVICE, "copy failed");
     return FMD_OK;
 }
 

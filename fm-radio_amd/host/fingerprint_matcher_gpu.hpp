@@ -8,6 +8,12 @@
 //   fm.Process(fp.WordsDev(0), fp.MaxPrints(), fp.CountsDev(), fp.MaxPrints(), nullptr, stream);   // behind the fingerprinter, same stream
 //   fm.OkDev();                                                                 // [C] uint8 for a mixer bus or a recorder's d_active
 //   fm.Update(); fm.Status(c).track; fm.Events(c); fm.Event(c, i);
+//
+// With an index configuration the object searches through the catalogue's index instead of by brute force (fmd_fpmatch_create_ex):
+//
+//   fmd_fpmatch_index_config idx; fmd_fpmatch_index_default_config(&idx);
+//   fmd_host::FingerprintMatcher_GPU fm(cfg, idx);
+//   fm.Update(); fm.IndexStatus(c).candidates;
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -25,12 +31,15 @@ namespace fmd_host {
 class FingerprintMatcher_GPU {
     fmd_fpmatch h = nullptr;
     fmd_fpmatch_config cfg{};
+    fmd_fpmatch_index_config idx{};
+    bool indexed = false;
     long long max_events = 0;
     fmd_fpmatch_event* d_events = nullptr;   // [C][max_events]
     int* d_counts = nullptr;                 // [C]
     uint8_t* d_flags = nullptr;              // [C]
     uint8_t* d_ok = nullptr;                 // [C]
     std::vector<fmd_fpmatch_status> status;
+    std::vector<fmd_fpmatch_index_status> index_status;   // of an indexed object
     std::vector<int> counts;
     std::vector<uint8_t> flags;
     std::vector<fmd_fpmatch_event> events;
@@ -41,12 +50,11 @@ class FingerprintMatcher_GPU {
             if (p) (void)hipFree(p);
         h = nullptr; d_events = nullptr; d_counts = nullptr; d_flags = nullptr; d_ok = nullptr;
     }
-public:
-    explicit FingerprintMatcher_GPU(const fmd_fpmatch_config& _cfg) : cfg(_cfg) {
-        if (fmd_fpmatch_create(&cfg, &h) != FMD_OK) throw std::runtime_error(std::string("fmd_fpmatch_create: ") + fmd_fpmatch_last_error(nullptr));
+    void create() {
+        if (fmd_fpmatch_create_ex(&cfg, indexed ? &idx : nullptr, &h) != FMD_OK) throw std::runtime_error(std::string("fmd_fpmatch_create: ") + fmd_fpmatch_last_error(nullptr));
         max_events = fmd_fpmatch_max_events(cfg.interval, cfg.max_words);
         const size_t C = (size_t)cfg.n_channels;
-        status.resize(C); counts.assign(C, 0); flags.assign(C, 0); events.assign(C * (size_t)max_events, fmd_fpmatch_event{});
+        status.resize(C); index_status.assign(indexed ? C : 0, fmd_fpmatch_index_status{}); counts.assign(C, 0); flags.assign(C, 0); events.assign(C * (size_t)max_events, fmd_fpmatch_event{});
         // (create has made `device` current where one was given); before the first Process every count and byte is 0
         if (hipMalloc(reinterpret_cast<void**>(&d_events), sizeof(fmd_fpmatch_event) * events.size()) != hipSuccess ||
             hipMalloc(reinterpret_cast<void**>(&d_counts), sizeof(int) * C) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&d_flags), C) != hipSuccess ||
@@ -56,6 +64,10 @@ public:
             throw std::runtime_error("FingerprintMatcher_GPU: the output's allocation failed");
         }
     }
+public:
+    explicit FingerprintMatcher_GPU(const fmd_fpmatch_config& _cfg) : cfg(_cfg) { create(); }
+    // an indexed object: the catalogue is searched through its index (max_bucket, follow)
+    FingerprintMatcher_GPU(const fmd_fpmatch_config& _cfg, const fmd_fpmatch_index_config& _idx) : cfg(_cfg), idx(_idx), indexed(true) { create(); }
     ~FingerprintMatcher_GPU() { release(); }
     FingerprintMatcher_GPU(const FingerprintMatcher_GPU&) = delete;
     FingerprintMatcher_GPU& operator=(const FingerprintMatcher_GPU&) = delete;
@@ -63,7 +75,9 @@ public:
     int GetTotalChannels() const { return cfg.n_channels; }
     const fmd_fpmatch_config& Config() const { return cfg; }
     long long MaxEvents() const { return max_events; }       // events a station's view holds: also the stride from one station to the next
-    long long StateBytes() const { return fmd_fpmatch_state_bytes(&cfg); }
+    bool Indexed() const { return indexed; }
+    const fmd_fpmatch_index_config& IndexConfig() const { return idx; }
+    long long StateBytes() const { return indexed ? fmd_fpmatch_index_state_bytes(&cfg, &idx) : fmd_fpmatch_state_bytes(&cfg); }
 
     // replaces the catalogue: track t is words[starts[t] ... starts[t + 1] - 1]; waits for the object's work
     void Load(const uint32_t* words, const long long* starts, int n_tracks) { check(fmd_fpmatch_load(h, words, starts, n_tracks), "fmd_fpmatch_load"); }
@@ -94,6 +108,7 @@ public:
     // waits for the object's work and copies every station's record, count, byte and events to the host
     void Update() {
         check(fmd_fpmatch_get_status(h, status.data()), "fmd_fpmatch_get_status");
+        if (indexed) check(fmd_fpmatch_get_index_status(h, index_status.data()), "fmd_fpmatch_get_index_status");
         if (hipMemcpy(counts.data(), d_counts, sizeof(int) * counts.size(), hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(flags.data(), d_flags, flags.size(), hipMemcpyDeviceToHost) != hipSuccess ||
             hipMemcpy(events.data(), d_events, sizeof(fmd_fpmatch_event) * events.size(), hipMemcpyDeviceToHost) != hipSuccess)
@@ -101,6 +116,8 @@ public:
     }
     // as of the last Update()
     const fmd_fpmatch_status& Status(int c) const { return status.at((size_t)c); }
+    // of an indexed object (std::out_of_range otherwise)
+    const fmd_fpmatch_index_status& IndexStatus(int c) const { return index_status.at((size_t)c); }
     int Events(int c) const { return counts.at((size_t)c); }
     bool Identified(int c) const { return (flags.at((size_t)c) & 1u) != 0; }
     const fmd_fpmatch_event& Event(int c, int i) const {

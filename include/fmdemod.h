@@ -1907,9 +1907,30 @@ const char* fmd_fprint_last_error(fmd_fprint h);
  *   memory      the catalogue (4 bytes a word), a ring of W words a station, the call's query windows (W words a query) and the
  *               partial minima of the search (8 bytes a query and column group, at most 256 groups): fmd_fpmatch_state_bytes reports
  *               the whole for max_words, max_catalogue_words and max_tracks.
- * Not built: the paper's hash-index prefilter (this exact search is the baseline one would be checked against), soft bits,
- * station-against-station comparison, catalogues loaded from device memory or appended to, several catalogues, per-station
- * configurations.
+ *   index       a second search method for the same object, chosen at create (fmd_fpmatch_create_ex with an fmd_fpmatch_index_config):
+ *               the paper's hash-index prefilter.  K = max_bucket, d = follow.  It is NOT exact: a query whose window shares no exact
+ *               masked word with the right position misses.  Restated in numpy by tests/fpmatch_index_ref.py.  W, I, mask, D, starts,
+ *               position validity, push, the query schedule, the detector, events, records, bytes and `inactive` are as above.  occ(k) is
+ *               the set of catalogue word positions p' with cat[p'] & mask == k.  The candidate set S of a query with window q of
+ *               station c:
+ *                 look-ups   for j = 0 ... W - 1 and k = q[j] & mask: where |occ(k)| > K the word is skipped (a common word, such as
+ *                            silence's, carries no information); otherwise every p' in occ(k) proposes p = p' - j.
+ *                 follow     where d > 0 and the station's record is identified at the time of this query (track >= 0 after the
+ *                            detector step of the station's previous query, also inside one call), p_exp = starts[track] + offset +
+ *                            I * (misses + 1), and p_exp - d ... p_exp + d are proposed.
+ *                 validity   S is the valid positions among those proposed (negative ones, ones above D - W and windows straddling two
+ *                            tracks are dropped); duplicates count once.
+ *               The result is the smallest errs(p) over S, on a tie the smallest p, reported as track, offset and errs as above; with S
+ *               empty track = -1, offset = 0, errs = 0xffffffff, a miss.  Nothing depends on the call split, on tiling or on how
+ *               repeated proposals are dropped.  fmd_fpmatch_load builds the index from the new catalogue on the host (a stable LSD
+ *               radix sort of (masked word, position) pairs and a directory over the keys' top dir_bits); a refused catalogue keeps
+ *               the old index, n_tracks = 0 empties it.
+ *   index stats a 32-byte record per station (fmd_fpmatch_get_index_status), cleared by reset, kept by load, left alone for an
+ *               inactive station: candidates = the sum over queries and j of |occ| for the words not skipped, skipped = the
+ *               (query, j) pairs skipped, followed = the queries the follow rule applied to, empty = the queries with S empty.
+ * Not built: soft or reliability-weighted bits, flipping unreliable bits to widen the look-up, building the index on the device, a
+ * fall-back to the brute-force search on an indexed miss, station-against-station comparison, catalogues loaded from device memory or
+ * appended to, several catalogues, per-station configurations.
  * ------------------------------------------------------------------------------------------------------------------ */
 typedef struct fmd_fpmatch_s* fmd_fpmatch;
 typedef struct {
@@ -1924,6 +1945,11 @@ typedef struct {
     long long max_catalogue_words; /* in [W, 2^28] */
     int       device;              /* HIP device ordinal, -1 = current */
 } fmd_fpmatch_config;
+/* the index of an indexed object (see "index" above) */
+typedef struct {
+    int       max_bucket;          /* K, 1 ... 64: a window word whose masked value the catalogue holds more than K times is skipped */
+    int       follow;              /* d, 0 ... 8: an identified station's expected position +- d is proposed too; 0 = off */
+} fmd_fpmatch_index_config;
 /* what the kernels are built on, from the constants they use */
 typedef struct {
     unsigned  mask;                /* 0xffffffff << (32 - n_bits) */
@@ -1934,6 +1960,22 @@ typedef struct {
     long long max_events;          /* fmd_fpmatch_max_events(interval, max_words) */
     long long max_queries;         /* n_channels * max_events */
 } fmd_fpmatch_design_t;
+/* what the index and k_fpmatch_probe are built on */
+typedef struct {
+    int       dir_bits;            /* the directory is over the keys' top dir_bits: min(n_bits, ceil(log2(max_catalogue_words)) - 4) in 1 ... 24 */
+    int       chunk;               /* candidates the probe's LDS list holds at most */
+    int       chunk_words;         /* window words whose runs a chunk takes: min(256, chunk / K) */
+    int       table;               /* slots of the LDS set that drops repeated proposals */
+    long long dir_entries;         /* 2^dir_bits + 1 */
+    long long index_bytes;         /* 8 * max_catalogue_words (keys and positions) + 4 * dir_entries */
+} fmd_fpmatch_index_design_t;
+/* one per station of an indexed object, 32 bytes.  After create and reset: all 0 */
+typedef struct {
+    unsigned long long candidates; /* the sum over queries and window words j of |occ| for the words not skipped */
+    unsigned long long skipped;    /* (query, j) pairs skipped */
+    unsigned long long followed;   /* queries to which the follow rule applied */
+    unsigned long long empty;      /* queries with S empty */
+} fmd_fpmatch_index_status;
 /* one per query, 24 bytes */
 typedef struct {
     unsigned long long end;        /* e: the station's word count at the window's end */
@@ -1974,9 +2016,23 @@ int fmd_fpmatch_design(const fmd_fpmatch_config* cfg, fmd_fpmatch_design_t* out)
 int fmd_fpmatch_check_catalogue(const fmd_fpmatch_config* cfg, const long long* starts, int n_tracks);
 /* the bytes of device memory an object of cfg holds; FMD_ERR_ARG for an invalid configuration */
 long long fmd_fpmatch_state_bytes(const fmd_fpmatch_config* cfg);
+/* max_bucket 8, follow 2 */
+int fmd_fpmatch_index_default_config(fmd_fpmatch_index_config* idx);
+/* FMD_OK for a valid pair of configurations and then *out (may be NULL) written; FMD_ERR_ARG otherwise and nothing written */
+int fmd_fpmatch_index_design(const fmd_fpmatch_config* cfg, const fmd_fpmatch_index_config* idx, fmd_fpmatch_index_design_t* out);
+/* the bytes of device memory an indexed object holds: the brute-force object's with one partial minimum a query instead of one a
+ * column group, a (candidates, skipped) pair a query, the index records and the index; FMD_ERR_ARG for an invalid pair */
+long long fmd_fpmatch_index_state_bytes(const fmd_fpmatch_config* cfg, const fmd_fpmatch_index_config* idx);
+/* the index fmd_fpmatch_load builds, into host memory: keys [n_words] the masked words ascending, pos [n_words] their positions (equal
+ * keys in ascending position), dir [dir_entries]: dir[b] = the first i with keys[i] >> (32 - dir_bits) >= b.  FMD_ERR_ARG, and nothing
+ * written, for an invalid pair, n_words outside [0, max_catalogue_words] or a null array (keys, pos and words may be NULL at n_words 0) */
+int fmd_fpmatch_index_build(const fmd_fpmatch_config* cfg, const fmd_fpmatch_index_config* idx, const uint32_t* words, long long n_words, uint32_t* keys, int* pos,
+                            int* dir);
 
 /* FMD_ERR_DEVICE where the device memory (fmd_fpmatch_state_bytes) cannot be had */
 int fmd_fpmatch_create(const fmd_fpmatch_config* cfg, fmd_fpmatch* out);
+/* idx == NULL is fmd_fpmatch_create exactly; otherwise an indexed object (see "index" above; its memory is fmd_fpmatch_index_state_bytes) */
+int fmd_fpmatch_create_ex(const fmd_fpmatch_config* cfg, const fmd_fpmatch_index_config* idx, fmd_fpmatch* out);
 int fmd_fpmatch_destroy(fmd_fpmatch h);
 /* station `channel` (-1 = every station) as after create: ring emptied, counters 0, track -1; the catalogue stays.  Waits for the
  * object's earlier work */
@@ -1996,6 +2052,8 @@ int fmd_fpmatch_get_status(fmd_fpmatch h, fmd_fpmatch_status* out);
 /* the device's own [C] records, for a consumer on the device: ordered behind the object's work on the stream of its last call, valid
  * until the next call */
 int fmd_fpmatch_status_dev(fmd_fpmatch h, const fmd_fpmatch_status** d_status);
+/* out [C]; synchronises with the object's work.  FMD_ERR_STATE on an object created without an index */
+int fmd_fpmatch_get_index_status(fmd_fpmatch h, fmd_fpmatch_index_status* out);
 const char* fmd_fpmatch_last_error(fmd_fpmatch h);
 
 #ifdef __cplusplus
