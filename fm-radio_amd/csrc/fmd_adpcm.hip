@@ -325,12 +325,11 @@ int fmd_adpcm_destroy(fmd_adpcm e) {
 
 int fmd_adpcm_reset(fmd_adpcm e, int channel) {
     if (!e) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= e->C) return ad_fail(e, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, e->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, e->C, &c0, &cn)) return ad_fail(e, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, e->C);
     if (!e->order.quiesce()) return ad_fail(e, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? e->C : 1;
     hipLaunchKernelGGL(k_adpcm_reset, dim3((unsigned)((cn + kT - 1) / kT)), dim3(kT), 0, nullptr, c0, cn, e->d_status, e->d_priv);
-    if (hipGetLastError() != hipSuccess) return ad_fail(e, FMD_ERR_DEVICE, "k_adpcm_reset launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return ad_fail(e, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* m = fmd::control_end("k_adpcm_reset launch failed")) return ad_fail(e, FMD_ERR_DEVICE, "%s", m);
     return FMD_OK;
 }
 
@@ -351,13 +350,13 @@ int fmd_adpcm_process_f32_dev(fmd_adpcm e, const float* d_in, long long in_strid
 
 int fmd_adpcm_flush(fmd_adpcm e, int channel, uint8_t* d_out, long long out_stride, int* d_nblocks, void* stream) {
     if (!e) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= e->C) return ad_fail(e, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, e->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, e->C, &c0, &cn)) return ad_fail(e, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, e->C);
     if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 4 != 0) return ad_fail(e, FMD_ERR_ARG, "null output, or output not aligned to 4 bytes");
     if (out_stride % 4 != 0 || out_stride < e->align)
         return ad_fail(e, FMD_ERR_ARG, "out_stride %lld is no multiple of 4 or below the block's %d bytes", out_stride, e->align);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (const char* m = e->order.begin(s)) return ad_fail(e, FMD_ERR_DEVICE, "%s", m);
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? e->C : 1;
     hipLaunchKernelGGL(k_adpcm_flush, dim3((unsigned)((cn + kSt - 1) / kSt)), dim3(kT), 0, s, c0, cn, e->S, e->align / 4, e->d_status, e->d_priv, e->d_open,
                        reinterpret_cast<uint32_t*>(d_out), out_stride / 4, d_nblocks);
     if (hipGetLastError() != hipSuccess) return ad_fail(e, FMD_ERR_DEVICE, "k_adpcm_flush launch failed");

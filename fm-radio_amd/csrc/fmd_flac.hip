@@ -577,12 +577,11 @@ int fmd_flac_destroy(fmd_flac e) {
 
 int fmd_flac_reset(fmd_flac e, int channel) {
     if (!e) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= e->C) return fl_fail(e, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, e->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, e->C, &c0, &cn)) return fl_fail(e, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, e->C);
     if (!e->order.quiesce()) return fl_fail(e, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? e->C : 1;
     hipLaunchKernelGGL(k_flac_reset, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, nullptr, c0, cn, e->d_status);
-    if (hipGetLastError() != hipSuccess) return fl_fail(e, FMD_ERR_DEVICE, "k_flac_reset launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return fl_fail(e, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* m = fmd::control_end("k_flac_reset launch failed")) return fl_fail(e, FMD_ERR_DEVICE, "%s", m);
     return FMD_OK;
 }
 
@@ -603,13 +602,13 @@ int fmd_flac_process_f32_dev(fmd_flac e, const float* d_in, long long in_stride,
 
 int fmd_flac_flush(fmd_flac e, int channel, uint8_t* d_out, long long out_stride, int* d_nbytes, int* d_nframes, void* stream) {
     if (!e) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= e->C) return fl_fail(e, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, e->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, e->C, &c0, &cn)) return fl_fail(e, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, e->C);
     if (!d_out || reinterpret_cast<uintptr_t>(d_out) % 4 != 0) return fl_fail(e, FMD_ERR_ARG, "null output, or output not aligned to 4 bytes");
     const long long need = fmd::flac_max_bytes(e->S, 1);
     if (out_stride % 4 != 0 || out_stride < need) return fl_fail(e, FMD_ERR_ARG, "out_stride %lld is no multiple of 4 or below a frame's %lld bytes", out_stride, need);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (const char* m = e->order.begin(s)) return fl_fail(e, FMD_ERR_DEVICE, "%s", m);
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? e->C : 1;
     hipLaunchKernelGGL(k_flac_flush, dim3((unsigned)cn), dim3(kT), e->lds(), s, c0, e->S, e->fs, e->sr_code, e->img_words, e->d_status, e->d_open, e->d_crc, d_out,
                        out_stride, d_nbytes, d_nframes);
     if (hipGetLastError() != hipSuccess) return fl_fail(e, FMD_ERR_DEVICE, "k_flac_flush launch failed");

@@ -5,7 +5,9 @@
 // on a tie the lowest position.  All integer, so every tiling gives the same result.
 //
 // Four kernels a call:
-//   k_fpmatch_map     one workgroup: the queries each active station fires, as an exclusive prefix sum: the rows of the search.
+//   k_fpmatch_map     one workgroup: the queries each active station fires, as an exclusive prefix sum: the rows of the search.  The scan
+//                     and its inverse (row -> station, and position -> track over the starts table) are fmd_rowmap.h's, shared with
+//                     the fingerprinter.
 //   k_fpmatch_gather  a workgroup a query: its W words, masked, from the ring and the caller's new words into a contiguous window.
 //   k_fpmatch_search  queries x catalogue positions with depth W.  A workgroup holds kFpmatchQueries queries and walks the column tiles
 //                     of its column group: the tile's kFpmatchTile + W - 1 catalogue words are staged once in LDS, lane <-> position
@@ -15,7 +17,8 @@
 //                     tiles, reduced across lanes by shuffles and across the four wavefronts through LDS, and written as the group's
 //                     partial minimum.
 //   k_fpmatch_finish  a wavefront a station: per query the minimum over the groups' partials, the track from the starts table, the
-//                     detector, the event; then the ring's newest words, the record, the count and the bytes.
+//                     detector, the event; then the ring's newest words, the record, the count and the bytes.  All but the first step is
+//                     fpm_finish, stated once for both finish kernels: a kernel is the source of a row's key, handed in as a hook.
 // An indexed object (fmd_fpmatch_create_ex) keeps map and gather and puts two kernels of its own behind them:
 //   k_fpmatch_probe       a workgroup a query.  Lane <-> window word j: the directory slice of the word's key, a binary search for the
 //                         key's run in the sorted keys, runs longer than K skipped.  A run's positions p' propose p = p' - j; a proposal
@@ -24,16 +27,16 @@
 //                         runs fit the list.  Then a wavefront (16 lanes where W < 64) a listed position: track validity, and the W
 //                         catalogue words at p read by consecutive lanes against the window in LDS, XOR, population count, a shuffle
 //                         sum.  The packed minimum as in the search; one partial a row, and the row's (candidates, skipped) counts.
-//   k_fpmatch_finish_idx  k_fpmatch_finish for the indexed object: walks a station's queries in order, and before a query's detector
-//                         step counts the follow rule's 2 d + 1 positions around the expected one itself, because they depend on the
-//                         detector state the query before left; adds the row's counts to the station's index record.
+//   k_fpmatch_finish_idx  fpm_finish with the indexed object's key: the row's one partial and, counted here before the query's detector
+//                         step, the follow rule's 2 d + 1 positions around the expected one, because they depend on the detector state
+//                         the query before left; adds the row's counts to the station's index record.
 // No global atomics (the probe's set and list use LDS atomics inside one workgroup), no register spills (scratch 0), no workgroup waits
 // on another, ordinary vector stores only.
 //
 // Bounds: k_fpmatch_gather reads ring slots taken mod W, new words below the station's k <= n <= words_stride, and writes window rows
 // below qbase[C] <= C * max_events(I, n) <= max_queries.  k_fpmatch_search reads catalogue words below D (zero behind it), LDS words below
 // kFpmatchTile - 1 + W - 1 < lds_words, starts entries 0 ... T, window rows below qbase[C] (a row past the last repeats it) and writes
-// partials at row * G + group, group < G <= groups.  k_fpmatch_finish writes events below the station's count <= max_events(I, n) <=
+// partials at row * G + group, group < G <= groups.  fpm_finish (both finish kernels) writes events below the station's count <= max_events(I, n) <=
 // events_stride and ring slots mod W.  k_fpmatch_probe reads window row r < qbase[C], directory entries b and b + 1 with b = key >> (32 -
 // dir_bits) < 2^dir_bits (the directory holds 2^dir_bits + 1), keys and positions at dir[b] ... dir[b + 1] - 1 < D, s_win below W <= 1024;
 // a chunk lists at most chunk_words * K <= kFpmIndexChunk positions (chunk_words = min(256, kFpmIndexChunk / K): W = 1024 at K = 64 is 16
@@ -49,6 +52,7 @@
 
 #include "fmd_fpmatch_design.h"
 #include "fmd_fpmatch_index.h"
+#include "fmd_rowmap.h"
 #include "fmd_side.h"
 #include "fmdemod.h"
 
@@ -59,10 +63,10 @@ using fmd::kFpmatchTile;
 using fmd::kFpmIndexChunk;
 using fmd::kFpmIndexTable;
 using fmd::kFpmIndexThreads;
+using fmd::rowmap::owner;               // the track of a position (starts [T + 1]) and the station of a row (qbase [C + 1])
 
 namespace {
 
-constexpr int kMapT = 1024;
 constexpr int kQR = kFpmatchQueries;
 constexpr int kWaves = kFpmatchThreads / 64;
 constexpr int kPasses = kFpmatchTile / kFpmatchThreads;
@@ -118,26 +122,6 @@ __device__ __forceinline__ uint32_t fpm_word(const uint32_t* __restrict__ ring, 
 // errs += popcount(q ^ c), both masked already: v_xor_b32, v_bcnt_u32_b32
 __device__ __forceinline__ unsigned fpm_errs(unsigned errs, uint32_t q, uint32_t c) { return (unsigned)__builtin_popcount(q ^ c) + errs; }
 
-// the track of position p: the largest t with starts[t] <= p
-__device__ __forceinline__ int fpm_track(const int* __restrict__ starts, int T, int p) {
-    int lo = 0, hi = T;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (starts[mid] <= p) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
-// the station of row r: qbase[c] <= r < qbase[c + 1]
-__device__ __forceinline__ int fpm_station(const int* __restrict__ qbase, int C, int r) {
-    int lo = 0, hi = C;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (qbase[mid] <= r) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ unsigned long long fpm_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 
 // the minimum over the wavefront, in every lane
@@ -151,34 +135,15 @@ __device__ __forceinline__ unsigned long long fpm_wave_min(unsigned long long v)
 }
 
 // qbase [C + 1]: the exclusive prefix sum of the queries each active station fires
-__global__ __launch_bounds__(kMapT) void k_fpmatch_map(FpmDev g, int n, const int* __restrict__ nwords, const uint8_t* __restrict__ active,
-                                                      const fmd_fpmatch_status* __restrict__ status, int* __restrict__ qbase) {
-    __shared__ int part[kMapT];
-    const int tid = threadIdx.x, C = g.C;
-    const int per = (C + kMapT - 1) / kMapT;
-    const int c0 = min(tid * per, C), c1 = min(c0 + per, C);
+__global__ __launch_bounds__(fmd::rowmap::kThreads) void k_fpmatch_map(FpmDev g, int n, const int* __restrict__ nwords, const uint8_t* __restrict__ active,
+                                                                      const fmd_fpmatch_status* __restrict__ status, int* __restrict__ qbase) {
     auto count = [&](int c) {
         if (active && active[c] == 0) return 0;
         bool cl;
         unsigned long long e0;
         return fpm_queries(status[c].words, fpm_take(nwords, c, n, &cl), g.W, g.I, &e0);
     };
-    int sum = 0;
-    for (int c = c0; c < c1; c++) sum += count(c);
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < kMapT; d <<= 1) {
-        const int v = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - sum;
-    for (int c = c0; c < c1; c++) {
-        qbase[c] = run;
-        run += count(c);
-    }
-    if (tid == kMapT - 1) qbase[C] = part[tid];
+    fmd::rowmap::scan(g.C, count, qbase);
 }
 
 // qwin [rows][W]: row r's window, masked
@@ -187,7 +152,7 @@ __global__ __launch_bounds__(64) void k_fpmatch_gather(FpmDev g, int n, const in
                                                       long long words_stride, uint32_t* __restrict__ qwin) {
     const int r = blockIdx.x;
     if (r >= qbase[g.C]) return;                                             // surplus workgroups leave at once
-    const int c = fpm_station(qbase, g.C, r);
+    const int c = owner(qbase, g.C, r);                                      // qbase[c] <= r < qbase[c + 1]
     const unsigned long long before = status[c].words;
     bool cl;
     unsigned long long e0;
@@ -226,7 +191,7 @@ __global__ __launch_bounds__(kFpmatchThreads) void k_fpmatch_search(int C, int W
             const int pl = s * kFpmatchThreads + wave * 64 + lane, p = base + pl;
             bool valid = p < npos;
             if (valid) {
-                const int tr = fpm_track(starts, T, p);
+                const int tr = owner(starts, T, p);
                 valid = p + W <= starts[tr + 1];
             }
             if (!__any(valid)) continue;                                     // (per wavefront; no barrier inside)
@@ -262,14 +227,16 @@ __global__ __launch_bounds__(kFpmatchThreads) void k_fpmatch_search(int C, int W
     }
 }
 
-// a wavefront a station; G = 0 with an empty catalogue
-__global__ __launch_bounds__(64) void k_fpmatch_finish(FpmDev g, int n, const int* __restrict__ nwords, const uint8_t* __restrict__ active, const int* __restrict__ qbase,
-                                                      const unsigned long long* __restrict__ part, int G, const int* __restrict__ starts, int T,
-                                                      const uint32_t* __restrict__ words, long long words_stride, fmd_fpmatch_status* __restrict__ status,
-                                                      uint32_t* __restrict__ ring_all, fmd_fpmatch_event* __restrict__ events, long long events_stride,
-                                                      int* __restrict__ nevents, uint8_t* __restrict__ flags, uint8_t* __restrict__ ok) {
-    const int c = blockIdx.x, lane = threadIdx.x;
-    if (active && active[c] == 0) return;
+// The finish of a call, stated once for both objects: a wavefront a station (the caller has seen to `active`).  Walks the station's
+// queries in order: key(row, st) is the row's packed minimum errs << 32 | p, or kNoKey, called with the record st as the query before
+// left it and the same in every lane; then the key as (track, offset, errs), the detector's step, the event.  Behind the walk, when every
+// reader of the ring and of the windows is done (k_fpmatch_gather and whatever key() reads): the ring's newest words, the record, the
+// count and the bytes.  key's state is the caller's locals.
+template <typename Key>
+__device__ __forceinline__ void fpm_finish(const FpmDev& g, int c, int lane, int n, const int* __restrict__ nwords, const int* __restrict__ qbase,
+                                           const int* __restrict__ starts, int T, const uint32_t* __restrict__ words, long long words_stride,
+                                           fmd_fpmatch_status* __restrict__ status, uint32_t* __restrict__ ring_all, fmd_fpmatch_event* __restrict__ events,
+                                           long long events_stride, int* __restrict__ nevents, uint8_t* __restrict__ flags, uint8_t* __restrict__ ok, Key&& key) {
     fmd_fpmatch_status st = status[c];
     const unsigned long long before = st.words;
     bool clamped;
@@ -279,16 +246,14 @@ __global__ __launch_bounds__(64) void k_fpmatch_finish(FpmDev g, int n, const in
     const int row0 = qbase[c];
     // every lane walks the detector alike; lane 0 stores
     for (int i = 0; i < cnt; i++) {
-        unsigned long long key = kNoKey;
-        for (int y = lane; y < G; y += 64) key = fpm_min(key, part[(size_t)(row0 + i) * (size_t)G + y]);
-        key = fpm_wave_min(key);
+        const unsigned long long m = key(row0 + i, st);
         const unsigned long long e = e0 + (unsigned long long)i * (unsigned long long)g.I;
         int track = -1, offset = 0;
         unsigned errs = 0xffffffffu;
-        if (key != kNoKey) {
-            const int p = (int)(unsigned)key;
-            errs = (unsigned)(key >> 32);
-            track = fpm_track(starts, T, p);
+        if (m != kNoKey) {
+            const int p = (int)(unsigned)m;
+            errs = (unsigned)(m >> 32);
+            track = owner(starts, T, p);
             offset = p - starts[track];
         }
         const bool hit = track >= 0 && errs <= g.max_errs;
@@ -310,7 +275,7 @@ __global__ __launch_bounds__(64) void k_fpmatch_finish(FpmDev g, int n, const in
             events[(size_t)c * (size_t)events_stride + (size_t)i] = ev;
         }
     }
-    // the ring's newest words: of the k new ones the last min(k, W)  (k_fpmatch_gather, the ring's only reader, is done)
+    // the ring's newest words: of the k new ones the last min(k, W)
     uint32_t* ring = ring_all + (size_t)c * (size_t)g.W;
     for (int j = (k > g.W ? k - g.W : 0) + lane; j < k; j += 64)
         ring[(int)((before + (unsigned long long)j) % (unsigned long long)g.W)] = words[(size_t)c * (size_t)words_stride + (size_t)j];
@@ -326,8 +291,24 @@ __global__ __launch_bounds__(64) void k_fpmatch_finish(FpmDev g, int n, const in
     }
 }
 
+// a wavefront a station: a row's key is the minimum over its G partials; G = 0 with an empty catalogue
+__global__ __launch_bounds__(64) void k_fpmatch_finish(FpmDev g, int n, const int* __restrict__ nwords, const uint8_t* __restrict__ active, const int* __restrict__ qbase,
+                                                      const unsigned long long* __restrict__ part, int G, const int* __restrict__ starts, int T,
+                                                      const uint32_t* __restrict__ words, long long words_stride, fmd_fpmatch_status* __restrict__ status,
+                                                      uint32_t* __restrict__ ring_all, fmd_fpmatch_event* __restrict__ events, long long events_stride,
+                                                      int* __restrict__ nevents, uint8_t* __restrict__ flags, uint8_t* __restrict__ ok) {
+    const int c = blockIdx.x, lane = threadIdx.x;
+    if (active && active[c] == 0) return;
+    fpm_finish(g, c, lane, n, nwords, qbase, starts, T, words, words_stride, status, ring_all, events, events_stride, nevents, flags, ok,
+               [&](int row, const fmd_fpmatch_status&) {
+                   unsigned long long key = kNoKey;
+                   for (int y = lane; y < G; y += 64) key = fpm_min(key, part[(size_t)row * (size_t)G + y]);
+                   return fpm_wave_min(key);
+               });
+}
+
 // whether position p, inside [0, D - W], has its W words inside one track
-__device__ __forceinline__ bool fpm_valid(const int* __restrict__ starts, int T, int p, int W) { return p + W <= starts[fpm_track(starts, T, p) + 1]; }
+__device__ __forceinline__ bool fpm_valid(const int* __restrict__ starts, int T, int p, int W) { return p + W <= starts[owner(starts, T, p) + 1]; }
 
 // the sum over groups of L consecutive lanes (L = 16 or 64), in every lane of the group
 template <int L>
@@ -440,7 +421,9 @@ __global__ __launch_bounds__(kFpmIndexThreads) void k_fpmatch_probe(int C, int W
     }
 }
 
-// k_fpmatch_finish for the indexed object: a wavefront a station; probed = 0 with an empty catalogue (no rows were probed)
+// k_fpmatch_finish for the indexed object: a row's key is its one partial and the follow rule's positions, counted here against the
+// detector state the query before left; the row's counts go to the station's index record.  probed = 0 with an empty catalogue (no
+// rows were probed)
 __global__ __launch_bounds__(64) void k_fpmatch_finish_idx(FpmDev g, int n, const int* __restrict__ nwords, const uint8_t* __restrict__ active, const int* __restrict__ qbase,
                                                           const unsigned long long* __restrict__ part, const uint2* __restrict__ rowstat, int probed,
                                                           const uint32_t* __restrict__ qwin, const uint32_t* __restrict__ cat, int D, int follow,
@@ -450,80 +433,32 @@ __global__ __launch_bounds__(64) void k_fpmatch_finish_idx(FpmDev g, int n, cons
                                                           int* __restrict__ nevents, uint8_t* __restrict__ flags, uint8_t* __restrict__ ok) {
     const int c = blockIdx.x, lane = threadIdx.x;
     if (active && active[c] == 0) return;
-    fmd_fpmatch_status st = status[c];
     fmd_fpmatch_index_status ix = istatus[c];
-    const unsigned long long before = st.words;
-    bool clamped;
-    const int k = fpm_take(nwords, c, n, &clamped);
-    unsigned long long e0;
-    const int cnt = fpm_queries(before, k, g.W, g.I, &e0);
-    const int row0 = qbase[c];
-    // every lane walks the detector alike; lane 0 stores
-    for (int i = 0; i < cnt; i++) {
-        unsigned long long key = kNoKey;
-        if (probed) {
-            key = part[row0 + i];
-            const uint2 cs = rowstat[row0 + i];
-            ix.candidates += cs.x;
-            ix.skipped += cs.y;
-        }
-        if (follow > 0 && st.track >= 0) {                                   // (identified: the catalogue is not empty, since a load clears the track)
-            ix.followed += 1ull;
-            const long long p_exp = (long long)starts[st.track] + (long long)st.offset + (long long)g.I * ((long long)st.misses + 1ll);
-            const uint32_t* q = qwin + (size_t)(row0 + i) * (size_t)g.W;
-            for (long long p = p_exp - follow; p <= p_exp + follow; p++) {   // (uniform: every lane reaches the shuffles)
-                if (p < 0 || p > (long long)(D - g.W) || !fpm_valid(starts, T, (int)p, g.W)) continue;
-                unsigned e = 0u;
-                for (int j = lane; j < g.W; j += 64) e = fpm_errs(e, q[j], cat[(size_t)p + (size_t)j]);
-                e = fpm_group_sum<64>(e);
-                key = fpm_min(key, ((unsigned long long)e << 32) | (unsigned)p);
-            }
-        }
-        const unsigned long long e = e0 + (unsigned long long)i * (unsigned long long)g.I;
-        int track = -1, offset = 0;
-        unsigned errs = 0xffffffffu;
-        if (key != kNoKey) {
-            const int p = (int)(unsigned)key;
-            errs = (unsigned)(key >> 32);
-            track = fpm_track(starts, T, p);
-            offset = p - starts[track];
-        } else {
-            ix.empty += 1ull;
-        }
-        const bool hit = track >= 0 && errs <= g.max_errs;
-        st.queries += 1;
-        st.errs = errs;
-        if (hit) {
-            st.hits += 1;
-            if (st.track != track) { st.track = track; st.since = e; }
-            st.offset = offset;
-            st.misses = 0;
-        } else if (st.track >= 0) {
-            st.misses += 1;
-            if (st.misses == (unsigned)g.hold) { st.track = -1; st.misses = 0; }
-        }
-        st.flags = hit ? 2u : 0u;
-        if (lane == 0) {
-            fmd_fpmatch_event ev;
-            ev.end = e; ev.track = track; ev.offset = offset; ev.errs = errs; ev.flags = hit ? 1u : 0u;
-            events[(size_t)c * (size_t)events_stride + (size_t)i] = ev;
-        }
-    }
-    // the ring's newest words: of the k new ones the last min(k, W)  (k_fpmatch_gather and this kernel's follow step, the ring's and the windows' readers, are done)
-    uint32_t* ring = ring_all + (size_t)c * (size_t)g.W;
-    for (int j = (k > g.W ? k - g.W : 0) + lane; j < k; j += 64)
-        ring[(int)((before + (unsigned long long)j) % (unsigned long long)g.W)] = words[(size_t)c * (size_t)words_stride + (size_t)j];
-    if (lane == 0) {
-        st.words = before + (unsigned long long)k;
-        st.clamped += clamped ? 1ull : 0ull;
-        st.fill = st.words < (unsigned long long)g.W ? (unsigned)st.words : (unsigned)g.W;
-        st.flags = (st.flags & 2u) | (st.track >= 0 ? 1u : 0u);
-        status[c] = st;
-        istatus[c] = ix;
-        if (nevents) nevents[c] = cnt;
-        if (flags) flags[c] = (uint8_t)st.flags;
-        if (ok) ok[c] = (uint8_t)(st.flags & 1u);
-    }
+    fpm_finish(g, c, lane, n, nwords, qbase, starts, T, words, words_stride, status, ring_all, events, events_stride, nevents, flags, ok,
+               [&](int row, const fmd_fpmatch_status& st) {
+                   unsigned long long key = kNoKey;
+                   if (probed) {
+                       key = part[row];
+                       const uint2 cs = rowstat[row];
+                       ix.candidates += cs.x;
+                       ix.skipped += cs.y;
+                   }
+                   if (follow > 0 && st.track >= 0) {                        // (identified: the catalogue is not empty, since a load clears the track)
+                       ix.followed += 1ull;
+                       const long long p_exp = (long long)starts[st.track] + (long long)st.offset + (long long)g.I * ((long long)st.misses + 1ll);
+                       const uint32_t* q = qwin + (size_t)row * (size_t)g.W;
+                       for (long long p = p_exp - follow; p <= p_exp + follow; p++) {   // (uniform: every lane reaches the shuffles)
+                           if (p < 0 || p > (long long)(D - g.W) || !fpm_valid(starts, T, (int)p, g.W)) continue;
+                           unsigned e = 0u;
+                           for (int j = lane; j < g.W; j += 64) e = fpm_errs(e, q[j], cat[(size_t)p + (size_t)j]);
+                           e = fpm_group_sum<64>(e);
+                           key = fpm_min(key, ((unsigned long long)e << 32) | (unsigned)p);
+                       }
+                   }
+                   if (key == kNoKey) ix.empty += 1ull;
+                   return key;
+               });
+    if (lane == 0) istatus[c] = ix;
 }
 
 // stations c0 ... as after create
@@ -691,31 +626,29 @@ int fmd_fpmatch_process_dev(fmd_fpmatch h, const uint32_t* d_words, long long wo
     const long long rows_max = (long long)C * need;                          // the host never learns the count: launched for the most
     const long long tiles = fmd::fpmatch_tiles(h->D, W);
     const int G = (int)(tiles < h->lay.groups ? tiles : h->lay.groups);      // 0 with an empty catalogue
-    hipLaunchKernelGGL(k_fpmatch_map, dim3(1), dim3(kMapT), 0, s, h->dev, n, d_nwords, d_active, h->d_status, h->d_qbase);
+    hipLaunchKernelGGL(k_fpmatch_map, dim3(1), dim3(fmd::rowmap::kThreads), 0, s, h->dev, n, d_nwords, d_active, h->d_status, h->d_qbase);
+    // the two objects' launch conditions are not one: a catalogue shorter than a window (D > 0, G = 0) is probed and is not searched
+    const bool searched = !h->indexed && rows_max > 0 && G > 0;
+    const bool probed = h->indexed && rows_max > 0 && h->D > 0;
+    if (searched || probed)
+        hipLaunchKernelGGL(k_fpmatch_gather, dim3((unsigned)rows_max), dim3(64), 0, s, h->dev, n, d_nwords, h->d_status, h->d_qbase, h->d_ring, d_words, words_stride,
+                           h->d_qwin);
     if (h->indexed) {
-        const int probed = rows_max > 0 && h->D > 0 ? 1 : 0;
         if (probed) {
             const FpmIdxDev x{h->d_keys, h->d_pos, h->d_dir, h->ilay.dir_bits, h->icfg.max_bucket, h->ilay.chunk_words, h->icfg.follow};
-            hipLaunchKernelGGL(k_fpmatch_gather, dim3((unsigned)rows_max), dim3(64), 0, s, h->dev, n, d_nwords, h->d_status, h->d_qbase, h->d_ring, d_words, words_stride,
-                               h->d_qwin);
             hipLaunchKernelGGL(k_fpmatch_probe, dim3((unsigned)rows_max), dim3(kFpmIndexThreads), 0, s, C, W, h->d_qbase, h->d_qwin, h->d_cat, h->D, h->d_starts, h->T, x,
                                h->d_part, h->d_rowstat);
         }
-        hipLaunchKernelGGL(k_fpmatch_finish_idx, dim3((unsigned)C), dim3(64), 0, s, h->dev, n, d_nwords, d_active, h->d_qbase, h->d_part, h->d_rowstat, probed, h->d_qwin,
-                           h->d_cat, h->D, h->icfg.follow, h->d_starts, h->T, d_words, words_stride, h->d_status, h->d_istatus, h->d_ring, d_events, events_stride,
-                           d_nevents, d_flags, d_ok);
-        if (hipGetLastError() != hipSuccess) return fpm_fail(h, FMD_ERR_DEVICE, "k_fpmatch launch failed");
-        if (const char* e = h->order.end(s)) return fpm_fail(h, FMD_ERR_DEVICE, "%s", e);
-        return FMD_OK;
+        hipLaunchKernelGGL(k_fpmatch_finish_idx, dim3((unsigned)C), dim3(64), 0, s, h->dev, n, d_nwords, d_active, h->d_qbase, h->d_part, h->d_rowstat, probed ? 1 : 0,
+                           h->d_qwin, h->d_cat, h->D, h->icfg.follow, h->d_starts, h->T, d_words, words_stride, h->d_status, h->d_istatus, h->d_ring, d_events,
+                           events_stride, d_nevents, d_flags, d_ok);
+    } else {
+        if (searched)
+            hipLaunchKernelGGL(k_fpmatch_search, dim3((unsigned)((rows_max + kQR - 1) / kQR), (unsigned)G), dim3(kFpmatchThreads), sizeof(uint32_t) * (size_t)h->lay.lds_words,
+                               s, C, W, h->d_qbase, h->d_qwin, h->d_cat, h->D, h->d_starts, h->T, G, h->d_part);
+        hipLaunchKernelGGL(k_fpmatch_finish, dim3((unsigned)C), dim3(64), 0, s, h->dev, n, d_nwords, d_active, h->d_qbase, h->d_part, G, h->d_starts, h->T, d_words,
+                           words_stride, h->d_status, h->d_ring, d_events, events_stride, d_nevents, d_flags, d_ok);
     }
-    if (rows_max > 0 && G > 0) {
-        hipLaunchKernelGGL(k_fpmatch_gather, dim3((unsigned)rows_max), dim3(64), 0, s, h->dev, n, d_nwords, h->d_status, h->d_qbase, h->d_ring, d_words, words_stride,
-                           h->d_qwin);
-        hipLaunchKernelGGL(k_fpmatch_search, dim3((unsigned)((rows_max + kQR - 1) / kQR), (unsigned)G), dim3(kFpmatchThreads), sizeof(uint32_t) * (size_t)h->lay.lds_words, s,
-                           C, W, h->d_qbase, h->d_qwin, h->d_cat, h->D, h->d_starts, h->T, G, h->d_part);
-    }
-    hipLaunchKernelGGL(k_fpmatch_finish, dim3((unsigned)C), dim3(64), 0, s, h->dev, n, d_nwords, d_active, h->d_qbase, h->d_part, G, h->d_starts, h->T, d_words,
-                       words_stride, h->d_status, h->d_ring, d_events, events_stride, d_nevents, d_flags, d_ok);
     if (hipGetLastError() != hipSuccess) return fpm_fail(h, FMD_ERR_DEVICE, "k_fpmatch launch failed");
     if (const char* e = h->order.end(s)) return fpm_fail(h, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;

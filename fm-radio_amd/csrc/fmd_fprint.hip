@@ -6,7 +6,8 @@
 // against the frame before the 32-bit word.
 //
 // Three kernels a piece of a call (a call of no more than FprintLayout::piece_frames frames is one piece):
-//   k_fprint_map    one workgroup: the sub-blocks each station completes, as an exclusive prefix sum: the rows of the GEMM.
+//   k_fprint_map    one workgroup: the sub-blocks each station completes, as an exclusive prefix sum: the rows of the GEMM (the scan and
+//                   its inverse, row -> station, are fmd_rowmap.h's, shared with the matcher).
 //   k_fprint_sub    the sub-block transform of the whole batch as ONE dense GEMM on v_mfma_f32_16x16x4_f32: rows are (station, sub-block)
 //                   pairs, columns the re and the im of the Kp bins, the depth runs over n in ascending order through the accumulator
 //                   from a zero C, which is a k-ordered fmaf chain with one rounding per product.  The A operand is formed
@@ -34,6 +35,7 @@
 #include <vector>
 
 #include "fmd_fprint_design.h"
+#include "fmd_rowmap.h"
 #include "fmd_side.h"
 #include "fmdemod.h"
 
@@ -47,7 +49,6 @@ namespace {
 constexpr int kT = 256;              // threads per workgroup: four wavefronts
 constexpr int kRT = 4;               // row tiles of a workgroup of k_fprint_sub (all four wavefronts work on them)
 constexpr int kCT = 4;               // column tiles a wavefront works on
-constexpr int kMapT = 1024;
 constexpr int kSpan = kFprintChunk + 2;
 static_assert(kFprintTile == 16, "the 16x16x4 MFMA's tile");
 
@@ -65,28 +66,9 @@ __device__ __forceinline__ unsigned fp_bits(float f) { return __float_as_uint(f)
 __device__ __forceinline__ bool fp_nonfinite(float f) { return (fp_bits(f) & 0x7f800000u) == 0x7f800000u; }
 
 // rowbase [C + 1]: the exclusive prefix sum of the sub-blocks (fill + n) / H each active station completes
-__global__ __launch_bounds__(kMapT) void k_fprint_map(int C, long long n, const uint8_t* __restrict__ active, const fmd_fprint_status* __restrict__ status, int H,
-                                                     int* __restrict__ rowbase) {
-    __shared__ int part[kMapT];
-    const int tid = threadIdx.x;
-    const int per = (C + kMapT - 1) / kMapT;
-    const int c0 = min(tid * per, C), c1 = min(c0 + per, C);
-    int sum = 0;
-    for (int c = c0; c < c1; c++) sum += (active && active[c] == 0) ? 0 : (int)(((long long)status[c].fill + n) / H);
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < kMapT; d <<= 1) {
-        const int v = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - sum;
-    for (int c = c0; c < c1; c++) {
-        rowbase[c] = run;
-        run += (active && active[c] == 0) ? 0 : (int)(((long long)status[c].fill + n) / H);
-    }
-    if (tid == kMapT - 1) rowbase[C] = part[tid];
+__global__ __launch_bounds__(fmd::rowmap::kThreads) void k_fprint_map(int C, long long n, const uint8_t* __restrict__ active,
+                                                                     const fmd_fprint_status* __restrict__ status, int H, int* __restrict__ rowbase) {
+    fmd::rowmap::scan(C, [&](int c) { return (active && active[c] == 0) ? 0 : (int)(((long long)status[c].fill + n) / H); }, rowbase);
 }
 
 // in [C][in_stride] frames (L, R); carry [C][H]; img [H][2 Kp]; scratch [rows][2 Kp]
@@ -133,12 +115,7 @@ __global__ __launch_bounds__(kT) void k_fprint_sub(const float2* __restrict__ in
 #pragma unroll
     for (int i = 0; i < kRT; i++) {
         const int r = min(row0 + i * kFprintTile + col, M - 1);              // a row past the batch repeats its last
-        int lo = 0, hi = C;                                                  // the station: rowbase[c] <= r < rowbase[c + 1]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (rowbase[mid] <= r) lo = mid; else hi = mid;
-        }
-        const int c = lo, sub = r - rowbase[c];
+        const int c = fmd::rowmap::owner(rowbase, C, r), sub = r - rowbase[c];   // the station: rowbase[c] <= r < rowbase[c + 1]
         const int fill = (int)status[c].fill;
         const long long q0 = (long long)sub * g.H + kq;                      // this lane's first sample, counted from the carry's start
         fr[i] = (int)(fill - q0);                                            // samples n0 below this come from the carry
@@ -405,12 +382,11 @@ int fmd_fprint_destroy(fmd_fprint h) {
 
 int fmd_fprint_reset(fmd_fprint h, int channel) {
     if (!h) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= h->cfg.n_channels) return fpr_fail(h, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, h->cfg.n_channels);
+    int c0, cn;
+    if (!fmd::channel_range(channel, h->cfg.n_channels, &c0, &cn)) return fpr_fail(h, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, h->cfg.n_channels);
     if (!h->order.quiesce()) return fpr_fail(h, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? h->cfg.n_channels : 1;
     hipLaunchKernelGGL(k_fprint_reset, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, nullptr, c0, cn, h->d_status);
-    if (hipGetLastError() != hipSuccess) return fpr_fail(h, FMD_ERR_DEVICE, "k_fprint_reset launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return fpr_fail(h, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_fprint_reset launch failed")) return fpr_fail(h, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 
@@ -439,7 +415,7 @@ int fmd_fprint_process_f32_dev(fmd_fprint h, const float* d_in, long long in_str
         const long long np = n - at < h->lay.piece_frames ? n - at : h->lay.piece_frames;
         const float2* in = reinterpret_cast<const float2*>(d_in) + at;
         const int first = at == 0, last = at + np == n;
-        hipLaunchKernelGGL(k_fprint_map, dim3(1), dim3(kMapT), 0, s, C, np, d_active, h->d_status, H, h->d_rowbase);
+        hipLaunchKernelGGL(k_fprint_map, dim3(1), dim3(fmd::rowmap::kThreads), 0, s, C, np, d_active, h->d_status, H, h->d_rowbase);
         const long long rows_max = (long long)C * ((np + H - 1) / H);        // at most C * piece
         if (rows_max > 0)
             hipLaunchKernelGGL(k_fprint_sub, dim3((unsigned)((rows_max + kRT * kFprintTile - 1) / (kRT * kFprintTile)), (unsigned)((ntiles + per_wg - 1) / per_wg)), dim3(kT),

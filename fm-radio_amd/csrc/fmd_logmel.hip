@@ -286,12 +286,11 @@ int fmd_logmel_destroy(fmd_logmel h) {
 
 int fmd_logmel_reset(fmd_logmel h, int channel) {
     if (!h) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= h->cfg.n_channels) return lm_fail(h, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, h->cfg.n_channels);
+    int c0, cn;
+    if (!fmd::channel_range(channel, h->cfg.n_channels, &c0, &cn)) return lm_fail(h, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, h->cfg.n_channels);
     if (!h->order.quiesce()) return lm_fail(h, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? h->cfg.n_channels : 1;
     hipLaunchKernelGGL(k_logmel_reset, dim3((unsigned)((cn + 63) / 64)), dim3(64), 0, nullptr, c0, cn, h->d_status);
-    if (hipGetLastError() != hipSuccess) return lm_fail(h, FMD_ERR_DEVICE, "k_logmel_reset launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return lm_fail(h, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_logmel_reset launch failed")) return lm_fail(h, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;
 }
 

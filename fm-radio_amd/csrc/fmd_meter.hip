@@ -409,9 +409,10 @@ int fmd_meter_destroy(fmd_meter m) {
 
 int fmd_meter_reset(fmd_meter m, int channel) {
     if (!m) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= m->C) return mt_fail(m, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, m->C);
+    int first, count;
+    if (!fmd::channel_range(channel, m->C, &first, &count)) return mt_fail(m, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, m->C);
     if (!m->order.quiesce()) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
-    const size_t c0 = channel < 0 ? 0 : (size_t)channel, cn = channel < 0 ? (size_t)m->C : 1;
+    const size_t c0 = (size_t)first, cn = (size_t)count;
     if (hipMemset(m->d_status + c0, 0, sizeof(fmd_meter_status) * cn) != hipSuccess ||
         hipMemset(m->d_carry + c0 * 2 * kCarry, 0, sizeof(double) * 2 * kCarry * cn) != hipSuccess ||
         hipMemset(m->d_hist + c0 * kMeterBins, 0, sizeof(unsigned) * kMeterBins * cn) != hipSuccess ||
@@ -425,9 +426,10 @@ int fmd_meter_reset(fmd_meter m, int channel) {
 
 int fmd_meter_reset_peaks(fmd_meter m, int channel) {
     if (!m) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= m->C) return mt_fail(m, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, m->C);
+    int first, count;
+    if (!fmd::channel_range(channel, m->C, &first, &count)) return mt_fail(m, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, m->C);
     if (!m->order.quiesce()) return mt_fail(m, FMD_ERR_DEVICE, "synchronise failed");
-    const size_t c0 = channel < 0 ? 0 : (size_t)channel, cn = channel < 0 ? (size_t)m->C : 1;
+    const size_t c0 = (size_t)first, cn = (size_t)count;
     char* p = reinterpret_cast<char*>(m->d_status + c0) + offsetof(fmd_meter_status, peak_call);
     if (hipMemset2D(p, sizeof(fmd_meter_status), 0, 4 * sizeof(float), cn) != hipSuccess) return mt_fail(m, FMD_ERR_DEVICE, "memset failed");
     // tp_call and tp_hold, the record's first 16 bytes (the interpolator's history stays)

@@ -333,24 +333,22 @@ int fmd_same_destroy(fmd_same d) {
 
 int fmd_same_reset(fmd_same d, int channel) {
     if (!d) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= d->C) return sm_fail(d, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, d->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, d->C, &c0, &cn)) return sm_fail(d, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, d->C);
     if (!d->order.quiesce()) return sm_fail(d, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? d->C : 1;
     hipLaunchKernelGGL(k_same_reset, dim3((unsigned)cn), dim3(kT), 0, nullptr, c0, d->d_status);
-    if (hipGetLastError() != hipSuccess) return sm_fail(d, FMD_ERR_DEVICE, "k_same_reset launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return sm_fail(d, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_same_reset launch failed")) return sm_fail(d, FMD_ERR_DEVICE, "%s", e);
     return FMD_OK;                                                           // (the parameters are kept; with every flag clear ok = 1 whatever the mask)
 }
 
 int fmd_same_set_params(fmd_same d, int channel, const fmd_same_params* p) {
     if (!d) return FMD_ERR_ARG;
-    if (channel < -1 || channel >= d->C) return sm_fail(d, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, d->C);
+    int c0, cn;
+    if (!fmd::channel_range(channel, d->C, &c0, &cn)) return sm_fail(d, FMD_ERR_ARG, "channel %d outside [-1, %d)", channel, d->C);
     if (fmd::same_check_params(p, &d->err) != FMD_OK) return FMD_ERR_ARG;
     if (!d->order.quiesce()) return sm_fail(d, FMD_ERR_DEVICE, "synchronise failed");
-    const int c0 = channel < 0 ? 0 : channel, cn = channel < 0 ? d->C : 1;
     hipLaunchKernelGGL(k_same_set, dim3((unsigned)((cn + kT - 1) / kT)), dim3(kT), 0, nullptr, c0, cn, *p, d->d_prm, d->d_status);
-    if (hipGetLastError() != hipSuccess) return sm_fail(d, FMD_ERR_DEVICE, "k_same_set launch failed");
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return sm_fail(d, FMD_ERR_DEVICE, "synchronise failed");   // done before a later call on any stream
+    if (const char* e = fmd::control_end("k_same_set launch failed")) return sm_fail(d, FMD_ERR_DEVICE, "%s", e);
     for (int c = c0; c < c0 + cn; c++) d->params[(size_t)c] = *p;
     return FMD_OK;
 }

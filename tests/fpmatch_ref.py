@@ -240,3 +240,32 @@ def tiled_catalogue(tile: int, block: int, seed: int = 700):
     starts = np.concatenate([[0], np.cumsum([t.size for t in tracks])])
     assert starts[1] // tile != starts[3] // tile and starts[-1] - block + 1 > 3 * tile
     return tracks
+
+
+ROWMAP_STATIONS = (1, 1024, 1025, 2049)      # shares of 1, 1, 2 and 3 stations a thread of the map's 1024; the short and empty shares move
+ROWMAP_CALLS = (24, 16)                      # n of the two calls
+
+
+def rowmap_case(C: int, ends: bool):
+    """The row map's shapes on the main configuration with short tracks: (tracks, per call (words [C, n], nwords [C]), active [C]).  A
+    scattered third of the stations is left out, stations 0 and C - 1 among them or, with `ends`, both taken.  Every station has its own
+    run of 40 words and hands over an uneven number of them a call (0 ... n, both ends forced), so that in either call some active
+    stations fire no query and others several, and the second call's map reads the counts the first one wrote.  A quarter of the stations
+    play track 2 clean from their own offset and another quarter with 5 % of the bits flipped, so that there are hits to hold and lose."""
+    rng = np.random.default_rng(4000 + 2 * C + int(ends))
+    tracks = [random_words(n, 4100 + i) for i, n in enumerate((16, 23, 64))]
+    c = np.arange(C)
+    active = c % 3 != 1
+    active[[0, C - 1]] = ends
+    runs = rng.integers(0, 1 << 32, (C, sum(ROWMAP_CALLS)), dtype=np.uint64).astype(np.uint32)
+    for s in range(0, C, 2):
+        piece = tracks[2][s % 20:s % 20 + 40]
+        runs[s] = piece if s % 4 == 0 else flip(piece, 0.05, 4200 + s)
+    calls, at = [], np.zeros(C, np.int64)
+    for n in ROWMAP_CALLS:
+        k = rng.integers(0, n + 1, C)
+        k[c % 7 == 2] = 0
+        k[c % 7 == 4] = n
+        calls.append((np.take_along_axis(runs, at[:, None] + np.arange(n)[None, :], axis=1), k.astype(np.int32)))
+        at += k
+    return tracks, calls, active

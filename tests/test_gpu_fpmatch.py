@@ -1,7 +1,8 @@
 """Fingerprint matcher on the GPU (fmd_fpmatch_*, FingerprintMatcher): events, counts, bytes and status records against the numpy
 restatement of the definition (tests/fpmatch_ref.py, itself checked in test_fpmatch_cpu.py), bit for bit: the whole stream in one call, a
 call per word, ragged calls on alternating streams, n_bits 32 and 9, the default W = 256 / I = 64, a catalogue across several column tiles
-with a duplicated track, more column tiles than column groups, n = 0, a batch of one, row 69 of 70, the `active` mask over pre-filled
+with a duplicated track, more column tiles than column groups, n = 0, a batch of one, row 69 of 70, the row map of 1 to 2049 stations
+with uneven counts, the `active` mask over pre-filled
 outputs, d_nwords NULL and clamped, NULL counts and bytes, the smallest events_stride, load and reset in mid-stream, argument errors, the
 C++ adaptor, and demodulator -> Fingerprinter -> FingerprintMatcher end to end.
 
@@ -215,6 +216,52 @@ def test_row_69_of_70(pkg):
         assert pkg.FingerprintMatcher.events_of(ev, k, c).tobytes() == want[c % 3].tobytes(), c
         assert st[c].tobytes() == ref3.status()[c % 3].tobytes() and int(fl[c]) == int(st[c]["flags"]) and int(ok[c]) == int(st[c]["flags"]) & 1, c
     m.close(); m3.close()
+
+
+def _rowmap(pkg, m, ref, C, ends, records):
+    """R.rowmap_case through the object and the restatement: every station's events, count and bytes of both calls (an inactive station's
+    are left as they were filled), and records(m, ref) behind each call"""
+    import torch
+    tracks, calls, active = R.rowmap_case(C, ends)
+    m.load(tracks)
+    assert ref.load(tracks)
+    ad = torch.from_numpy(active.astype(np.uint8)).cuda()
+    fired = []
+    for i, (words, k) in enumerate(calls):
+        n = words.shape[1]
+        rows = pkg.fpmatch_max_events(m.interval, n)
+        ev = torch.full((C, rows, 3), 0x5A5A5A5A5A5A5A5A, dtype=torch.int64, device="cuda")
+        cnt = torch.full((C,), -7, dtype=torch.int32, device="cuda")
+        fl, ok = torch.full((C,), 0xEE, dtype=torch.uint8, device="cuda"), torch.full((C,), 0xDD, dtype=torch.uint8, device="cuda")
+        m.process(torch.from_numpy(words.view(np.int32)).cuda(), nwords=torch.from_numpy(k).cuda(), active=ad, events=ev, nevents=cnt, flags=fl, ok=ok)
+        wev, wfl, wok = ref.process(words, nwords=k, n=n, active=active)
+        raw = ev.cpu().numpy()
+        got = raw.reshape(C, rows * 3).view(R.EVENT_DTYPE)
+        cnt, fl, ok = cnt.cpu().numpy(), fl.cpu().numpy(), ok.cpu().numpy()
+        for c in range(C):
+            if not active[c]:
+                assert wev[c] is None and (cnt[c], fl[c], ok[c]) == (-7, 0xEE, 0xDD) and (raw[c] == 0x5A5A5A5A5A5A5A5A).all(), (i, c)
+                continue
+            assert cnt[c] == wev[c].size and got[c, :cnt[c]].tobytes() == wev[c].tobytes() and (raw[c, cnt[c]:] == 0x5A5A5A5A5A5A5A5A).all(), (i, c, got[c], wev[c])
+            assert (fl[c], ok[c]) == (wfl[c], wok[c]), (i, c)
+        records(m, ref)
+        fired.append(np.array([-1 if e is None else e.size for e in wev]))
+    if C > 1:                                                                # in either call stations of no row and of several; hits, and tracks held
+        assert all((f == 0).any() and (f >= 2).any() for f in fired) and ref.status()["hits"].sum() > C // 8 and (ref.status()["track"] >= 0).any()
+
+
+def _same_status(m, ref):
+    assert m.status().tobytes() == ref.status().tobytes()
+
+
+@pytest.mark.parametrize("ends", [True, False], ids=["ends_taken", "ends_left_out"])
+@pytest.mark.parametrize("C", R.ROWMAP_STATIONS)
+def test_row_map_of_many_stations(pkg, C, ends):
+    """1, 1024, 1025 and 2049 stations (a thread of k_fpmatch_map takes 1, 1, 2 and 3 of them; the short and the empty shares fall on
+    other threads), a scattered third inactive, uneven d_nwords, two calls: every station's outputs and record, bit for bit"""
+    m, ref = _pair(pkg, dict(R.MAIN, n_channels=C), None)
+    _rowmap(pkg, m, ref, C, ends, _same_status)
+    m.close()
 
 
 def test_active_mask_over_prefilled_outputs(pkg):

@@ -11,7 +11,7 @@ import pytest
 
 import fpmatch_index_ref as X
 import fpmatch_ref as R
-from test_gpu_fpmatch import RAGGED, _cuda, _fm, _i32, _same_call
+from test_gpu_fpmatch import RAGGED, _cuda, _fm, _i32, _rowmap, _same_call
 
 pytestmark = pytest.mark.gpu
 ROOT = Path(__file__).resolve().parent.parent
@@ -113,6 +113,17 @@ def test_ragged_calls_on_alternating_streams(pkg, n_bits, K, d):
     """1 + 3 + 4 + 5 + 15 + 16 + 17 + the rest, every other call on another stream, the records checked after every call"""
     m, ref, words = _main(pkg, n_bits, K, d)
     _both(pkg, m, ref, words, cuts=list(np.cumsum(RAGGED)), each=True, alternate=True)
+    m.close()
+
+
+@pytest.mark.parametrize("ends", [True, False], ids=["ends_taken", "ends_left_out"])
+@pytest.mark.parametrize("C", R.ROWMAP_STATIONS)
+def test_row_map_of_many_stations(pkg, C, ends):
+    """test_gpu_fpmatch.py's row map shapes through the indexed object (the default index: K = 8, d = 2): every station's outputs, record
+    and index record, bit for bit"""
+    m, ref = _pair(pkg, dict(R.MAIN, n_channels=C), None, None)
+    _rowmap(pkg, m, ref, C, ends, _same_records)
+    assert C == 1 or ref.index_status()["followed"].sum() > 0
     m.close()
 
 

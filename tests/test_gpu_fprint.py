@@ -1,6 +1,7 @@
 """Audio fingerprinter on the GPU (fmd_fprint_*, Fingerprinter): words, counts, energies and status records against the C restatement of
 the arithmetic contract (tests/cpp/fprint_ref.c, itself checked in test_fprint_cpu.py), bit for bit, compared as integer views: one call,
 a call per hop, ragged calls on alternating streams, R = 4, 8 and 32, the default geometry at 32 kHz, n = 0, batch and row invariance, the
+row map of 1 to 2049 stations at different fills, the
 `active` mask over pre-filled outputs, NULL counts and energies, the smallest out_stride, odd strides and views, inf / NaN / denormal
 samples, resets, the device's records, argument errors, the C++ adaptor, and demodulator -> Fingerprinter end to end.
 
@@ -265,6 +266,59 @@ def test_active_mask_null_counts_and_out_stride(pkg, ref, streams, want_main):
         assert e.value.status == -1 and m.status().tobytes() == st.tobytes()
     with pytest.raises(ValueError):
         m.process(xd, out=torch.zeros((3, rows_max - 1), dtype=torch.int32, device="cuda"))
+    m.close()
+
+
+ROWMAP_CALLS = (7, 73)       # frames of the two calls under test, behind a first call of ROWMAP_PRE frames that every other station takes
+ROWMAP_PRE = 91
+
+
+@pytest.mark.parametrize("ends", [True, False], ids=["ends_taken", "ends_left_out"])
+@pytest.mark.parametrize("C", [1, 1024, 1025, 2049])
+def test_row_map_of_many_stations(pkg, ref, C, ends):
+    """1, 1024, 1025 and 2049 stations (a thread of k_fprint_map takes 1, 1, 2 and 3 of them; the short and the empty shares fall on
+    other threads) at the main shape.  A first call of 91 frames under a mask of its own (every other station) leaves the stations at
+    fill 11 or 0; then two calls of 7 and 73 frames under a mask that leaves out a scattered third, stations 0 and C - 1 among them or,
+    with `ends`, both taken.  A call has one n, so its stations' rows differ by one at most: the call of 7 frames completes 1 sub-block
+    (fill 11) or none (fill 0), the call of 73 then 4 (fill 2) or 5 (fill 7), from the fills the call before wrote.  Every station's words,
+    count and energies of both calls and its record behind each, bit for bit; an inactive station's are left as they were filled."""
+    import torch
+    rng = np.random.default_rng(5000 + 2 * C + int(ends))
+    x = (rng.standard_normal((C, ROWMAP_PRE + sum(ROWMAP_CALLS), 2)) * rng.uniform(0.05, 2.0, (C, 1, 1))).astype(np.float32)
+    c = np.arange(C)
+    first = c % 2 == 0
+    active = c % 3 != 1
+    active[[0, C - 1]] = ends
+    cfg = fprint_ref.config(**MAIN)
+    chans = [ref.channel(cfg) for _ in range(C)]
+    m = pkg.Fingerprinter(C, FS, **{k: v for k, v in MAIN.items() if k != "fs"})
+    xd = _cuda(x)
+    m.process(xd[:, :ROWMAP_PRE], active=_cuda(first.astype(np.uint8)), nprints=False)
+    for s in np.flatnonzero(first):
+        chans[s].process(x[s, :ROWMAP_PRE])
+    assert m.status().tobytes() == np.concatenate([ch.status() for ch in chans]).tobytes()
+    PAT, at, ad = 0x7FC0BEEF, ROWMAP_PRE, _cuda(active.astype(np.uint8))
+    for n, subs in zip(ROWMAP_CALLS, ((1, 0), (4, 5))):
+        fill = m.status()["fill"].astype(np.int64)
+        assert C == 1 or set(((fill[active] + n) // 16).tolist()) == set(subs)
+        rows = pkg.fprint_max_prints(16, n)
+        out = torch.full((C, rows), PAT, dtype=torch.int32, device="cuda")
+        en = torch.zeros((C, rows, 9), device="cuda")
+        en.view(torch.int32).fill_(PAT)
+        cnt = torch.full((C,), -7, dtype=torch.int32, device="cuda")
+        m.process(xd[:, at:at + n], active=ad, out=out, nprints=cnt, energy=en)
+        o, k, e = _u32(out), cnt.cpu().numpy(), bits(en.cpu().numpy())
+        for s in range(C):
+            if not active[s]:
+                assert k[s] == -7 and (o[s] == PAT).all() and (e[s] == PAT).all(), (n, s)
+                continue
+            w, we = chans[s].process(x[s, at:at + n])
+            assert k[s] == w.shape[0] and np.array_equal(o[s, :k[s]], w) and np.array_equal(e[s, :k[s]], bits(we)), (n, s)
+            assert (o[s, k[s]:] == PAT).all() and (e[s, k[s]:] == PAT).all(), (n, s)
+        assert m.status().tobytes() == np.concatenate([ch.status() for ch in chans]).tobytes(), n
+        at += n
+    st = m.status()
+    assert C == 1 or (set(st["prints"][active & first].tolist()), set(st["prints"][active & ~first].tolist())) == ({6}, {1})
     m.close()
 
 
