@@ -476,6 +476,7 @@ def load_library():
     L.fmd_chan_reset.argtypes = [C.c_void_p]
     L.fmd_chan_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_int)] * 4
     L.fmd_chan_get_taps.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t]
+    L.fmd_chan_kernel_form.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     for fmt in ("cf32", "u8", "s8", "s16"):
         getattr(L, f"fmd_chan_process_{fmt}_dev").argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.c_void_p]
     L.fmd_scan_default_nfft.restype = C.c_int
@@ -1249,6 +1250,9 @@ def chan_default_taps(fs_in: float, fs_out: float = 256_000.0) -> int:
     return t
 
 
+CHAN_FORMS = ("k_channelize", "k_channelize16", "k_channelize16_mfma", "k_channelize_band_mfma")     # by FMD_CHAN_FORM_*
+
+
 class Channelizer(_Handle):
     """Wideband capture (cf32, u8, s8 or s16) -> [C][n_out] cf32 stations at fs_out on the GPU (fmd_chan_*); feeds BatchDemod.process directly.
 
@@ -1256,7 +1260,8 @@ class Channelizer(_Handle):
     the whole FM band in one capture), with 4 to 4096 taps per phase; taps_per_phase=0 takes chan_default_taps(fs_in, fs_out).  Kernels:
     10 MSa/s -> 256 kSa/s with 640 taps per phase on the matrix cores (k_channelize16_mfma); the whole-band pairs with L dividing 16
     (16, 20, 20.48, 24, 30.72, 32, 32.768 MSa/s) on the matrix cores too (k_channelize_band_mfma); every other pair on the vector ALUs.
-    A station's output does not depend on its row or on the number of stations."""
+    A station's output does not depend on its row or on the number of stations.  `form` names the kernel that serves the handle (one of
+    CHAN_FORMS) and `tile_outputs` the outputs a workgroup of it takes per tile (fmd_chan_kernel_form)."""
     _prefix = "fmd_chan"
 
     def __init__(self, fs_in: float, center_hz, fs_out: float = 256_000.0, max_input_samples: int = 640_000, taps_per_phase: int = 0, device: int = -1):
@@ -1266,6 +1271,10 @@ class Channelizer(_Handle):
         l, m, t, c = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         self.L.fmd_chan_info(self.h, C.byref(l), C.byref(m), C.byref(t), C.byref(c))
         self.interp, self.decim, self.taps_per_phase, self.n_stations = l.value, m.value, t.value, c.value
+        f, to = C.c_int(), C.c_int()
+        self._check(self.L.fmd_chan_kernel_form(self.h, C.byref(f), C.byref(to)))
+        # which kernel serves process() (CHAN_FORMS: fixed at create) and the consecutive outputs one of its workgroups takes per tile
+        self.form, self.tile_outputs = CHAN_FORMS[f.value], to.value
 
     def taps(self) -> np.ndarray:
         a = np.empty((self.taps_per_phase, self.interp), np.float32)

@@ -391,6 +391,16 @@ int fmd_chan_destroy(fmd_channelizer h);
 int fmd_chan_reset(fmd_channelizer h);
 int fmd_chan_info(fmd_channelizer h, int* L, int* M, int* taps_per_phase, int* n_stations);
 int fmd_chan_get_taps(fmd_channelizer h, float* taps, size_t cap_floats);
+/* host-only: which kernel serves this handle's process calls (fixed at create by the rate pair and the taps per phase) and how many
+ * consecutive outputs one of its workgroups takes per tile (128; 64, 32 or 16 for the general kernel at the whole-band rates; 16 G for
+ * the band form's G = 8, 4 or 2 groups).  Either pointer may be NULL.  Diagnostic: results do not depend on the caller knowing it. */
+enum {
+    FMD_CHAN_FORM_GENERAL = 0,       /* k_channelize: one output per thread, any L <= 64 */
+    FMD_CHAN_FORM_VALU16 = 1,        /* k_channelize16: L = 16 on the vector ALUs, taps per phase a multiple of 64 up to 1024 that the next form cannot hold */
+    FMD_CHAN_FORM_MFMA16 = 2,        /* k_channelize16_mfma: L = 16 on the matrix cores, floor(15 M / 16) + taps per phase <= 1232 */
+    FMD_CHAN_FORM_BAND = 3           /* k_channelize_band_mfma: the whole-band pairs with L dividing 16 */
+};
+int fmd_chan_kernel_form(fmd_channelizer h, int* form, int* tile_outputs);
 /* d_wide: [n_in][2] cf32 on the device; n_in * L must be a multiple of M (625 input samples per 16 outputs at 10 M -> 256 k).
  * d_out: [n_stations][out_capacity_per_station][2] cf32 on the device — station k's *n_out samples start at row k (row
  * stride = out_capacity_per_station; pass the exact n_out to get the dense [C][n_out] layout fmd_process_cf32_dev takes).

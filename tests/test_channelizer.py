@@ -13,6 +13,9 @@ import synth
 from rds_groups import decode_groups
 
 FS_IN, FS_OUT = 10_000_000.0, 256_000.0
+# white noise against the float64 definition, max|y - ref| / max|ref| over the whole output: twice the worst figure measured on an MI355X
+# over this file's four cases (2.70e-6, the 640-tap matrix-core case; DESIGN.md §6 "Tap placement"), in place of the 2e-5 the tests had
+NOISE_BAR = 5.4e-6
 
 
 @pytest.fixture(scope="module")
@@ -66,10 +69,13 @@ def test_kernel_matches_float64_definition_and_streams(pkg):
     y = ch.process(xt).cpu().numpy()
     y = y[..., 0] + 1j * y[..., 1]
     assert y.shape == (6, 1536)
+    assert (ch.form, ch.tile_outputs) == ("k_channelize16_mfma", 128)
+    worst = 0.0
     for k, f in enumerate(centers):
         ref = ref_channelize(x, f, taps, ch.interp, ch.decim)
-        err = np.abs(y[k] - ref).max() / np.abs(ref).max()
-        assert err < 2e-5, (k, err)
+        worst = max(worst, float(np.abs(y[k] - ref).max() / np.abs(ref).max()))
+    print(f"k_channelize16_mfma, T = 640: max|y - ref| / max|ref| = {worst:.2e}")
+    assert worst < NOISE_BAR, worst
     # streaming: the same capture in three unequal calls gives the same samples (history + mixer phase carry over)
     ch.reset()
     parts = [625 * 20, 625 * 33, 625 * 43]
@@ -79,7 +85,7 @@ def test_kernel_matches_float64_definition_and_streams(pkg):
         pos += n
     y2 = np.concatenate(outs, axis=1)
     y2 = y2[..., 0] + 1j * y2[..., 1]
-    assert np.abs(y2 - y).max() <= 5e-6 * np.abs(y).max()    # (the mixer's phasor is re-seeded exactly per tile and advanced by recurrence: < 2e-6 of drift)
+    assert np.abs(y2 - y).max() <= 5e-6 * np.abs(y).max()    # (the mixer's phasor is re-seeded exactly per tile and advanced by recurrence: up to 4.5e-6 of drift on one sample, far less on a sum over 640)
     with pytest.raises(Exception):
         ch.process(xt[:1000].contiguous())               # 1000 inputs is not a whole number of outputs
     # the shortest legal calls, 625 inputs -> 16 outputs: shorter than the 639-sample history (the history hand-over
@@ -107,10 +113,12 @@ def test_kernel_matches_float64_definition_and_streams(pkg):
 
 
 @pytest_gpu
-@pytest.mark.parametrize("fs_out,tpp,form", [(256e3, 512, "16 branches on the VALU (k_channelize16)"), (200e3, 128, "one output per thread (k_channelize)")])
+@pytest.mark.parametrize("fs_out,tpp,form", [(256e3, 768, "16 branches on the VALU (k_channelize16)"), (200e3, 128, "one output per thread (k_channelize)"),
+                                             (256e3, 512, "16 branches on the matrix cores (k_channelize16_mfma)")])
 def test_the_other_kernel_forms_match_the_float64_definition(pkg, fs_out, tpp, form):
-    """The default configuration (16 / 625, 640 taps per phase) runs k_channelize16_mfma; other tap counts and rate pairs keep the
-    VALU forms.  Same check as above, incl. a call that ends in a partial tile."""
+    """The default configuration (16 / 625, 640 taps per phase) runs k_channelize16_mfma, and so does every tap count up to 644 (512
+    here); 704 to 1024 taps per phase in multiples of 64 run 16 branches on the VALU (k_channelize16), other rate pairs one output per
+    thread (k_channelize).  Same check as above, incl. a call that ends in a partial tile; each case asserts the form it runs."""
     import torch
     rng = np.random.default_rng(4)
     taps, L, M = pkg.chan_design(FS_IN, fs_out, tpp)
@@ -119,14 +127,17 @@ def test_the_other_kernel_forms_match_the_float64_definition(pkg, fs_out, tpp, f
     centers = np.array([-3.1e6, 0.0, 2.2e6])
     ch = pkg.Channelizer(FS_IN, centers, fs_out=fs_out, max_input_samples=n_in, taps_per_phase=tpp)
     assert (ch.interp, ch.decim) == (L, M)
+    assert f"({ch.form})" in form and ch.tile_outputs == 128, (form, ch.form)
     xt = torch.from_numpy(np.ascontiguousarray(x).view(np.float32).reshape(-1, 2)).cuda()
     y = ch.process(xt).cpu().numpy()
     y = y[..., 0] + 1j * y[..., 1]
+    worst = 0.0
     for k, f in enumerate(centers):
         ref = ref_channelize(x, f, ch.taps(), L, M)
         assert y.shape[1] == ref.size
-        err = np.abs(y[k] - ref).max() / np.abs(ref).max()
-        assert err < 2e-5, (form, k, err)
+        worst = max(worst, float(np.abs(y[k] - ref).max() / np.abs(ref).max()))
+    print(f"{form}, T = {tpp}: max|y - ref| / max|ref| = {worst:.2e}")
+    assert worst < NOISE_BAR, (form, worst)
     # streamed (only the matrix-core form had its history hand-over checked across calls): the same capture in several
     # calls — uneven ones, and then the SHORTEST legal calls (one M-sample step of the rate pair, shorter than the T - 1 samples of
     # history, so a call's window lies in the history buffer and the block at once) — must give the one-shot result

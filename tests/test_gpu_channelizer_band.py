@@ -1,9 +1,11 @@
 """Whole-band channeliser on the GPU: capture rates of 16 - 32.768 MSa/s -> 256 kSa/s stations (the whole FM band in one capture).
 Same definition as tests/test_channelizer.py, same float64 restatement as the oracle.  Which kernel serves a configuration:
   * L dividing 16 and the band form's tile within its LDS budget (16, 20, 20.48, 24, 30.72, 32, 32.768 MSa/s with the default taps):
-    k_channelize_band_mfma, on the matrix cores;
+    k_channelize_band_mfma, on the matrix cores, with a tile of G = 8 or 4 groups of 16 outputs (G = 2 with 3000 taps per phase at
+    32.768 MSa/s);
   * every other pair beyond the 128-output window (25 MSa/s: L = 32; 20 MSa/s with 4096 taps per phase, whose prototype would not fit the
     band form's LDS): k_channelize with a tile of fewer outputs.
+Every case asserts the form its handle reports (Channelizer.form, Channelizer.tile_outputs).
 """
 import os
 
@@ -30,7 +32,14 @@ RATES = {
 FORMS = [(f, 0, "k_channelize_band_mfma") for f in RATES if f != 25e6] + [
     (25e6, 0, "k_channelize, tile of 32"),
     (20e6, 4096, "k_channelize, tile of 32 (L = 8 divides 16; the 128 KB prototype exceeds the band form's LDS)"),
+    (32.768e6, 3000, "k_channelize_band_mfma"),          # G = 2: the 3000-tap prototype leaves room for two groups' rails
 ]
+# (fs_in, taps per phase) -> Channelizer.tile_outputs: the band form's 16 G (G = 8, 4 or 2 groups), k_channelize's tile
+TILES = {(16e6, 0): 128, (20.48e6, 0): 128, (20e6, 0): 64, (24e6, 0): 64, (30.72e6, 0): 64, (32e6, 0): 64, (32.768e6, 0): 64,
+         (32.768e6, 3000): 32, (25e6, 0): 32, (20e6, 4096): 32}
+# white noise against the float64 definition, max|y - ref| / max|ref| over the whole output: twice the worst figure measured on an MI355X
+# over FORMS (2.41e-6, at 20.48 MSa/s; DESIGN.md §6 "Tap placement"), in place of the 2e-5 the test had
+NOISE_BAR = 4.9e-6
 
 pytestmark = pytest.mark.gpu
 
@@ -81,6 +90,8 @@ def test_matches_the_float64_definition(pkg, fs_in, tpp, form):
     x = _input(rng, n_in)
     centers = np.linspace(-0.45, 0.45, 6) * fs_in + 1234.5
     ch = pkg.Channelizer(fs_in, centers, max_input_samples=n_in, taps_per_phase=tpp)
+    assert form.startswith(ch.form + ",") or form == ch.form, (form, ch.form)
+    assert ch.tile_outputs == TILES[fs_in, tpp], form
     y = _cf(ch.process(_dev(torch, x)))
     assert y.shape == (6, n_out)
     taps = ch.taps()
@@ -89,7 +100,7 @@ def test_matches_the_float64_definition(pkg, fs_in, tpp, form):
         ref = ref_channelize(x, f, taps, L, M, fs_in=fs_in)
         worst = max(worst, float(np.abs(y[k] - ref).max() / np.abs(ref).max()))
     print(f"{fs_in / 1e6} MSa/s, T = {ch.taps_per_phase}, {form}: max|y - ref| / max|ref| = {worst:.2e}")
-    assert worst < 2e-5, (form, worst)
+    assert worst < NOISE_BAR, (form, worst)
     ch.close()
 
 

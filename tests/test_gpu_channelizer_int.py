@@ -7,6 +7,7 @@ the input into calls, in any mix of formats.  Which configuration selects which 
   * 2.4 MSa/s (L / M = 8 / 75, the RTL-SDR rate): k_channelize;
   * 20.48 and 20 MSa/s: k_channelize_band_mfma with tiles of 8 and 4 groups;
   * 25 MSa/s (L = 32): k_channelize with a tile of 32 outputs.
+Every case asserts the form its handle reports (Channelizer.form, Channelizer.tile_outputs).
 """
 import os
 
@@ -30,6 +31,13 @@ FORMS = [
     (25e6, 0, 32, 3125, "k_channelize, tile of 32"),
 ]
 IDS = [f[4] for f in FORMS]
+# what Channelizer.form and Channelizer.tile_outputs must say for each label
+KERNELS = {"k_channelize16_mfma": ("k_channelize16_mfma", 128), "k_channelize16": ("k_channelize16", 128), "k_channelize": ("k_channelize", 128),
+           "k_channelize_band_mfma, G = 8": ("k_channelize_band_mfma", 128), "k_channelize_band_mfma, G = 4": ("k_channelize_band_mfma", 64),
+           "k_channelize, tile of 32": ("k_channelize", 32)}
+# integer captures against the float64 definition, max|y - ref| / max|ref| over the whole output: twice the worst figure measured on an
+# MI355X over FORMS x FORMATS (3.06e-6, s16 on k_channelize16_mfma; DESIGN.md §6 "Tap placement"), in place of the 2e-5 the test had
+NOISE_BAR = 6.2e-6
 FORMATS = ("u8", "s8", "s16")
 LIMITS = {"u8": (0, 255, np.uint8), "s8": (-128, 127, np.int8), "s16": (-32768, 32767, np.int16)}
 
@@ -79,6 +87,7 @@ def test_integer_input_is_bit_identical_to_its_cf32_conversion(pkg, fs_in, tpp, 
     centers = np.linspace(-0.45, 0.45, 6) * fs_in + 1234.5
     ch = pkg.Channelizer(fs_in, centers, max_input_samples=n_in, taps_per_phase=tpp)
     assert (ch.interp, ch.decim) == (L, M)
+    assert (ch.form, ch.tile_outputs) == KERNELS[form]
     for fmt in FORMATS:
         a = _capture(rng, fmt, n_in)
         ch.reset()
@@ -99,6 +108,7 @@ def test_integer_input_matches_the_float64_definition(pkg, fs_in, tpp, L, M, for
     n_out, n_in = _sizes(L, M)
     centers = np.linspace(-0.45, 0.45, 6) * fs_in + 1234.5
     ch = pkg.Channelizer(fs_in, centers, max_input_samples=n_in, taps_per_phase=tpp)
+    assert (ch.form, ch.tile_outputs) == KERNELS[form]
     taps = ch.taps()
     for fmt in FORMATS:
         a = _capture(rng, fmt, n_in)
@@ -111,7 +121,7 @@ def test_integer_input_matches_the_float64_definition(pkg, fs_in, tpp, L, M, for
             ref = ref_channelize(x, f, taps, L, M, fs_in=fs_in)
             worst = max(worst, float(np.abs(y[k] - ref).max() / np.abs(ref).max()))
         print(f"{form}, {fmt}: max|y - ref| / max|ref| = {worst:.2e}")
-        assert worst < 2e-5, (form, fmt, worst)
+        assert worst < NOISE_BAR, (form, fmt, worst)
     ch.close()
 
 
@@ -129,7 +139,7 @@ def test_streamed_calls_in_alternating_formats_over_two_streams(pkg, fs_in, tpp,
     units = [3, 1, 70, 1, 1, 5, 2, 1, 190, 4, 1, 6]
     n_in = unit * sum(units)
     ch = pkg.Channelizer(fs_in, np.array([-0.41, -0.1, 0.0, 0.07, 0.33, 0.449]) * fs_in, max_input_samples=n_in, taps_per_phase=tpp)
-    assert unit < ch.taps_per_phase - 1
+    assert unit < ch.taps_per_phase - 1 and (ch.form, ch.tile_outputs) == KERNELS[form]
     order = ("u8", "cf32", "s16", "s8")
     pieces, conv = [], []                                 # (format, device tensor) and the piece as cf32
     for i, nu in enumerate(units):
