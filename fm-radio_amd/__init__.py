@@ -25,6 +25,7 @@ from .capi import (  # noqa: F401
     Fingerprinter, FPRINT_STATUS_DTYPE, FprintConfig, FprintDesign, fprint_ber, fprint_default_config, fprint_design, fprint_match, fprint_max_prints, fprint_state_bytes,
     FingerprintMatcher, FPMATCH_STATUS_DTYPE, FPMATCH_EVENT_DTYPE, FpmatchConfig, FpmatchDesign, fpmatch_check_catalogue, fpmatch_default_config, fpmatch_design, fpmatch_max_errs, fpmatch_max_events, fpmatch_state_bytes,
     FPMATCH_INDEX_STATUS_DTYPE, FpmatchIndexConfig, FpmatchIndexDesign, fpmatch_index_build, fpmatch_index_default_config, fpmatch_index_design, fpmatch_index_state_bytes,
+    Limiter, LIMITER_STATUS_DTYPE, LimiterConfig, LimiterDesign, limiter_default_config, limiter_design, limiter_gain_for_loudness,
     SameDecoder, SAME_STATUS_DTYPE, SAME_MESSAGE_DTYPE, SAME_SYNCED, SAME_ALERT_OPEN, SAME_KIND_HEADER, SAME_KIND_EOM, SAME_RING, SameConfig, SameParams, SameHeader, SameEncodeConfig,
     SAME_VALID_ORG, SAME_VALID_EVENT, SAME_VALID_LOCATIONS, SAME_VALID_DURATION, SAME_VALID_TIME, SAME_VALID_CALLSIGN, same_default_params, same_encode, same_parse, same_vote,
     AudioMonitor, AUDMON_STATUS_DTYPE, AudmonConfig, AudmonParams, AUDMON_SILENCE, AUDMON_LEFT_LOST, AUDMON_RIGHT_LOST, AUDMON_ANTIPHASE, AUDMON_MONO, audmon_balance_db, audmon_correlation, audmon_default_params, audmon_level_db, audmon_side_mid_db,

@@ -243,6 +243,23 @@ ADPCM_DEFAULT_BLOCK_FRAMES = 1017
 ADPCM_WAV_HEADER_BYTES = 60
 
 
+class LimiterConfig(C.Structure):
+    """include/fmdemod.h fmd_limiter_config"""
+    _fields_ = [("n_channels", C.c_int), ("fs", C.c_int), ("lookahead_ms", C.c_double), ("release_ms", C.c_double), ("ceiling_db", C.c_double),
+                ("max_input_frames", C.c_longlong), ("device", C.c_int)]
+
+
+class LimiterDesign(C.Structure):
+    """include/fmdemod.h fmd_limiter_design_t"""
+    _fields_ = [("lookahead_frames", C.c_int), ("step", C.c_uint), ("ceiling", C.c_float), ("latency_frames", C.c_int)]
+
+
+# include/fmdemod.h fmd_limiter_status (64 bytes)
+LIMITER_STATUS_DTYPE = np.dtype([("frames", "<u8"), ("limited", "<u8"), ("clamped", "<u8", (2,)), ("nonfinite", "<u8"), ("min_gain", "<f4"), ("gain", "<f4"),
+                                 ("eq", "<u4"), ("reserved", "u1", (12,))])
+assert LIMITER_STATUS_DTYPE.itemsize == 64
+
+
 class FlacConfig(C.Structure):
     _fields_ = [("n_channels", C.c_int), ("block_frames", C.c_int), ("sample_rate", C.c_int), ("max_input_frames", C.c_longlong), ("device", C.c_int)]
 
@@ -579,6 +596,16 @@ def load_library():
     L.fmd_adpcm_create.argtypes = [C.POINTER(AdpcmConfig), C.POINTER(C.c_void_p)]
     L.fmd_adpcm_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
     L.fmd_adpcm_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_limiter_design.argtypes = [C.c_int, C.c_double, C.c_double, C.c_double, C.POINTER(LimiterDesign)]
+    L.fmd_limiter_default_config.argtypes = [C.c_int, C.POINTER(LimiterConfig)]
+    L.fmd_limiter_gain_for_loudness.argtypes = [C.c_double, C.c_double]
+    L.fmd_limiter_gain_for_loudness.restype = C.c_float
+    L.fmd_limiter_create.argtypes = [C.POINTER(LimiterConfig), C.POINTER(C.c_void_p)]
+    L.fmd_limiter_set_gain.argtypes = [C.c_void_p, C.c_int, C.c_float]
+    L.fmd_limiter_get_gain.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_float)]
+    L.fmd_limiter_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_limiter_flush.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
+    L.fmd_limiter_debug_set_frames.argtypes = [C.c_void_p, C.c_int, C.c_ulonglong]
     L.fmd_flac_frame_bound.argtypes = [C.c_int]
     L.fmd_flac_max_bytes.argtypes = [C.c_int, C.c_longlong]
     L.fmd_flac_max_bytes.restype = C.c_longlong
@@ -638,13 +665,13 @@ def load_library():
     L.fmd_same_get_params.argtypes = [C.c_void_p, C.c_int, C.POINTER(SameParams)]
     L.fmd_same_process_f32_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_longlong, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     # what every side object declares alike
-    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "fprint", "fpmatch", "rdsdec"):
+    for pre in ("chan", "scan", "iqcorr", "resampler", "mixer", "meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "fprint", "fpmatch", "limiter", "rdsdec"):
         getattr(L, f"fmd_{pre}_destroy").argtypes = [C.c_void_p]
         getattr(L, f"fmd_{pre}_last_error").restype = C.c_char_p
         getattr(L, f"fmd_{pre}_last_error").argtypes = [C.c_void_p]
-    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "fprint", "fpmatch"):
+    for pre in ("meter", "modmon", "squelch", "audmon", "tonedet", "adpcm", "same", "flac", "logmel", "fprint", "fpmatch", "limiter"):
         getattr(L, f"fmd_{pre}_reset").argtypes = [C.c_void_p, C.c_int]
-        if pre not in ("tonedet", "adpcm", "same", "flac", "logmel", "fprint", "fpmatch"):   # (the tone detector, the encoders, the SAME decoder, the log-mel front end, the fingerprinter and the matcher hold no peaks)
+        if pre not in ("tonedet", "adpcm", "same", "flac", "logmel", "fprint", "fpmatch", "limiter"):   # (the tone detector, the encoders, the SAME decoder, the log-mel front end, the fingerprinter, the matcher and the limiter hold no peaks)
             getattr(L, f"fmd_{pre}_reset_peaks").argtypes = [C.c_void_p, C.c_int]
         getattr(L, f"fmd_{pre}_get_status").argtypes = [C.c_void_p, C.c_void_p]
         getattr(L, f"fmd_{pre}_status_dev").argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
@@ -2813,3 +2840,126 @@ class FingerprintMatcher(_Monitor):
         self._check(self.L.fmd_fpmatch_process_dev(self.g, C.c_void_p(words.data_ptr()), wstride, pw, n, pa, C.c_void_p(events.data_ptr()), estride, pn, pf, po,
                                                    C.c_void_p(stream)))
         return events, (None if nevents is False else nevents), flags, ok
+
+
+def limiter_design(fs: int, lookahead_ms: float, release_ms: float, ceiling_db: float) -> LimiterDesign:
+    """fmd_limiter_design (host only): D = llround(lookahead_ms * fs / 1000) in [0, 255], step = clamp(llround(2^30 / (release_ms * fs / 1000)), 1, 2^30)
+    (release_ms = 0: 2^30), T = (float)10^(ceiling_db / 20) with ceiling_db in [-40, 0], and the latency, D frames"""
+    L = load_library()
+    out = LimiterDesign()
+    rc = L.fmd_limiter_design(int(fs), float(lookahead_ms), float(release_ms), float(ceiling_db), C.byref(out))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_limiter", rc)
+    return out
+
+
+def limiter_default_config(fs: int, **fields) -> LimiterConfig:
+    """fmd_limiter_default_config (host only): one station, 1.5 ms look-ahead, 500 ms release, -1 dBFS ceiling (conventional values, not
+    tuned by listening); `fields` then replace the named fields"""
+    L = load_library()
+    cfg = LimiterConfig()
+    rc = L.fmd_limiter_default_config(int(fs), C.byref(cfg))
+    if rc != FMD_OK:
+        raise _global_error(L, "fmd_limiter", rc)
+    for k, v in fields.items():
+        if k not in dict(LimiterConfig._fields_):
+            raise TypeError(f"LimiterConfig has no field {k}")
+        setattr(cfg, k, v)
+    return cfg
+
+
+def limiter_gain_for_loudness(lufs: float, target_lufs: float = -23.0) -> float:
+    """fmd_limiter_gain_for_loudness (host only): 10^((target_lufs - lufs) / 20) as a float: what takes meter_integrated's result to
+    Limiter.set_gain"""
+    return float(load_library().fmd_limiter_gain_for_loudness(float(lufs), float(target_lufs)))
+
+
+class Limiter(_Monitor):
+    """Look-ahead peak limiter of C stations' (or buses') stereo audio on the GPU (fmd_limiter_*): a gain per station and a brick-wall
+    ceiling.  Feed it the same [C, n, 2] float32 CUDA tensors as AudioMixer, the monitors and the encoders; it changes nothing in them.
+    process() returns the [C, n, 2] float32 output, the input delayed by `latency` frames; flush() pushes the last `latency` frames out.
+    status() returns LIMITER_STATUS_DTYPE records."""
+    _prefix, _attr, _status_dtype = "fmd_limiter", "l", LIMITER_STATUS_DTYPE
+
+    def __init__(self, n_channels: int, fs: int = 32000, lookahead_ms: float = 1.5, release_ms: float = 500.0, ceiling_db: float = -1.0,
+                 max_input_frames: int = 1 << 16, device: int = -1):
+        cfg = LimiterConfig(int(n_channels), int(fs), float(lookahead_ms), float(release_ms), float(ceiling_db), int(max_input_frames), device)
+        self._create("create", C.byref(cfg))
+        self.n_channels = int(n_channels)
+        self.design = limiter_design(fs, lookahead_ms, release_ms, ceiling_db)
+
+    @property
+    def latency(self) -> int:
+        """frames by which the output trails the input: D"""
+        return int(self.design.latency_frames)
+
+    def reset_peaks(self, channel: int = -1):
+        raise AttributeError("the limiter holds no peaks")
+
+    def set_gain(self, gain: float, channel: int = -1):
+        """fmd_limiter_set_gain: the gain of station `channel` (-1 = of every station), finite and >= 0, for the frames later calls take"""
+        self._check(self.L.fmd_limiter_set_gain(self.l, int(channel), float(gain)))
+
+    def get_gain(self, channel: int) -> float:
+        g = C.c_float(0.0)
+        self._check(self.L.fmd_limiter_get_gain(self.l, int(channel), C.byref(g)))
+        return float(g.value)
+
+    def _out(self, out, rows: int, device, stream):
+        """(out, its pointer, out_stride): out None = a new zeroed [C, rows, 2] tensor"""
+        import torch
+        if out is None:
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device) if stream else torch.cuda.default_stream(device)):
+                out = torch.zeros((self.n_channels, max(rows, 1), 2), dtype=torch.float32, device=device)
+        if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and out.shape[0] == self.n_channels and out.shape[2] == 2 and out.stride(2) == 1
+                and out.stride(1) == 2):
+            raise ValueError("out must be a [C, >= n, 2] float32 CUDA tensor with contiguous frames")
+        if out.shape[1] < rows:
+            raise ValueError(f"out's rows hold {out.shape[1]} frames; the call writes {rows}")
+        return out, C.c_void_p(out.data_ptr()), out.stride(0) // 2 if self.n_channels > 1 else out.shape[1]
+
+    def process(self, x, n: int | None = None, active=None, out=None, gr=False, stream=None):
+        """takes the first n frames (default all) of x: [C, >= n, 2] float32 on the device, contiguous frames; active: None or a [C]
+        uint8 / bool CUDA tensor (a station whose byte is 0 is skipped whole: its state, its row of out and its gr are kept); out: the
+        [C, >= n, 2] float32 CUDA tensor to write (frames behind n are kept), None = a new zeroed one of n frames; gr: False = not
+        written, True = a new [C] float32 tensor, or the tensor to write: the smallest gain among the call's output frames.  Returns
+        out, or (out, gr) where gr was asked for.  Asynchronous on `stream` (default: torch's current)."""
+        import torch
+        px, in_stride, n = _batch_input(x, self.n_channels, n, ("float32",), "frames")
+        pa, stream = _active_ptr(active, self.n_channels), _stream_ptr(stream, x.device)
+        out, po, stride = self._out(out, max(n, 0), x.device, stream)
+        pg = None
+        if gr is True:
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=x.device) if stream else torch.cuda.default_stream(x.device)):
+                gr = torch.ones(self.n_channels, dtype=torch.float32, device=x.device)
+        if gr is not False and gr is not None:
+            if not (gr.is_cuda and gr.dtype == torch.float32 and gr.shape == (self.n_channels,) and gr.is_contiguous()):
+                raise ValueError("gr must be a contiguous [C] float32 CUDA tensor")
+            pg = C.c_void_p(gr.data_ptr())
+        self._check(self.L.fmd_limiter_process_f32_dev(self.l, px, in_stride, n, pa, po, stride, pg, C.c_void_p(stream)))
+        return out if pg is None else (out, gr)
+
+    def flush(self, channel: int = -1, out=None, nout=None, stream=None, device=None):
+        """fmd_limiter_flush: the `latency` frames that as many frames of silence push out of station `channel` (-1 = of every station), at
+        out[c], and their number in nout[c] (None = a new [C] int32 tensor, False = not written); then the station's signal state is as
+        after a reset, counters and gain kept.  Returns (out, nout)."""
+        import torch
+        device = device if device is not None else (out.device if out is not None else torch.device("cuda", torch.cuda.current_device()))
+        stream = _stream_ptr(stream, device)
+        out, po, stride = self._out(out, self.latency, device, stream)
+        pn = None
+        if nout is None:
+            with torch.cuda.stream(torch.cuda.ExternalStream(stream, device=device) if stream else torch.cuda.default_stream(device)):
+                nout = torch.zeros(self.n_channels, dtype=torch.int32, device=device)
+        if nout is False:
+            nout = None
+        else:
+            if not (nout.is_cuda and nout.dtype == torch.int32 and nout.shape == (self.n_channels,) and nout.is_contiguous()):
+                raise ValueError("nout must be a contiguous [C] int32 CUDA tensor")
+            pn = C.c_void_p(nout.data_ptr())
+        self._check(self.L.fmd_limiter_flush(self.l, int(channel), po, stride, pn, C.c_void_p(stream)))
+        return out, nout
+
+    def debug_set_frames(self, channel: int, frames: int):
+        """fmd_limiter_debug_set_frames (include/fmdemod_limiter_debug.h): a test's way to a frame count past 2^32"""
+        self._check(self.L.fmd_limiter_debug_set_frames(self.l, int(channel), int(frames)))

@@ -2066,6 +2066,106 @@ int fmd_fpmatch_status_dev(fmd_fpmatch h, const fmd_fpmatch_status** d_status);
 int fmd_fpmatch_get_index_status(fmd_fpmatch h, fmd_fpmatch_index_status* out);
 const char* fmd_fpmatch_last_error(fmd_fpmatch h);
 
+/* ------------------------------------------------------------------------------------------------------------------
+ * Look-ahead peak limiter (NOT part of the reference): the stage that acts on a level.  A make-up gain per station and a brick-wall
+ * look-ahead limiter with a ceiling, behind the loudness measurement as EBU R 128 practice has it.  It reads the device array
+ * [C][in_stride][2] f32 (interleaved L, R) that the mixer, the monitors and the encoders read (station audio or a mixer's bus output),
+ * changes nothing in it, and writes a caller-owned [C][out_stride][2] f32 array: the same audio, delayed by D frames, times the
+ * station's gain, limited to the ceiling T.  Stereo only, fs 8000 ... 192000 Hz.  Sample peaks, not true peaks.
+ * Arithmetic, restated in C by tests/cpp/limiter_ref.c.  Per station the frame index n counts from the station's reset or flush;
+ * ONE = 2^30;  W = D + 1;  everything from before index 0 counts as silence at unity gain: u = 0, rq = mq = eq = ONE.
+ *   gain        u[n] = x[n] * gain                              one fp32 multiply per rail, round to nearest, with the station's gain as it
+ *               stands when the call is made.  A rail value that is NaN or +-inf after the multiply becomes +0, nonfinite++ (per sample)
+ *   peak        p[n] = max(|uL[n]|, |uR[n]|)                    linked: both rails get one gain, the stereo image holds still
+ *   required    rq[n] = ONE where p[n] <= T, else (uint32)((T / p[n]) * 2^30f): the correctly rounded fp32 division (no reciprocal
+ *               approximation), an exact multiply, a truncating conversion.  fp32 denormals are kept
+ *   look-ahead  mq[n] = min(rq[n - W + 1 ... n])
+ *   release     eq[n] = min(mq[n], eq[n - 1] + step), in integers, eq[-1] = ONE: a gain that recovers on a straight line, step per
+ *               frame.  Closed form, exact in int64, with eq_in the eq just before the span's first frame (index 0 of the span):
+ *                 eq[n] = min(eq_in + (n + 1) * step, min over j <= n of (mq[j] + (n - j) * step))
+ *   attack      S[n] = sum of eq[n - W + 1 ... n], exact in uint64;  g[n] = (float)S[n] / (float)(W * 2^30): the conversion rounds to
+ *               nearest, the division is the correctly rounded fp32 division.  g[n] = 1.0f exactly where nothing in reach is over T
+ *   output      y[n] = u[n - D] * g[n] per rail, one fp32 multiply;  then y > T -> T and y < -T -> -T, each with the rail's clamped++
+ *               (the roundings of T / p and of g can leave a product one ulp over).  limited++ where S[n] < W * ONE
+ *   ceiling     |y| <= T always: every eq under the sum is at most rq[n - D], so g[n] <= rq[n - D] / ONE before rounding
+ *   transparent where no frame in [n - 2D, n] exceeds T after the gain and the release has returned to ONE, y[n] is u[n - D] bit for bit
+ *   streaming   eq, the last D values of rq and of eq and the last D frames of u live in the limiter and carry to the next call.  Every
+ *               scan is in integers: nothing depends, bit for bit, on how the frames are split into calls, on streams, on the batch or
+ *               on the station's row.  Ordinary stores, no atomics.
+ *   flush       writes the D frames that D frames of silence would push out, and D to d_nout[c];  they count in limited, clamped and
+ *               min_gain, not in frames.  Then the station's signal state is as after reset; counters and gain stay.  A whole
+ *               stream's output is therefore D zero frames followed by the limited input, frames + D in all.
+ *   design      host, double, host libm (fmd_limiter_design):  D = llround(lookahead_ms * fs / 1000), in [0, 255];
+ *               step = clamp(llround(2^30 / (release_ms * fs / 1000)), 1, 2^30), release_ms = 0 gives 2^30 (an instant release):
+ *               release_ms is the time the gain needs from 0 to 1;  T = (float)pow(10, ceiling_db / 20), ceiling_db in [-40, 0].
+ *               The defaults (1.5 ms, 500 ms, -1 dBFS: a 3 dB reduction recovers in about 150 ms) are conventional values; nobody
+ *               has tuned them by listening.
+ * ------------------------------------------------------------------------------------------------------------------ */
+typedef struct fmd_limiter_s* fmd_limiter;
+typedef struct {
+    int       n_channels;         /* C: station rows of the input and the output */
+    int       fs;                 /* Hz, 8000 ... 192000 */
+    double    lookahead_ms;       /* D = llround(lookahead_ms * fs / 1000) frames, at most 255 */
+    double    release_ms;         /* the time the gain needs from 0 to 1; 0 = instant */
+    double    ceiling_db;         /* dBFS, -40 ... 0 */
+    long long max_input_frames;   /* largest n of a process call, in (0, 2^30] */
+    int       device;             /* HIP device ordinal, -1 = current */
+} fmd_limiter_config;
+typedef struct {
+    int      lookahead_frames;    /* D */
+    unsigned step;                /* Q30 per frame, 1 ... 2^30 */
+    float    ceiling;             /* T */
+    int      latency_frames;      /* D */
+} fmd_limiter_design_t;
+/* one per station, 64 bytes: frames at byte 0, limited 8, clamped 16, nonfinite 32, min_gain 40, gain 44, eq 48, reserved 52 */
+typedef struct {
+    unsigned long long frames;        /* frames taken since reset */
+    unsigned long long limited;       /* output frames with S < W * ONE */
+    unsigned long long clamped[2];    /* output samples of L, R moved back to +-T */
+    unsigned long long nonfinite;     /* samples (of either rail) that were NaN or +-inf after the gain: taken as +0 */
+    float              min_gain;      /* the smallest g since reset; 1 after a reset */
+    float              gain;          /* the station's gain, as set */
+    unsigned           eq;            /* the release state, Q30 */
+    unsigned char      reserved[12];
+} fmd_limiter_status;
+
+/* host-only (no GPU needed) */
+/* D, step, T and the latency as `design` above says; FMD_ERR_ARG for fs outside 8000 ... 192000, a look-ahead above 255 frames, a
+ * negative time or ceiling_db outside [-40, 0] */
+int fmd_limiter_design(int fs, double lookahead_ms, double release_ms, double ceiling_db, fmd_limiter_design_t* out);
+/* one station, 1.5 ms look-ahead, 500 ms release, -1 dBFS ceiling, max_input_frames 65536, the current device */
+int fmd_limiter_default_config(int fs, fmd_limiter_config* cfg);
+/* 10^((target_lufs - lufs) / 20) as a float: what takes fmd_meter_integrated's result to fmd_limiter_set_gain */
+float fmd_limiter_gain_for_loudness(double lufs, double target_lufs);
+
+int fmd_limiter_create(const fmd_limiter_config* cfg, fmd_limiter* out);
+int fmd_limiter_destroy(fmd_limiter l);
+/* station `channel` (-1 = every station) as after create, except that its gain stays.  Waits for the limiter's earlier work */
+int fmd_limiter_reset(fmd_limiter l, int channel);
+/* the gain of station `channel` (-1 = of every station): finite and >= 0, else FMD_ERR_ARG; 1 after create.  It holds for the frames
+ * that later calls take; waits for the limiter's earlier work */
+int fmd_limiter_set_gain(fmd_limiter l, int channel, float gain);
+int fmd_limiter_get_gain(fmd_limiter l, int channel, float* gain);
+/* takes n frames of every station and writes n output frames at d_out + c * out_stride.  d_in [C][in_stride][2] f32 and d_out
+ * [C][out_stride][2] f32 on the device, 8-byte aligned, strides in frames; frames of d_out behind n are left as they are.  d_active:
+ * [C] uint8 on the device, NULL = all: a station whose byte is 0 is skipped whole, its state, its row of d_out and its d_gr are left
+ * as they are.  d_gr: [C] f32 on the device, may be NULL: the smallest g among the call's output frames, 1.0f for n = 0.  n < 0,
+ * n > in_stride, n > out_stride, n > max_input_frames, a null or misaligned d_in or d_out, or an output range (d_out up to row C - 1's
+ * frame n) that overlaps the input's range return FMD_ERR_ARG and change nothing.  Asynchronous on `stream`; consecutive calls may use different streams (the library orders
+ * them). */
+int fmd_limiter_process_f32_dev(fmd_limiter l, const float* d_in, long long in_stride, long long n, const uint8_t* d_active, float* d_out,
+                                long long out_stride, float* d_gr, void* stream);
+/* station `channel` (-1 = every station) as `flush` above says: D frames at d_out + c * out_stride and D in d_nout[c] ([C] int32 on
+ * the device, may be NULL); other stations' rows and counts are left as they are.  d_out 8-byte aligned and out_stride at least D, else
+ * FMD_ERR_ARG.  Asynchronous on `stream`, ordered like a process call */
+int fmd_limiter_flush(fmd_limiter l, int channel, float* d_out, long long out_stride, int* d_nout, void* stream);
+/* out [C]; synchronises with the limiter's work */
+int fmd_limiter_get_status(fmd_limiter l, fmd_limiter_status* out);
+/* the device's own [C] records, for a consumer on the device: ordered behind the limiter's work on the stream of its last call, valid
+ * until the next call */
+int fmd_limiter_status_dev(fmd_limiter l, const fmd_limiter_status** d_status);
+const char* fmd_limiter_last_error(fmd_limiter l);
+
 #ifdef __cplusplus
 }
 #endif
